@@ -121,10 +121,19 @@ def parse():
                          "auto = where the lone-batch launch chain is used (single_stream, --streams 1), off = the composition everywhere")
     ap.add_argument("--shared-inputs", action="store_true",
                     help="diagnostic: all in-flight slots read the SAME input tensors (round 1 behaviour)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step computed as DIR/<name>.npy (float32 or "
+                         "float64): y, its audio, and for golf-ss-train, golf-ff-train and golf-ss-decoder-train the gradients "
+                         "w.r.t. the step's inputs (grad_<input>); N>1: every rank its shard, <name>_rank<r>.npy.  At most %d MB "
+                         "for the whole job: beyond that, the same seeded sample of batch rows of every array, their indices in "
+                         "DIR/rows.npy.  The line's dumped_outputs names the slot (input seed) the step ran on.  "
+                         "golf-ss-train-step updates its weights every step: its dump also depends on how many steps ran"
+                         % (DUMP_BYTES // 10 ** 6))
     return ap.parse_args()
 
 
 FUSE_SOURCE_MAPS = "auto"   # --fuse-source-maps
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: bytes written by the whole job, at most
 PROFILE_ROUND = "r06"       # profiles/<round>_hbm_traffic.json / _sq_counters_4stream.json: the counter passes of THIS round's kernels
 
 
@@ -213,6 +222,10 @@ def make_step(workload, inp, osc, ss, ff, fast=True, overlap=False, mode=None):
                 t.grad = None
             y.backward(gy)
             return y
+
+        if train:
+            step.grads = lambda: {"grad_gain": gain.grad, "grad_a": a.grad, "grad_wsel": wsel_g.grad, "grad_log_mag": lm.grad,
+                                  "grad_room_kernel": rk.grad}
     elif workload == "ddsp-decoder":  # cfg/ae/decoder/ddsp.yaml: 155-harmonic additive synth + filtered noise + room
         from golf_amd.synthetic import make_harmonic_amplitudes
 
@@ -298,6 +311,8 @@ def make_step(workload, inp, osc, ss, ff, fast=True, overlap=False, mode=None):
             gain_g.grad = a_g.grad = w_g.grad = None
             y.backward(gy[:, : y.shape[1]])
             return y
+
+        step.grads = lambda: {"grad_gain": gain_g.grad, "grad_a": a_g.grad, "grad_wsel": w_g.grad}
     else:  # golf-ss-train: forward + custom backward w.r.t. gain, a, table_select_weight
         gain_g = gain.clone().requires_grad_(True)
         a_g = a.clone().requires_grad_(True)
@@ -312,6 +327,9 @@ def make_step(workload, inp, osc, ss, ff, fast=True, overlap=False, mode=None):
             y.backward(gy[:, : y.shape[1]])
             return y
 
+        step.grads = lambda: {"grad_gain": gain_g.grad, "grad_a": a_g.grad, "grad_wsel": w_g.grad}
+
+    # step.grads (training workloads): () -> {name: .grad of each input the step differentiates}, what its caller receives
     y = step()
     return step, int(y.shape[0] * y.shape[1]), y.shape[1]
 
@@ -470,6 +488,33 @@ def stream_set_time(streams, issue):
     return wall, max(e0.elapsed_time(e) for e in ends) * 1e-3
 
 
+def dump_outputs(out_dir, outputs, rank=0, world=1, seed=2434):
+    """--dump-outputs: the tensors of ``outputs`` (name -> tensor, the first one batch-major) as out_dir/<name>.npy, float64 as
+    float64 and anything else as float32; N>1: out_dir/<name>_rank<r>.npy, each rank's shard.  DUMP_BYTES bounds the whole
+    job, so a rank writes at most DUMP_BYTES // world.  Over that, every array whose rows are the batch's is cut to the same
+    seeded sample of rows (the same rows for the same shapes), their indices in out_dir/rows[_rank<r>].npy, so that two builds
+    run with the same arguments compare file for file.  Returns {file name: shape written}."""
+    budget, sfx, header = DUMP_BYTES // world, "" if world == 1 else "_rank%d" % rank, 256   # header: an .npy header, at most
+    arrays = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        arrays[name + sfx] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    if sum(a.nbytes + header for a in arrays.values()) > budget:
+        B = next(iter(arrays.values())).shape[0]
+        batch = [k for k, a in arrays.items() if a.ndim and a.shape[0] == B]
+        fixed = sum(a.nbytes for k, a in arrays.items() if k not in batch) + header * (len(arrays) + 1)
+        n = min(B, (budget - fixed) // (sum(arrays[k][0].nbytes for k in batch) + 8))   # + 8: a row's float64 index
+        if n < 1:
+            raise ValueError(f"--dump-outputs: not one batch row of {list(arrays)} fits in {budget} bytes")
+        rows = np.sort(np.random.default_rng(seed).choice(B, n, replace=False))
+        arrays = {k: (a[rows] if k in batch else a) for k, a in arrays.items()}
+        arrays["rows" + sfx] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def smi_clocks():
     """Shader / memory clock and power state of device 0 as rocm-smi reports them right now (None if the tool is missing):
     recorded before the first and after the last timed region, so that a run that comes out slow in ALL its regions (one in
@@ -514,6 +559,11 @@ def main():
     FUSE_SOURCE_MAPS = args.fuse_source_maps
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
+    # the draws that take no generator of their own (upstream gradients of the training workloads, module initialisation):
+    # the same arguments give the same inputs in every run (--dump-outputs compares builds on them)
+    torch.manual_seed(2434)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         have = torch.cuda.device_count()
         if have < args.gpus and not args.single_device:
@@ -625,7 +675,7 @@ def main():
     # a serving loop keeps several batches in flight on separate HIP streams, each step replayed as ONE hipGraph
     # (8 kernels + allocator traffic -> one launch).  Every step does the full work and writes its own output.
     use_graphs = not args.no_graphs  # training steps (forward + custom backward) are captured whole, like inference
-    graphs, outs = [], []
+    graphs, outs, out_grads = [], [], []
     g_lat = None
     if use_graphs:
         for i in range(S):
@@ -640,6 +690,8 @@ def main():
                 yg = steps_fn[i]()
             graphs.append(g)
             outs.append(yg)
+            # the gradients the captured backward writes on every replay (the eager check below rebinds the inputs' .grad)
+            out_grads.append(steps_fn[i].grads() if hasattr(steps_fn[i], "grads") else {})
         torch.cuda.synchronize()
         for i in range(S):   # every slot's replay equals an eager call on that slot's inputs, bit for bit
             ref = steps_fn[i]()
@@ -706,6 +758,7 @@ def main():
         torch.cuda.synchronize()
 
     step_no = [0]
+    last_slot = [None]   # the slot of the last step issued (--dump-outputs)
     refresh_pool = [None]   # --refresh-inputs: packed batches (device or pinned host) copied into the slot before every replay
     gather_on = [True]      # N > 1: the same regions once more without the exchange (exchange.ms_per_step_no_gather)
 
@@ -725,6 +778,7 @@ def main():
         else:
             i = step_no[0] % S
         step_no[0] += 1
+        last_slot[0] = i
         with torch.cuda.stream(streams[i]):
             if refresh_pool[0] is not None:   # ordered on the slot's stream: after its previous replay, before this one
                 slot_flat[i].copy_(refresh_pool[0][step_no[0] % len(refresh_pool[0])], non_blocking=True)
@@ -755,9 +809,12 @@ def main():
 
             dist.barrier()
 
+    last_out = [None]   # what the last step of the last region issued returned (--dump-outputs)
+
     def issue_region():
         for _ in range(args.steps):
-            full_step()
+            y = full_step()
+        last_out[0] = y
         drain()  # every gather issued inside the timed region completes inside it
 
     def timed_regions(n):
@@ -805,7 +862,18 @@ def main():
             spent = float(t.item())
         if spent > 0.3:
             break
+    # the headline's regions start on slot 0: the settling regions before them are counted by time, and with round-robin issue
+    # the slot of the last timed step (--dump-outputs) then follows from the arguments alone
+    step_no[0] = 0
     regions = timed_regions(args.repeats)
+    # --dump-outputs: the last timed step's results, copied on the device (the passes below replay the same graphs); written
+    # to disk after the last measurement of this rank, so that no host pause falls in front of a timed pass
+    dump = None
+    if args.dump_outputs:
+        s_last = last_slot[0]
+        grads = (out_grads[s_last] if use_graphs else steps_fn[s_last].grads()) if hasattr(steps_fn[s_last], "grads") else {}
+        dump = {k: v.detach().clone() for k, v in dict(y=last_out[0], **grads).items()}
+        dump_slot = {"slot": s_last, "input_seed": 2434 + (0 if args.shared_inputs else s_last)}
     gc.enable()
     clocks_after = smi_clocks() if rank == 0 else None
     walls = sorted(w for w, _ in regions)
@@ -1197,8 +1265,12 @@ def main():
                 result["speedup_vs_cpu_port"] = value / result["cpu_baseline"]["value"]
             except Exception as e:  # the checker is optional for the measurement itself
                 result["cpu_baseline"] = {"error": repr(e)}
-        if not (do_gather and not args.no_compare_gather_modes):
-            print(json.dumps(result), flush=True)
+    if dump is not None:
+        written = dump_outputs(args.dump_outputs, dump, rank, world)
+        if result is not None:   # (N>1: rank 0's files and slot)
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": written, **dump_slot}
+    if rank == 0 and not (do_gather and not args.no_compare_gather_modes):
+        print(json.dumps(result), flush=True)
     if world > 1:
         import torch.distributed as dist
 

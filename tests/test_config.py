@@ -1,9 +1,8 @@
 """The reference's plugin surface is YAML (``class_path`` + ``init_args``): the same trees must build on
 this package's classes.  The YAML below is written for this test in the shape of the reference's decoder / model files
-(cfg/ae/decoder/golf*.yaml, ckpts/interspeech24/*/config.yaml); when the reference checkout is present (this container
-only) its own shipped files are instantiated as well."""
+(cfg/ae/decoder/golf*.yaml, ckpts/interspeech24/*/config.yaml); the reference's own shipped files are instantiated as
+well, from their parsed values stored in golden g28 (oracle/make_config_fixtures.py)."""
 import glob
-import os
 
 import numpy as np
 import pytest
@@ -118,7 +117,6 @@ def test_unknown_class_is_reported():
         build_model({"decoder": {"class_path": "models.filters.LTVMLSAFilter", "init_args": {}}})
 
 
-REF = "/root/reference"
 GOLF_FILES = ["cfg/ae/decoder/golf.yaml", "cfg/ae/decoder/golf-precise.yaml", "cfg/ae/decoder/golf-v1.yaml",
               "cfg/ae/decoder/ddsp.yaml", "ckpts/interspeech24/golf-ss/config.yaml",
               "ckpts/interspeech24/golf-ff/config.yaml", "ckpts/interspeech24/golf-v1/config.yaml",
@@ -131,14 +129,15 @@ ISMIR_SPLITS = {"glottal_d": ((64,), (), (1, 22), (1, 22), ()), "ddsp": ((1, 150
                 "pulse": ((), (), (1, 26), (1, 22), ()), "sawsing": ((), (), (256,), (80,), ())}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("rel", GOLF_FILES)
-def test_shipped_golf_configs_instantiate(rel):
+def test_shipped_golf_configs_instantiate(rel, golden):
     """Every GOLF / DDSP / NHV / WORLD config the reference ships builds unchanged (the MLSA baseline needs diffsptk's
     MLSA filter, which is out of scope and raises NotImplementedError, see test_unknown_class_is_reported)."""
     from golf_amd.config import build_model
 
-    model = build_model(os.path.join(REF, rel))
+    g = golden("g28_shipped_configs")
+    assert list(g["path"]) == GOLF_FILES
+    model = build_model(str(g["config"][GOLF_FILES.index(rel)]))
     dec = getattr(model, "decoder", model)
     if "ismir23" in rel:   # ISMIR'23 models: the decoder of each (the Lightning module around it is control plane)
         assert dec.split_sizes_and_trsfms[0] == ISMIR_SPLITS[rel.split("/")[2].rsplit("_", 1)[0]]
