@@ -36,6 +36,7 @@ SIGNATURES = {
     "golf_ltv_allpole_transitions_f32": (_int, [_c_f32p] + [_int] * 5 + [_vp, _sz, _int, _vp]),
     "golf_ltv_allpole_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 5
                                  + [_vp, _sz, _int, _vp, _vp]),
+    "golf_ltv_allpole_fwd_state_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 5 + [_c_f32p, _vp]),
     "golf_ltv_allpole_status_u32": (_int, [_vp, _sz] + [_int] * 6 + [_vp, _vp]),
     "golf_ltv_allpole_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64,
                                         _c_f32p, _c_f32p] + [_int] * 5 + [_vp, _sz, _int, _vp]),
@@ -75,6 +76,8 @@ SIGNATURES = {
     "golf_phase_accumulate_workspace_bytes": (_sz, [_int] * 2),
     "golf_phase_accumulate_f32": (_int, [_c_f32p, _i64, _int, _int, _int, _c_f32p, _i64, _c_f32p, _i64, _int, _int, _vp,
                                          _sz, _vp]),
+    "golf_glottal_osc_stream_f32": (_int, [_c_f32p, _i64, _int, _int, _int, _int, _c_f32p, _i64, _int, _i64, _int, _c_f32p,
+                                           _int, _int, _int, _i64, _vp, _c_f32p, _i64, _c_f32p, _int, _vp]),
     "golf_decimate_fir_f32": (_int, [_c_f32p, _i64, _int, _c_f32p, _int, _int, _c_f32p, _i64, _int, _int, _vp]),
     "golf_decimate_fir_adj_f32": (_int, [_c_f32p, _i64, _int, _c_f32p, _int, _int, _c_f32p, _int, _int, _vp]),
     "golf_noise_band_workspace_bytes": (_sz, [_int] * 3),

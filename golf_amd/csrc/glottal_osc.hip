@@ -2570,7 +2570,119 @@ __global__ __launch_bounds__(256) void osc_wrapped_phase_kernel(const float* __r
     }
     out[(size_t)b * out_stride + n] = (float)((double)Phi * 5.421010862427522e-20);   // * 2^-64
 }
+
+
+// =============================================================================================
+// Streaming oscillator (golf_glottal_osc_stream_f32): the fine-rate signal of a run of coarse phase samples from a carried
+// Q0.64 phase.  One workgroup per utterance walks the run in tiles of 256 coarse samples: the segment totals (the one-shot
+// scan's own integers, osc_phase_tile_kernel) are scanned across the workgroup and added to the carry, then every thread renders
+// its segment's P fine samples as osc_render_kernel does -- the blended table rows are formed per sample instead of staged in
+// LDS, since a streaming call covers a few hundred samples per utterance and no interval's worth.
+// =============================================================================================
+__global__ __launch_bounds__(256) void osc_stream_kernel(const float* __restrict__ phase, int64_t phase_stride, int nseg,
+                                                         int final_point, int P, int os, const float* __restrict__ wsel,
+                                                         int64_t wsel_stride, int nw, int64_t w_first, int hop_t,
+                                                         const float* __restrict__ table, int n_tab, int L, int equal_energy,
+                                                         int64_t j0, u64* __restrict__ acc, float* __restrict__ pre,
+                                                         int64_t pre_stride, float* __restrict__ wrapped) {
+    __shared__ u64 wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* pb = phase + (size_t)b * phase_stride;
+    const float* wb = wsel + (size_t)b * wsel_stride;
+    float* ob = pre + (size_t)b * pre_stride;
+    float* qb = wrapped ? wrapped + (size_t)b * pre_stride : nullptr;
+    const double scale_a = 18446744073709551616.0 / (double)os, scale_d = scale_a / (double)P;
+    const u64 tri = (u64)P * (u64)(P - 1) / 2;
+    const float inv_hop_t = 1.0f / (float)hop_t, inv_P = 1.0f / (float)P, inv_osf = 1.0f / (float)os;
+    const int lshift = (L & (L - 1)) == 0 ? 31 - __clz(L) : -1;
+    const int64_t w_last = w_first + nw - 1;
+    u64 carry = acc[b];
+    const int nall = nseg + final_point;
+    for (int base = 0; base < nall; base += 256) {
+        const int i = base + tid;
+        const bool act = i < nall, fin = i == nseg;   // fin: the utterance's last point (k = 0 only, d = 0)
+        const float p0 = act ? pb[i] : 0.f;
+        const float p1 = act && !fin ? pb[i + 1] : p0;
+        const u64 a = osc_fix_a(p0, scale_a), d = osc_fix_d(p0, p1, scale_d);
+        const u64 seg = act && !fin ? (u64)P * a + d * tri : 0;
+        const u64 incl = wave_incl_scan(seg, lane);
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        u64 ph = carry + incl - seg, tot = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wv) ph += wsum[w];
+            tot += wsum[w];
+        }
+        __syncthreads();
+        carry += tot;
+        if (!act) continue;
+        const int64_t mb = (j0 + i) * (int64_t)P;
+        const float dpf = (p1 - p0) * inv_P;
+        u64 inc = a;
+        const int cnt = fin ? 1 : P;
+        for (int k = 0; k < cnt; ++k) {
+            ph += inc;   // inclusive cumulative phase of fine sample mb + k
+            inc += d;
+            const int64_t m = mb + k;
+            const unsigned hi = (unsigned)(ph >> 32);
+            int c0;
+            float cf;
+            if (lshift >= 0) {
+                c0 = (int)(hi >> (32 - lshift));
+                cf = (float)((hi << lshift) >> 8) * (1.0f / 16777216.0f);
+            } else {
+                const u64 pos = (u64)hi * (u64)L;
+                c0 = (int)(pos >> 32);
+                cf = (float)((unsigned)pos >> 8) * (1.0f / 16777216.0f);
+            }
+            const int c1 = c0 + 1 == L ? 0 : c0 + 1;
+            const int64_t r0 = m / hop_t;
+            const float rf = (float)(int)(m - r0 * hop_t) * inv_hop_t;
+            float v[2][2];
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) {
+                const int64_t r = r0 + rr < w_last ? r0 + rr : w_last;
+                const float idx = wb[r - w_first] * (float)(n_tab - 1);
+                int t0 = (int)idx;
+                t0 = t0 < 0 ? 0 : (t0 > n_tab - 2 ? n_tab - 2 : t0);
+                const float pw = idx - (float)t0;
+                const float* ta = table + (size_t)t0 * L;
+                v[rr][0] = ta[c0] * (1.0f - pw) + ta[L + c0] * pw;
+                v[rr][1] = ta[c1] * (1.0f - pw) + ta[L + c1] * pw;
+            }
+            const float top = fmaf(cf, v[0][1] - v[0][0], v[0][0]);
+            const float bot = fmaf(cf, v[1][1] - v[1][0], v[1][0]);
+            const float scale = equal_energy ? rsqrtf(fmaf((float)k, dpf, p0) * inv_osf) : 1.0f;
+            ob[(size_t)i * P + k] = fmaf(rf, bot - top, top) * scale;
+            if (qb) qb[(size_t)i * P + k] = (float)((double)ph * 5.421010862427522e-20);   // * 2^-64, as osc_wrapped_phase_kernel
+        }
+    }
+    if (tid == 0) acc[b] = carry;
+}
 }  // namespace golf
+
+extern "C" int golf_glottal_osc_stream_f32(const float* phase, int64_t phase_stride, int nseg, int final_point, int phase_hop,
+                                           int os, const float* wsel, int64_t wsel_stride, int nw, int64_t w_first, int w_hop,
+                                           const float* table, int n_tab, int L, int equal_energy, int64_t j0, uint64_t* acc,
+                                           float* pre, int64_t pre_stride, float* wrapped, int B, void* stream) {
+    using namespace golf;
+    if (!phase || !wsel || !table || !acc || !pre) return fail(GOLF_EINVAL, "glottal_osc_stream: null pointer");
+    if (B < 1 || nseg < 0 || (final_point != 0 && final_point != 1) || nseg + final_point < 1 || phase_hop < 1 || os < 1 ||
+        nw < 1 || w_first < 0 || w_hop < 1 || n_tab < 2 || L < 2 || j0 < 0)
+        return fail(GOLF_EINVAL, "glottal_osc_stream: bad argument");
+    const int64_t P = (int64_t)phase_hop * os, n = nseg * P + final_point, hop_t = (int64_t)w_hop * os;
+    if (n > (int64_t)1 << 30 || hop_t > (int64_t)1 << 30) return fail(GOLF_EINVAL, "glottal_osc_stream: call too long");
+    if (phase_stride < nseg + 1 || wsel_stride < nw || pre_stride < n)
+        return fail(GOLF_EINVAL, "glottal_osc_stream: row stride too small");
+    if (j0 * P / hop_t < w_first)
+        return fail(GOLF_EINVAL, "glottal_osc_stream: table-select row %lld is needed but the rows start at %lld",
+                    (long long)(j0 * P / hop_t), (long long)w_first);
+    hipLaunchKernelGGL(osc_stream_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, phase, phase_stride, nseg, final_point,
+                       (int)P, os, wsel, wsel_stride, nw, w_first, (int)hop_t, table, n_tab, L, equal_energy, j0, (u64*)acc,
+                       pre, pre_stride, wrapped);
+    GOLF_LAUNCH_CHECK();
+    return GOLF_OK;
+}
 
 extern "C" size_t golf_phase_accumulate_workspace_bytes(int B, int Tp) {
     if (B < 1 || Tp < 1) return 0;

@@ -445,12 +445,14 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_row(float v) {   // row-level DPP move (row_shr / row_half_mirror): every lane has a source or reads 0
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
-template <int W, int NT, int LPU>
+// STATE (golf_ltv_allpole_fwd_state_f32): y[<0] comes from state (B, M), state[b][i] = y[b][-1-i], loaded into the ring before the
+// time loop; after it the block's last M outputs (read back from y) replace it.  The time loop itself is the same either way.
+template <int W, int NT, int LPU, bool STATE = false>
 __device__ __forceinline__ void serial_fwd_unit(int unit, float* __restrict__ xt, float* __restrict__ yt,
                                                 const float* __restrict__ ex, int64_t ex_stride,
                                                 const float* __restrict__ gain, const float* __restrict__ a,
                                                 float* __restrict__ y, int64_t y_stride, int B, int T, int F, int M,
-                                                int hop) {
+                                                int hop, float* state = nullptr) {
     static_assert(LPU == 4 || LPU == 8, "a quad or half a DPP row per utterance");
     constexpr int ROWS = 64 / LPU;
     constexpr int TPL = LPU == 4 ? quad_tpl(W, NT) : (NT + LPU - 1) / LPU;
@@ -488,6 +490,13 @@ __device__ __forceinline__ void serial_fwd_unit(int unit, float* __restrict__ xt
     float w[TPL], a0[TPL], a1[TPL], an[TPL], dd[TPL];
 #pragma unroll
     for (int k = 0; k < TPL; ++k) w[k] = 0.f;
+    if constexpr (STATE) {   // tap i = r*TPL + k reads slot (s-1-k) mod TPL of lane r: at s = 0 that holds y[-1-i]
+#pragma unroll
+        for (int k = 0; k < TPL; ++k) {
+            const int i = r * TPL + k;
+            w[TPL - 1 - k] = i < M ? state[(size_t)b * M + i] : 0.f;
+        }
+    }
     int f = 0, n0 = 0;
     load_row(a0, 0);
     load_row(a1, 1);
@@ -558,6 +567,25 @@ __device__ __forceinline__ void serial_fwd_unit(int unit, float* __restrict__ xt
         }
         wave_lds_fence();
     }
+    if constexpr (STATE) {
+        // the ring ran on past T inside the last W-block, so the new state is read back from y: y[T-1-i], or for T < M the
+        // old state shifted in.  Every read of the row is issued before its first write (one wave owns the row).
+        __threadfence();
+        constexpr int NS = (NT + LPU - 1) / LPU;
+        float v[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int i = r + j * LPU;
+            v[j] = i < M ? (i < T ? y[(size_t)b * y_stride + (T - 1 - i)] : state[(size_t)b * M + (i - T)]) : 0.f;
+        }
+        if (row < nrow) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                const int i = r + j * LPU;
+                if (i < M) state[(size_t)b * M + i] = v[j];
+            }
+        }
+    }
 }
 
 template <int W, int NT, int LPU>
@@ -572,6 +600,20 @@ __global__ __launch_bounds__(256) void lpc_serial_fwd_kernel(const float* __rest
     __shared__ float yt_all[4][TL::SIZE];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     serial_fwd_unit<W, NT, LPU>(blockIdx.x * 4 + wv, xt_all[wv], yt_all[wv], ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop);
+}
+
+template <int W, int NT, int LPU>
+__global__ __launch_bounds__(256) void lpc_serial_fwd_state_kernel(const float* __restrict__ ex, int64_t ex_stride,
+                                                                  const float* __restrict__ gain,
+                                                                  const float* __restrict__ a, float* __restrict__ y,
+                                                                  int64_t y_stride, int B, int T, int F, int M, int hop,
+                                                                  float* state) {
+    using TL = Tile<W, 64 / LPU>;
+    __shared__ float xt_all[4][TL::SIZE];
+    __shared__ float yt_all[4][TL::SIZE];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    serial_fwd_unit<W, NT, LPU, true>(blockIdx.x * 4 + wv, xt_all[wv], yt_all[wv], ex, ex_stride, gain, a, y, y_stride, B, T, F,
+                                      M, hop, state);
 }
 
 // Final pass of the flat-scan path: every chunk runs from its boundary state S_c (first pass + correction, or the fp64
@@ -3220,6 +3262,37 @@ __global__ void lpc_ss_generic_kernel(const float* __restrict__ ex, int64_t ex_s
     }
 }
 
+// The same with a carried state (golf_ltv_allpole_fwd_state_f32): y[<0] = state[b][-1-t'], every tap taken in the order above;
+// afterwards the row's last M outputs (for T < M: with the old state shifted in) replace the state, highest index first so that
+// no entry is overwritten before it is read.
+__global__ void lpc_ss_generic_state_kernel(const float* __restrict__ ex, int64_t ex_stride, const float* __restrict__ gain,
+                                            const float* __restrict__ a, float* y, int64_t y_stride, int B, int T, int F,
+                                            int M, int hop, float* state) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* exb = ex + (size_t)b * ex_stride;
+    volatile float* yb = y + (size_t)b * y_stride;
+    float* sb = state + (size_t)b * M;
+    const float inv_hop = 1.0f / (float)hop;
+    for (int t = 0; t < T; ++t) {
+        int f = F >= 2 ? t / hop : 0;
+        if (F >= 2 && f > F - 2) f = F - 2;
+        const float n = (float)(t - f * hop);
+        const float* pa0 = a + ((size_t)b * F + f) * M;
+        const float* pa1 = F >= 2 ? pa0 + M : pa0;
+        const float g0 = gain[(size_t)b * F + f];
+        const float g1 = F >= 2 ? gain[(size_t)b * F + f + 1] : g0;
+        float acc = exb[t] * fmaf(n, (g1 - g0) * inv_hop, g0);
+        float ra = 0.f;
+        for (int i = M - 1; i >= 0; --i) {
+            const float cf = fmaf(n, (pa1[i] - pa0[i]) * inv_hop, pa0[i]);
+            ra = fmaf(cf, t - 1 - i >= 0 ? yb[t - 1 - i] : sb[i - t], ra);
+        }
+        yb[t] = acc - ra;
+    }
+    for (int i = M - 1; i >= 0; --i) sb[i] = i < T ? yb[T - 1 - i] : sb[i - T];
+}
+
 // a-5 inverse filter: fully parallel FIR with interpolated coefficients.
 __global__ void lpc_inverse_kernel(const float* __restrict__ y, int64_t y_stride, const float* __restrict__ a,
                                    float* __restrict__ e, int64_t e_stride, int B, int T, int F, int M, int hop) {
@@ -3751,15 +3824,21 @@ static int launch_bwd(const SsPlan& p, const float* gy, int64_t gy_stride, const
     return GOLF_OK;
 }
 
+// eight lanes per utterance while that leaves at most one wave per SIMD (the wave's time per sample falls from ~19 to ~14
+// instructions): measured 2673 -> 2381 us at B = 2048, 2785 -> 2481 at 8192; at 16 384 (two waves per SIMD) the quad wins,
+// 3071 vs 3351 -- there the chip is busy either way and the quad does the least total work
+template <int W, int NT>
+static bool serial_use8(int B) {
+    static const int lpu_env = [] { const char* e = getenv("GOLF_SS_SERIAL_LPU"); return e ? atoi(e) : 0; }();   // A/B knob (dev)
+    constexpr bool can8 = W % 8 == 0 && W % ((NT + 7) / 8) == 0;
+    return can8 && (lpu_env ? lpu_env == 8 : (int64_t)B * 8 <= (int64_t)64 * 1024);
+}
+
 template <int W, int NT>
 static int launch_serial_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const float* gain, const float* a,
                              float* y, int64_t y_stride, int B, int T, int F, int M, int hop, hipStream_t st) {
-    // eight lanes per utterance while that leaves at most one wave per SIMD (the wave's time per sample falls from ~19 to ~14
-    // instructions): measured 2673 -> 2381 us at B = 2048, 2785 -> 2481 at 8192; at 16 384 (two waves per SIMD) the quad wins,
-    // 3071 vs 3351 -- there the chip is busy either way and the quad does the least total work
-    static const int lpu_env = [] { const char* e = getenv("GOLF_SS_SERIAL_LPU"); return e ? atoi(e) : 0; }();   // A/B knob (dev)
     constexpr bool can8 = W % 8 == 0 && W % ((NT + 7) / 8) == 0;
-    const bool use8 = can8 && (lpu_env ? lpu_env == 8 : (int64_t)B * 8 <= (int64_t)64 * 1024);
+    const bool use8 = serial_use8<W, NT>(B);
     if constexpr (can8) {
         if (use8) {
             hipLaunchKernelGGL((lpc_serial_fwd_kernel<W, NT, 8>), dim3((unsigned)ceil_div(B, 32)), dim3(256), 0, st, ex, ex_stride,
@@ -3770,6 +3849,25 @@ static int launch_serial_fwd(const SsPlan& p, const float* ex, int64_t ex_stride
     }
     hipLaunchKernelGGL((lpc_serial_fwd_kernel<W, NT, 4>), dim3((unsigned)ceil_div(B, 64)), dim3(256), 0, st, ex, ex_stride,
                        gain, a, y, y_stride, B, T, F, M, hop);
+    GOLF_LAUNCH_CHECK();
+    return GOLF_OK;
+}
+
+// golf_ltv_allpole_fwd_state_f32: the serial forward above, from and into a carried state (same lane-count rule)
+template <int W, int NT>
+static int launch_serial_fwd_state(const SsPlan& p, const float* ex, int64_t ex_stride, const float* gain, const float* a,
+                                   float* y, int64_t y_stride, int B, int T, int F, int M, int hop, float* state, hipStream_t st) {
+    constexpr bool can8 = W % 8 == 0 && W % ((NT + 7) / 8) == 0;
+    if constexpr (can8) {
+        if (serial_use8<W, NT>(B)) {
+            hipLaunchKernelGGL((lpc_serial_fwd_state_kernel<W, NT, 8>), dim3((unsigned)ceil_div(B, 32)), dim3(256), 0, st, ex,
+                               ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state);
+            GOLF_LAUNCH_CHECK();
+            return GOLF_OK;
+        }
+    }
+    hipLaunchKernelGGL((lpc_serial_fwd_state_kernel<W, NT, 4>), dim3((unsigned)ceil_div(B, 64)), dim3(256), 0, st, ex, ex_stride,
+                       gain, a, y, y_stride, B, T, F, M, hop, state);
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }
@@ -3932,6 +4030,26 @@ extern "C" int golf_ltv_allpole_fwd_f32(const float* ex, int64_t ex_stride, cons
     if (side == st) side = nullptr;
     GOLF_SS_DISPATCH(launch_fwd, p, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, (char*)ws, flags, side, st)
     return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd: no kernel for W=%d NT=%d", p.W, p.NT);
+}
+
+extern "C" int golf_ltv_allpole_fwd_state_f32(const float* ex, int64_t ex_stride, const float* gain, const float* a, float* y,
+                                              int64_t y_stride, int B, int T, int F, int M, int hop, float* state,
+                                              void* stream) {
+    if (int rc = check_ss_args(B, T, F, M, hop)) return rc;
+    if (!ex || !gain || !a || !y || !state) return fail(GOLF_EINVAL, "ltv_allpole_fwd_state: null pointer");
+    if (ex_stride < T || y_stride < T) return fail(GOLF_EINVAL, "ltv_allpole_fwd_state: row stride < T");
+    hipStream_t st = (hipStream_t)stream;
+    SsPlan p;
+    if (!make_ss_plan(B, T, F, M, hop, &p, GOLF_SS_SERIAL)) {
+        hipLaunchKernelGGL(lpc_ss_generic_state_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, st, ex, ex_stride, gain,
+                           a, y, y_stride, B, T, F, M, hop, state);
+        GOLF_LAUNCH_CHECK();
+        return GOLF_OK;
+    }
+    if (!serial_strides_ok(ex_stride, y_stride))
+        return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd_state: serial path needs row strides < 2^24");
+    GOLF_SS_DISPATCH(launch_serial_fwd_state, p, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state, st)
+    return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd_state: no kernel for W=%d NT=%d", p.W, p.NT);
 }
 
 extern "C" int golf_ltv_allpole_bwd_f32(const float* gy, int64_t gy_stride, const float* y, int64_t y_stride,

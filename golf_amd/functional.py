@@ -271,6 +271,33 @@ def ltv_allpole_ss(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: i
     return _LTVAllPoleSS.apply(ex, gain, a, int(hop), prepared, bool(fast_inference), SS_MODES[mode], status, length)
 
 
+def _inference_only(what: str, *tensors) -> None:
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError(f"golf_amd: {what} is inference only (an input requires grad)")
+
+
+def ltv_allpole_ss_state(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: int, state: torch.Tensor) -> torch.Tensor:
+    """ltv_allpole_ss from a carried state (golf_ltv_allpole_fwd_state_f32): y[b, -1-i] = state[b, i],
+    output (B, min(Tx, (F-1)*hop+1)); ``state`` (B, M) fp32 is updated in place to the block's last M outputs.  Inference only.
+    Always the serial recursion: blocks that start on frame boundaries, chained through ``state`` from zeros, give the bits of
+    ``ltv_allpole_ss(..., mode="serial")`` over the whole."""
+    _inference_only("ltv_allpole_ss_state", ex, gain, a)
+    ex, gain, a = _rows(ex.float()), gain.float().contiguous(), a.float().contiguous()   # (autocast: fp16/bf16 tracks first)
+    _lib.require_device(ex, gain, a, state)
+    B, Tx = ex.shape
+    F, M = a.shape[1], a.shape[2]
+    if gain.shape != (B, F) or a.shape[0] != B or state.shape != (B, M) or not state.is_contiguous():
+        raise _lib.GolfError(f"ltv_allpole_ss_state: ex {tuple(ex.shape)}, gain {tuple(gain.shape)}, a {tuple(a.shape)}, "
+                             f"state {tuple(state.shape)} (contiguous (B, M) required)")
+    T = ss_output_length(Tx, F, int(hop))
+    y = torch.empty(B, T, dtype=torch.float32, device=ex.device)
+    lib = _lib.load()
+    rc = lib.golf_ltv_allpole_fwd_state_f32(ex.data_ptr(), ex.stride(0), gain.data_ptr(), a.data_ptr(), y.data_ptr(),
+                                            y.stride(0), B, T, F, M, int(hop), state.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "golf_ltv_allpole_fwd_state_f32")
+    return y
+
+
 def ss_status(status: torch.Tensor, warn: bool = True) -> dict:
     """Decode the 4 status words of ltv_allpole_ss(..., status=t) (synchronises: reads the device tensor).  ``warn=False``:
     the caller reports a fix-up timeout itself (the module's health monitor: one warning per event, not two)."""
@@ -649,6 +676,34 @@ def source_filter_ss(phase, wsel, table, taps, phase_hop: int, w_hop: int, overs
     handle = PreparedTransitions(ss_ws, (B, T, F, M, int(hop), a.data_ptr(), a._version, SS_MODES[mode]), None, a, True, False, True)
     with torch.no_grad():
         return ltv_allpole_ss(src, gain, a, hop, prepared=handle, fast_inference=True, mode=mode, status=status, length=length)
+
+
+def glottal_osc_stream(phase, j0: int, nseg: int, final_point: bool, phase_hop: int, oversampling: int, wsel, w_first: int,
+                       w_hop: int, table, equal_energy: bool, acc: torch.Tensor, want_wrapped: bool = False):
+    """Fine-rate glottal oscillator samples of coarse phase samples j0 .. j0+nseg-1 (+ the utterance's last point with
+    ``final_point``) from the carried Q0.64 phase ``acc`` ((B,) int64 holding the uint64 bits, updated in place):
+    golf_glottal_osc_stream_f32.  ``phase`` (B, >= nseg+1) holds p[j0 ..], ``wsel`` (B, nw) rows w_first .. of the table-select
+    track.  Returns (B, nseg*P + final_point) before decimation, and the wrapped phase at the same samples with
+    ``want_wrapped`` (bit-identical to instantaneous_phase's).  Inference only."""
+    _inference_only("glottal_osc_stream", phase, wsel, table)
+    phase, wsel, table = _rows(phase.float()), _rows(wsel.float()), table.float().contiguous()
+    _lib.require_device(phase, wsel, table)
+    if not acc.is_cuda or acc.dtype != torch.int64 or acc.shape != (phase.shape[0],):
+        raise _lib.GolfError(f"glottal_osc_stream: acc must be a ({phase.shape[0]},) int64 device tensor")
+    B = phase.shape[0]
+    P = int(phase_hop) * int(oversampling)
+    n = int(nseg) * P + int(bool(final_point))
+    pre = torch.empty(B, n, dtype=torch.float32, device=phase.device)
+    wrapped = torch.empty_like(pre) if want_wrapped else None
+    n_tab, L = table.shape
+    lib = _lib.load()
+    rc = lib.golf_glottal_osc_stream_f32(phase.data_ptr(), phase.stride(0), int(nseg), int(bool(final_point)), int(phase_hop),
+                                         int(oversampling), wsel.data_ptr(), wsel.stride(0), wsel.shape[1], int(w_first),
+                                         int(w_hop), table.data_ptr(), n_tab, L, int(bool(equal_energy)), int(j0),
+                                         acc.data_ptr(), pre.data_ptr(), pre.stride(0), _lib.ptr(wrapped), B,
+                                         _lib.stream_ptr())
+    _lib.check(rc, "golf_glottal_osc_stream_f32")
+    return (pre, wrapped) if want_wrapped else pre
 
 
 # ------------------------------------------------------------------------------------------------

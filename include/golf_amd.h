@@ -133,6 +133,18 @@ int golf_ltv_allpole_fwd_f32(const float* ex, int64_t ex_stride, const float* ga
                              float* y, int64_t y_stride, int B, int T, int F, int M, int hop,
                              void* ws, size_t ws_bytes, int flags, void* side_stream, void* stream);
 
+/* Streaming form (additive in ABI 6): the same recursion, up() interpolation and T <= (F-1)*hop+1 rule, but y[<0] is not 0:
+ *   y[b][-1-i] = state[b][i],  state (B, M) fp32 DEVICE buffer, in and out (the oracle's `zi`, sample_wise_lpc(x, A, zi)).
+ * On return state[b][i] = y[b][T-1-i], the block's last M outputs (for T < M the old state shifted in behind them), so that
+ * the next block continues the recursion.  Always the serial recursion (GOLF_SS_SERIAL: 8 or 4 lanes per utterance by batch
+ * size; the generic kernel where no ring fits (M, hop)), and the per-tap summation order does not depend on where a block
+ * starts: blocks that start on frame boundaries, each given the frames it spans (frame 0 = the frame of its first sample),
+ * chained through `state` from zeros, give the same bits as one golf_ltv_allpole_fwd_f32(.., GOLF_SS_SERIAL) over the whole.
+ * No workspace; the row strides must stay below 2^24 on the ring path. */
+int golf_ltv_allpole_fwd_state_f32(const float* ex, int64_t ex_stride, const float* gain, const float* a,
+                                   float* y, int64_t y_stride, int B, int T, int F, int M, int hop,
+                                   float* state, void* stream);
+
 /* Conditioning and health status of the forward that last used `ws` (ABI 3).  The reference's sequential fp32
  * recursion degrades gracefully when an interpolated filter comes close to instability (models/filters.py:99-113 ->
  * torchlpc.sample_wise_lpc); the time-chunked algorithm keeps that behaviour by recomputing the
@@ -355,6 +367,25 @@ size_t golf_phase_accumulate_workspace_bytes(int B, int Tp);
 int golf_phase_accumulate_f32(const float* phase, int64_t phase_stride, int Tp, int phase_hop, int os,
                               const float* phase_offset, int64_t offset_stride, float* wrapped, int64_t wrapped_stride,
                               int B, int N, void* ws, size_t ws_bytes, void* stream);
+
+/* Streaming oscillator (additive in ABI 6): golf_glottal_osc_fwd_f32's fine-rate signal (before decimation) for the
+ * fine samples of coarse phase samples j0 .. j0+nseg-1, from a carried phase:
+ *   phase  (B, >= nseg+1) rows of stride phase_stride: phase[b][i] = p[b][j0+i] (p[j0+nseg] closes the last segment)
+ *   acc    (B) uint64 DEVICE words, Q0.64 cycles: on entry the exact phase before fine sample j0*P (P = phase_hop*os), on
+ *          return the phase before sample (j0+nseg)*P -- the same integer sums as the one-shot scan, so any split of the
+ *          track into calls accumulates the one-shot's phase bit for bit
+ *   final_point 1: also the utterance's last fine sample, k = 0 of coarse sample j0+nseg (the one-shot's (Tp-1)*P)
+ *   wsel   (B, >= nw) rows of stride wsel_stride: rows w_first .. w_first+nw-1 of the table-select track at w_hop output
+ *          samples; rows past the last given one repeat it (the one-shot's last frame at the utterance's end), rows before
+ *          w_first must not be needed
+ *   pre    (B, nseg*P + final_point) stride pre_stride: the fine samples (table blend, bilinear lookup, equal_energy scale)
+ *   wrapped (optional, may be NULL; same shape and stride as pre): frac of the inclusive phase as fp32, bit-identical to
+ *          golf_phase_accumulate_f32's output at the same fine samples
+ * Decimation is left to the caller (golf_decimate_fir_f32 over a window that carries (K-1)/2 fine samples of context). */
+int golf_glottal_osc_stream_f32(const float* phase, int64_t phase_stride, int nseg, int final_point, int phase_hop, int os,
+                                const float* wsel, int64_t wsel_stride, int nw, int64_t w_first, int w_hop,
+                                const float* table, int n_tab, int L, int equal_energy, int64_t j0, uint64_t* acc,
+                                float* pre, int64_t pre_stride, float* wrapped, int B, void* stream);
 
 /* The oscillator's decimator on its own (kazane.Decimate(os) stand-in, models/synth.py:208,262; taps are an input):
  *   out[b,o] = sum_k taps[k] * x[b, o*os + k - (K-1)/2], zero padded, Tout = (N-1)/os + 1, K odd, os in [2,64];
