@@ -48,6 +48,5 @@ struct SsPlan {
     size_t off_gflag;   // merged chunk pass (lpc_fwdq2m_kernel): [B][NG] "defect response published" + [B] "fp64 states ready" words
 };
 bool make_ss_plan(int B, int T, int F, int M, int hop, SsPlan* p, int mode = 0);
-int ss_serial_min_batch();
 
 }  // namespace golf

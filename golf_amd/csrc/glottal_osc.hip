@@ -21,7 +21,6 @@
 #include "device_common.h"
 #include "lpc_p1f.h"
 #include <algorithm>
-#include <cstdlib>
 
 namespace golf {
 
@@ -2050,12 +2049,8 @@ extern "C" size_t golf_glottal_osc_workspace_bytes(int B, int Tp, int phase_hop,
 // The fused forward's geometry, and whether it serves this call (the backward asks too: a workspace the fused forward filled
 // still holds the tile totals and the transposed tap fragments, GOLF_OSC_WS_KEPT).
 struct OscFused2 { int dmin, dmax, KS, nrows, ntile2, lshift, TO, ntile_f; size_t lds; };
-static int osc_unfused_env() {
-    static const int v = [] { const char* e = getenv("GOLF_OSC_UNFUSED"); return e ? atoi(e) : 0; }();  // A/B knob
-    return v;
-}
 static bool osc_fused2_plan(const OscGeom& g, const float* table, int L, int os, int K, bool want_pre, int Tout, int B, OscFused2* f) {
-    if (!(os == 4 && g.P == 4 && (L & (L - 1)) == 0 && L >= 8 && !want_pre && !osc_unfused_env())) return false;
+    if (!(os == 4 && g.P == 4 && (L & (L - 1)) == 0 && L >= 8 && !want_pre)) return false;
     if ((uintptr_t)table & 15) return false;                    // table rows are fetched as 16-byte words
     const int half = (K - 1) / 2;
     f->dmin = -((half + os - 1) / os);
@@ -2146,9 +2141,8 @@ extern "C" int golf_glottal_osc_fwd_f32(const float* phase, int64_t phase_stride
         // two forms are equal (122.8 vs 122.5 us for the step).  With FOUR such batches in flight every oscillator launch is a
         // "first round" -- the tiles of an utterance enter together and wave 0 of every workgroup polls twice -- and the two
         // launches are cheaper: 69.4 - 69.9 against 70.7 - 70.8 us/step on one box, three alternations (profiles/r06_ab_r05_vs_r06.txt).
-        // GOLF_OSC_THROUGHPUT asks for them below a device-filling batch; GOLF_OSC_TWO_LAUNCH=0/1 forces either (A/B knob).
-        static const int tl_env = [] { const char* e = getenv("GOLF_OSC_TWO_LAUNCH"); return e ? atoi(e) : -1; }();
-        const bool two_launch = tl_env >= 0 ? tl_env != 0 : (throughput && (int64_t)B * f2.ntile_f < 8192);
+        // GOLF_OSC_THROUGHPUT asks for them below a device-filling batch.
+        const bool two_launch = throughput && (int64_t)B * f2.ntile_f < 8192;
         if (two_launch) {   // round 5's form: the tile totals by a launch of their own (the phase is read twice)
             hipLaunchKernelGGL(osc_tile_totals_kernel<OSCF_TO>, dim3(f2.ntile2, B), dim3(osct_threads(OSCF_TO)), 0, st, phase, phase_stride,
                                Ttot, Tp, g.P, os, f2.ntile2, taps, K, f2.dmin, f2.KS, (float*)nullptr, f2.dmax, (float*)nullptr, (u64*)nullptr);
@@ -2214,11 +2208,10 @@ extern "C" int golf_source_transitions_f32(const float* phase, int64_t phase_str
                                            void* osc_ws, size_t osc_ws_bytes, const float* addend, int64_t addend_stride,
                                            int Tadd, const void* tap_frags, const float* a, int T, int F, int M, int hop,
                                            void* ss_ws, size_t ss_ws_bytes, int ss_flags, void* stream) {
-    static const bool split_env = [] { const char* e = getenv("GOLF_SOURCE_MAPS_SPLIT"); return e && atoi(e) != 0; }();   // A/B knob
     OscGeom g;
     OscFused2 f2;
     SsPlan p;
-    bool fuse = !split_env && phase && wsel && table && out && a && osc_ws && ss_ws && B >= 1 && Tp >= 1 && phase_hop >= 1 &&
+    bool fuse = phase && wsel && table && out && a && osc_ws && ss_ws && B >= 1 && Tp >= 1 && phase_hop >= 1 &&
                 Fw >= 1 && w_hop >= 1 && os >= 1 && T >= 1 && F >= 1 && M >= 1 && hop >= 1 &&
                 (ss_flags & GOLF_SS_FAST_TRANSITIONS) && (ss_flags & GOLF_SS_MAPS_ONLY) && !(ss_flags & GOLF_SS_SERIAL);
     if (fuse) fuse = osc_check(B, Tp, phase_hop, Fw, w_hop, n_tab, L, os, K, taps) == GOLF_OK;
@@ -2297,7 +2290,7 @@ extern "C" int golf_glottal_osc_bwd_wsel_f32(const float* g_out, int64_t g_out_s
     const bool ws_kept = (equal_energy & GOLF_OSC_WS_KEPT) != 0;
     equal_energy &= 1;
     // ---- fused path (the GOLF configuration, as in the forward): tile totals + osc_fused_bwd_kernel + a reduction
-    if (os == 4 && g.P == 4 && (L & (L - 1)) == 0 && !osc_unfused_env()) {
+    if (os == 4 && g.P == 4 && (L & (L - 1)) == 0) {
         const int half = (K - 1) / 2;
         const int dmin = -((half + os - 1) / os);
         const int dmax = half / os;

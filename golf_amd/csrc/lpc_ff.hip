@@ -770,15 +770,13 @@ static FfBwdPlan ff_bwd_plan(int B, int F, int Wl, int nfr, int Ty) {
     return p;
 }
 
-// Row sum of |G| up to which a wave of the block-recursion kernel keeps its feedback part in fp32 (dev knob GOLF_FF_KAPPA)
-static float ff_kappa_max() {
-    static const float v = [] { const char* e = getenv("GOLF_FF_KAPPA"); return e ? (float)atof(e) : 64.f; }();
-    return v;
-}
-// The block-recursion kernel's conditions (dev knob GOLF_FF_QUADS=1: the direct-form quad kernel, A/B)
+// Row sum of |G| up to which a wave of the block-recursion kernel keeps its feedback part in fp32 (build parameter)
+#ifndef GOLF_FF_KAPPA
+#define GOLF_FF_KAPPA 64
+#endif
+// The block-recursion kernel's conditions (other shapes take the direct-form quad kernel)
 static bool ff_block_ok(int Wl, int hop, size_t lds_bytes) {
-    static const bool quads = [] { const char* e = getenv("GOLF_FF_QUADS"); return e && atoi(e) != 0; }();
-    return !quads && Wl % 32 == 0 && hop % 4 == 0 && lds_bytes <= 56 * 1024;
+    return Wl % 32 == 0 && hop % 4 == 0 && lds_bytes <= 56 * 1024;
 }
 
 template <int W, int NT>
@@ -797,25 +795,11 @@ static int launch_ff_bwd(const float* gy, int64_t gy_stride, const float* ex, in
     hipLaunchKernelGGL(ff_gq_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, gy, gy_stride, window, gq, B,
                        Ty, hop, Wl, nfr);
     GOLF_LAUNCH_CHECK();
-    bool blocked = false;
-    if constexpr (NT <= 24) {
-        const size_t ldsb = sizeof(float) * 4 * (size_t)Wl;
-        // the adjoint stages 4 whole frames of window * g_q per wave instead of their union: 56 us against the quads' 45 at
-        // B = 32 -- measured, so the backward keeps the quad kernel unless GOLF_FF_BLOCK_BWD=1 (A/B)
-        static const bool bwd_block = [] { const char* e = getenv("GOLF_FF_BLOCK_BWD"); return e && atoi(e) != 0; }();
-        if (bwd_block && ff_block_ok(Wl, hop, ldsb)) {   // block recursion (ff_framesb_kernel)
-            static const hipError_t attr = hipFuncSetAttribute((const void*)ff_framesb_kernel<NT, true>,
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            if (attr != hipSuccess) return fail((int)attr, "lti_frames_bwd: cannot raise the dynamic LDS limit");
-            hipLaunchKernelGGL((ff_framesb_kernel<NT, true>), dim3((unsigned)ceil_div(nfr, 4), B), dim3(64), ldsb, st,
-                               (const float*)gq, (int64_t)Ty, gain, a, window, uf, Ty, F, M, hop, Wl, nfr, ff_kappa_max());
-            blocked = true;
-        }
-    }
-    if (!blocked)
-        hipLaunchKernelGGL((ff_framesq_kernel<W, NT, true>), dim3((unsigned)ceil_div(nfr, 16), B), dim3(64),
-                           sizeof(float) * (size_t)Wl, st, (const float*)gq, (int64_t)Ty, gain, a, window, uf, Ty, F, M,
-                           hop, Wl, nfr);
+    // the adjoint stays on the quad kernel: the block recursion's adjoint (ff_framesb_kernel<NT, true>) stages 4 whole frames
+    // of window * g_q per wave instead of their union and measured 56 us against the quads' 45 at B = 32
+    hipLaunchKernelGGL((ff_framesq_kernel<W, NT, true>), dim3((unsigned)ceil_div(nfr, 16), B), dim3(64),
+                       sizeof(float) * (size_t)Wl, st, (const float*)gq, (int64_t)Ty, gain, a, window, uf, Ty, F, M,
+                       hop, Wl, nfr);
     GOLF_LAUNCH_CHECK();
     const int nq = B * F;
     const int RS = 2 * Wl + NT + 8;
@@ -844,7 +828,7 @@ static int launch_ff(const float* ex, int64_t ex_stride, const float* gain, cons
                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
             if (attr != hipSuccess) return fail((int)attr, "lti_frames_ola: cannot raise the dynamic LDS limit");
             hipLaunchKernelGGL((ff_framesb_kernel<NT, false>), dim3((unsigned)ceil_div(nfr, 4), B), dim3(64), ldsb, st, ex,
-                               ex_stride, gain, a, window, wf, Tx, F, M, hop, Wl, nfr, ff_kappa_max());
+                               ex_stride, gain, a, window, wf, Tx, F, M, hop, Wl, nfr, (float)GOLF_FF_KAPPA);
             blocked = true;
         }
     }

@@ -53,20 +53,19 @@ static const WNT kTable[] = {{8, 2},   {8, 4},   {8, 6},   {16, 8},  {16, 12}, {
                              {24, 16}, {24, 20}, {24, 22}, {32, 16}, {32, 22}, {32, 26}, {32, 30}, {40, 22},
                              {40, 26}, {40, 32}, {40, 38}};
 
-// Batch size from which the batch-parallel serial kernels replace the chunked scan (dev knob: GOLF_SS_SERIAL_MIN_BATCH).
+// Batch size from which the batch-parallel serial kernels replace the chunked scan (build parameter).
 // Chunking buys parallelism in time at the price of (M+2)-fold arithmetic; once the batch alone fills the chip's wave
 // slots that price stops paying.  Measured crossover on MI355X (M=22, T=47761): DESIGN.md §4.1.
-int ss_serial_min_batch() {
-    static const int v = [] { const char* e = getenv("GOLF_SS_SERIAL_MIN_BATCH"); return e ? atoi(e) : 2048; }();
-    return v;
-}
+#ifndef GOLF_SS_SERIAL_MIN_BATCH
+#define GOLF_SS_SERIAL_MIN_BATCH 2048
+#endif
 
 bool make_ss_plan(int B, int T, int F, int M, int hop, SsPlan* p, int mode) {
     p->W = 0;
     p->NT = 0;
     // mode: 0 = by batch size, GOLF_SS_SERIAL / GOLF_SS_CHUNKED force one; rows of 16 utterances must fit a 2 GB
     // buffer descriptor
-    p->serial = mode == GOLF_SS_SERIAL || (mode != GOLF_SS_CHUNKED && B >= ss_serial_min_batch());
+    p->serial = mode == GOLF_SS_SERIAL || (mode != GOLF_SS_CHUNKED && B >= GOLF_SS_SERIAL_MIN_BATCH);
     if (F >= 2) {
         for (const WNT& e : kTable) {
             if (e.NT < M || hop % e.W != 0) continue;
@@ -231,11 +230,6 @@ static float phi_guard3() {
 }
 // rows of 16 utterances are addressed through one 32-bit buffer descriptor (serial kernels)
 static bool serial_strides_ok(int64_t s0, int64_t s1) { return s0 < (1 << 24) && s1 < (1 << 24); }
-// diagnostic A/B switch (bench): no fix-up launch at all, every utterance is treated as tier 1 (status words are then void)
-static bool no_fixup() {
-    static const bool v = [] { const char* e = getenv("GOLF_SS_NO_FIXUP"); return e && atoi(e) != 0; }();
-    return v;
-}
 constexpr unsigned kTierHot = 2u, kTierPrecise = 3u;
 // Which boundary scan the forward ran is recorded behind the tier words ([2B]); the backward's first kernel compares it with
 // its own and raises [2B + 1], which golf_ltv_allpole_status_u32 reports: a C caller that hands the backward other scan
@@ -747,9 +741,9 @@ __global__ __launch_bounds__(256) void lpc_serial_adj_kernel(const float* __rest
 //   PhiT[q][i][j] (row i contiguous: forward scan reads rows)
 //   lane = flat chunk q;  `pair` selects trajectories (2*pair, 2*pair+1)
 // ------------------------------------------------------------------------------------------
-// trajectories per lane (GOLF_P1H_KT=1/2/3 overrides).  B=32: 22 trajectories / KT groups x 100 chunk blocks =
-// 2200 / 1100 / 800 waves of relative length 0.67 / 1 / 1.33 on 1024 SIMDs: only KT=3 fits one wave per SIMD.
-constexpr int p1h_kt(int W) { return 3; }
+// trajectories per lane: KT = 3 (launch_transitions).  B=32: 22 trajectories / KT groups x 100 chunk blocks =
+// 2200 / 1100 / 800 waves of relative length 0.67 / 1 / 1.33 on 1024 SIMDs for KT = 1 / 2 / 3: only KT=3 fits one wave
+// per SIMD.
 
 template <int W, int NT, int KT, typename R>
 __device__ __forceinline__ void p1_hom_body(int qblk, int grp, const float* __restrict__ a, float* __restrict__ Phi,
@@ -2089,7 +2083,7 @@ __global__ __launch_bounds__(256) void lpc_group_prepass_kernel(const float* __r
         for (int i = threadIdx.x; i < zp.ngflag; i += 256) zp.gflag[i] = 0u;
         if (threadIdx.x == 0 && zp.nonfinite) zp.nonfinite[0] = 0u;
     }
-    const bool fix = fa.pmax != nullptr && (parts & 1);   // (no fix-up at all: diagnostic switch GOLF_SS_NO_FIXUP)
+    const bool fix = fa.pmax != nullptr && (parts & 1);   // (fa.pmax == nullptr: no fix-up at all; no host path passes that)
     const int nu = NG * B;
     const int nf1 = fix ? B * KF1 : 0, nz = (parts & 2) ? (nu + 3) / 4 : 0, nc = (parts & 1) ? nu : 0;
     int blk = (int)blockIdx.x;
@@ -3427,9 +3421,12 @@ static int device_cu_count() {
 //   B = 32: 71.9 vs 71.6 / 140 vs 166;  B = 48: 101 vs 94 / 192 vs 214;  B = 64: 132 vs 117 / 212 vs 229;
 //   (with the earlier fp32 composites) B = 96: 204 vs 166 / 300 vs 286;  B = 256: 537 vs 437 / 629 vs 515
 // so it is taken while B x NG stays below half the SIMD count (B <= 39 at 2 s), where it costs the pipelined rate nothing.
+// (Build parameter GOLF_SS_TWO_LEVEL_WAVES: a fixed cap on B x NG instead; 0 = 2 x the CU count.)
+#ifndef GOLF_SS_TWO_LEVEL_WAVES
+#define GOLF_SS_TWO_LEVEL_WAVES 0
+#endif
 static bool use_two_level_scan(const SsPlan& p, int B, int flags) {
-    static const long env = [] { const char* e = getenv("GOLF_SS_TWO_LEVEL_WAVES"); return e ? atol(e) : 0L; }();   // dev knob
-    const int64_t cap = env > 0 ? (int64_t)env : (int64_t)2 * device_cu_count();
+    const int64_t cap = GOLF_SS_TWO_LEVEL_WAVES > 0 ? (int64_t)GOLF_SS_TWO_LEVEL_WAVES : (int64_t)2 * device_cu_count();
     return p.NG > 0 && !(flags & GOLF_SS_FLAT_SCAN) && (int64_t)B * p.NG <= cap;
 }
 
@@ -3441,7 +3438,7 @@ static FixArgs fix_args(const SsPlan& p, const float* a, int F, int M, int hop, 
     fa.PhiT = (float*)(ws + p.off_phiT);
     fa.Phi = (training && !accurate) ? (float*)(ws + p.off_phi) : nullptr;
     fa.Phi64 = (double*)(ws + p.off_phi64);
-    fa.pmax = no_fixup() ? nullptr : (const float*)(ws + p.off_pmax);
+    fa.pmax = (const float*)(ws + p.off_pmax);
     fa.tier = (unsigned*)(ws + p.off_tier);
     fa.status = (unsigned*)(ws + p.off_status);
     fa.fixcnt = (unsigned*)(ws + p.off_fixcnt);
@@ -3451,15 +3448,18 @@ static FixArgs fix_args(const SsPlan& p, const float* a, int F, int M, int hop, 
     fa.hot16 = hot_all_16ths();
     fa.hotn = hot_count();
     fa.accurate = accurate;
-    static const bool nowait = [] { const char* e = getenv("GOLF_SS_FIXUP_NOWAIT"); return e && atoi(e) != 0; }();   // dev knob (A/B timing only: wrong for hot batches)
-    if (nowait) fa.g3 = -12345.f;
     return fa;
 }
 // fix-up workgroups (4 waves of 16 units) per utterance: KF1 lead the grid (the guarantee), KF2 trail it (the speed);
-// together at most one pass over all units of an utterance
-static void fixup_kf(const SsPlan& p, int NT, int* kf1, int* kf2, bool own_launch = false, bool lone_batch = false) {
-    static const int e1 = [] { const char* e = getenv("GOLF_SS_FIXUP_KF1"); return e ? atoi(e) : 0; }();   // dev knobs
-    static const int e2 = [] { const char* e = getenv("GOLF_SS_FIXUP_KF2"); return e ? atoi(e) : -1; }();
+// together at most one pass over all units of an utterance.  Build parameters GOLF_SS_FIXUP_KF1 (> 0) / GOLF_SS_FIXUP_KF2 (>= 0)
+// fix either count; the defaults take the rules below.
+#ifndef GOLF_SS_FIXUP_KF1
+#define GOLF_SS_FIXUP_KF1 0
+#endif
+#ifndef GOLF_SS_FIXUP_KF2
+#define GOLF_SS_FIXUP_KF2 -1
+#endif
+static void fixup_kf(const SsPlan& p, int NT, int* kf1, int* kf2, bool lone_batch = false) {
     const int64_t all = ceil_div((int64_t)p.NP * NT, 64);   // workgroups that cover every unit in one pass
     // Round 6 (G2 = 8: a hot utterance of the recipe now has 50 - 150 hot chunks, not 5 - 20): a caller WITHOUT batches in flight
     // (no GOLF_SS_THROUGHPUT, two-level path) gets (10, 38) -- trailing workgroups cost a lone batch nothing, leading ones cost its
@@ -3467,7 +3467,7 @@ static void fixup_kf(const SsPlan& p, int NT, int* kf1, int* kf2, bool own_launc
     // (10, 22) 137.3 / 122.4 / 142.9 / 164.1; (10, 38) 136.2 / 121.8 / 142.2 / 161.1; (8, 48) 136.8; (10, 59) 137.3; (6, 63) 137.8;
     // (16, 32) 139.0 / 128.8 / ..; (32, 0) 140.1 / 131.1.  With four batches in flight the same settings LOSE (headline 68.7 ->
     // 70.2 - 72.6 us/step): there every idle workgroup is dispatch cost, and (6, 10) stays.
-    int k1 = e1 > 0 ? e1 : (lone_batch ? 10 : 6);
+    int k1 = GOLF_SS_FIXUP_KF1 > 0 ? GOLF_SS_FIXUP_KF1 : (lone_batch ? 10 : 6);
     if (k1 > all) k1 = (int)(all < 1 ? 1 : all);
     // Every fix-up workgroup that finds nothing to do is dispatch cost, and with several batches in flight that is what
     // counts.  Measured, (KF1, KF2) -> us/step pipelined: B = 256, launch of its own (18 hot utterances + one tier 3 in the
@@ -3475,8 +3475,7 @@ static void fixup_kf(const SsPlan& p, int NT, int* kf1, int* kf2, bool own_launc
     // B = 32, merged into the pre-pass (headline / driver's 20 steps / recipe_stream): (6, 10) 74.3 / 82.9 / 77.9,
     // (6, 26) 74.9 / 83.5 / 78.4, (6, 42) 75.8 / 86.4 / 80.9.  16 workgroups = 1024 units per pass: one pass for up to 46 hot
     // chunks of an utterance (typical: 5 - 20); a tier-3 utterance (all 199) takes five.
-    (void)own_launch;
-    int64_t k2 = e2 >= 0 ? e2 : (lone_batch ? 38 : 10);
+    int64_t k2 = GOLF_SS_FIXUP_KF2 >= 0 ? GOLF_SS_FIXUP_KF2 : (lone_batch ? 38 : 10);
     if (k1 + k2 > all) k2 = all - k1 > 0 ? all - k1 : 0;
     *kf1 = k1;
     *kf2 = (int)k2;
@@ -3486,9 +3485,9 @@ static void fixup_kf(const SsPlan& p, int NT, int* kf1, int* kf2, bool own_launc
 template <int W, int NT>
 static int launch_fixup(const SsPlan& p, const float* a, int B, int F, int M, int hop, char* ws, int accurate,
                         int training, hipStream_t st) {
-    if (p.NP <= 0 || no_fixup()) return GOLF_OK;
+    if (p.NP <= 0) return GOLF_OK;
     int k1, k2;
-    fixup_kf(p, NT, &k1, &k2, true);
+    fixup_kf(p, NT, &k1, &k2);
     FixArgs fa = fix_args(p, a, F, M, hop, ws, accurate, training);
     fa.B = B;
     hipLaunchKernelGGL((lpc_fixup_kernel<W, NT>), dim3((unsigned)(k1 + k2), B), dim3(256), 0, st, fa);
@@ -3507,8 +3506,8 @@ static int launch_composites(const SsPlan& p, const float* a, int B, int F, int 
             FixArgs fa = fix_args(p, a, F, M, hop, ws, accurate, training);
             fa.B = B;
             int k1, k2;
-            fixup_kf(p, NT, &k1, &k2, false, !(flags & GOLF_SS_THROUGHPUT));
-            const int nf = fa.pmax ? B * (k1 + k2) : 0, nu = p.NG * B;
+            fixup_kf(p, NT, &k1, &k2, !(flags & GOLF_SS_THROUGHPUT));
+            const int nf = B * (k1 + k2), nu = p.NG * B;
             hipLaunchKernelGGL((lpc_group_prepass_kernel<W, NT>), dim3((unsigned)(nf + nu)), dim3(256), 0, st,
                                (const float*)(ws + p.off_phiT), (float*)nullptr, (float*)(ws + p.off_mt),
                                (float*)nullptr, p.NP, p.NG, B, 1, fa, k1, k2,
@@ -3547,19 +3546,9 @@ static int launch_transitions(const SsPlan& p, const float* a, int B, int T, int
         if (flags & GOLF_SS_MAPS_ONLY) return GOLF_OK;   // the forward runs the fix-up and the composites itself
         return launch_composites<W, NT>(p, a, B, F, M, hop, ws, 0, flags, st);
     }
-    static const int kt_env = [] { const char* e = getenv("GOLF_P1H_KT"); return e ? atoi(e) : 0; }();  // dev knob
-    if (kt_env == 1) {
-        hipLaunchKernelGGL((lpc_p1h_kernel<W, NT, 1, double>), dim3((unsigned)ceil_div(ceil_div(nq, 64) * NT, 4)),
-                           dim3(256), 0, st, a, Phi, PhiT, F, M, hop, p.L, p.NP, nq);
-    } else if (p1h_kt(W) == 3 && kt_env != 2) {
-        constexpr int NG = (NT + 2) / 3;
-        hipLaunchKernelGGL((lpc_p1h_kernel<W, NT, 3, double>), dim3((unsigned)ceil_div(ceil_div(nq, 64) * NG, 4)),
-                           dim3(256), 0, st, a, Phi, PhiT, F, M, hop, p.L, p.NP, nq);
-    } else {
-        constexpr int NG = (NT + 1) / 2;
-        hipLaunchKernelGGL((lpc_p1h_kernel<W, NT, 2, double>), dim3((unsigned)ceil_div(ceil_div(nq, 64) * NG, 4)),
-                           dim3(256), 0, st, a, Phi, PhiT, F, M, hop, p.L, p.NP, nq);
-    }
+    constexpr int NG = (NT + 2) / 3;
+    hipLaunchKernelGGL((lpc_p1h_kernel<W, NT, 3, double>), dim3((unsigned)ceil_div(ceil_div(nq, 64) * NG, 4)),
+                       dim3(256), 0, st, a, Phi, PhiT, F, M, hop, p.L, p.NP, nq);
     GOLF_LAUNCH_CHECK();
     hipLaunchKernelGGL((lpc_transpose_kernel<W, NT>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st,
                        (const float*)Phi, PhiT, nq, (float*)(ws + p.off_pmax), (unsigned*)(ws + p.off_fixcnt), B);
@@ -3598,7 +3587,7 @@ static int launch_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const
     float* PhiT = (float*)(ws + p.off_phiT);
     float* z = (float*)(ws + p.off_z);
     float* S = (float*)(ws + p.off_S);
-    const unsigned* tier = p.NP > 0 && !no_fixup() ? (const unsigned*)(ws + p.off_tier) : nullptr;
+    const unsigned* tier = p.NP > 0 ? (const unsigned*)(ws + p.off_tier) : nullptr;
     unsigned* nonfinite = (unsigned*)(ws + p.off_status);
     const double* Phi64 = (const double*)(ws + p.off_phi64);
     constexpr int D = 8;
@@ -3694,8 +3683,8 @@ static int launch_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const
             FixArgs fa = fix_args(p, a, F, M, hop, ws, fast ? 0 : 1, training);
             fa.B = B;
             int k1, k2;
-            fixup_kf(p, NT, &k1, &k2, false, !(flags & GOLF_SS_THROUGHPUT));
-            const int nf = fa.pmax ? B * (k1 + k2) : 0, nu = p.NG * B, nz = (int)ceil_div(nu, 4);
+            fixup_kf(p, NT, &k1, &k2, !(flags & GOLF_SS_THROUGHPUT));
+            const int nf = B * (k1 + k2), nu = p.NG * B, nz = (int)ceil_div(nu, 4);
             const int parts = (fused_p1 ? 3 : 2) | (zin ? 4 : 0), count = (fused_p1 ? nf + nu : 0) + nz;   // in workgroups
             hipLaunchKernelGGL((lpc_group_prepass_kernel<W, NT>), dim3((unsigned)count), dim3(256), 0, st,
                                (const float*)PhiT, z, MT, Vz, p.NP, p.NG, B, parts, fa, k1, k2,
@@ -3763,7 +3752,7 @@ static int launch_bwd(const SsPlan& p, const float* gy, int64_t gy_stride, const
     float* pa = (float*)(ws + p.off_pa);
     float* pg = (float*)(ws + p.off_pg);
     float* dadj = (float*)(ws + p.off_dadj);
-    const unsigned* tier = p.NP > 0 && !no_fixup() ? (const unsigned*)(ws + p.off_tier) : nullptr;   // as the forward left them
+    const unsigned* tier = p.NP > 0 ? (const unsigned*)(ws + p.off_tier) : nullptr;   // as the forward left them
     const double* Phi64 = (const double*)(ws + p.off_phi64);
     constexpr int D = 8;
     const dim3 gq((unsigned)ceil_div(p.NC, 16), B);
@@ -3829,9 +3818,8 @@ static int launch_bwd(const SsPlan& p, const float* gy, int64_t gy_stride, const
 // 3071 vs 3351 -- there the chip is busy either way and the quad does the least total work
 template <int W, int NT>
 static bool serial_use8(int B) {
-    static const int lpu_env = [] { const char* e = getenv("GOLF_SS_SERIAL_LPU"); return e ? atoi(e) : 0; }();   // A/B knob (dev)
     constexpr bool can8 = W % 8 == 0 && W % ((NT + 7) / 8) == 0;
-    return can8 && (lpu_env ? lpu_env == 8 : (int64_t)B * 8 <= (int64_t)64 * 1024);
+    return can8 && (int64_t)B * 8 <= (int64_t)64 * 1024;
 }
 
 template <int W, int NT>

@@ -1257,7 +1257,7 @@ def test_conditioning_soak_bounded(seed):
 def test_source_and_transition_maps_in_one_launch_is_bit_identical(B, seed, M, with_add, monkeypatch):
     """``source_filter_ss`` = oscillator || transition maps as one grid, then the pre-pass with the zero-state pass in front and
     the merged chunk pass: the same bits as the composition ``ltv_allpole_ss(glottal_osc(...))`` on either launch chain, the
-    split fallback (GOLF_SOURCE_MAPS_SPLIT semantics: M = 12 takes the two calls by itself -- ring 16) included, and the float64
+    two-call fallback of ``golf_source_transitions_f32`` (M = 12 takes it by itself -- ring 16) included, and the float64
     oracle's values.  Seed 2435 holds a hot utterance (fix-up inside the pre-pass)."""
     from golf_amd import functional as GF
     from golf_amd.synth import DownsampledIndexedGlottalFlowTable

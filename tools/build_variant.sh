@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev: build golf_amd/lib/libgolf_<tag>.so from the current sources with extra hipcc flags for ONE or more translation units;
 # the other objects are taken from golf_amd/lib/*.hip.o (run `python -c "import golf_amd._lib as l; l.build()"` first).
-# usage: tools/build_variant.sh TAG "lpc_ss.hip glottal_osc.hip" -DGOLF_GP_DC=3 ...     (GOLF_FULL=1: all (W, NT) instantiations)
+# usage: tools/build_variant.sh TAG "lpc_ss.hip glottal_osc.hip" -DGOLF_SS_FIXUP_KF1=10 -DGOLF_FF_KAPPA=32 ...     (GOLF_FULL=1: all (W, NT) instantiations)
 set -e
 R=$(cd $(dirname $0)/.. && pwd); L=$R/golf_amd/lib; C=$R/golf_amd/csrc
 tag=$1; units=$2; shift 2

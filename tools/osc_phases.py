@@ -18,7 +18,7 @@ inps = [make_inputs(B=B, device="cuda", seed=2434 + i) for i in range(4)]
 run = lambda i: GF.glottal_osc(inps[i]["phase"], inps[i]["wsel"], osc.table, osc.decimater.taps, 1, inps[i]["w_hop"], 4, True, add=inps[i]["noise"])
 n = int(os.environ.get('OSC_PHASES_WGS', 24 * B))   # workgroups that leave stamps (persistent grid: CUs x workgroups per CU)
 import os as _os
-print("library:", _os.environ.get("GOLF_HIP_LIBRARY"), "GOLF_OSCF_OLD =", _os.environ.get("GOLF_OSCF_OLD"))
+print("library:", _os.environ.get("GOLF_HIP_LIBRARY"))
 def dump(tag):
     torch.cuda.synchronize()
     buf = np.zeros(8 * n, dtype=np.uint64)

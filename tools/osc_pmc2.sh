@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/osc_pmc2.sh <tag> [B]   (env GOLF_OSCF_GEOM / GOLF_OSC_UNFUSED select the variant)
+# usage: tools/osc_pmc2.sh <tag> [B]   (GOLF_HIP_LIBRARY selects the build)
 R=$GRAFT_REPO_ROOT; tag=$1; B=${2:-256}
 i=0
 for set in "SQ_WAVES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_SMEM" "SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VMEM"; do

@@ -1,7 +1,6 @@
-"""dev: time the glottal oscillator forward for the fused-kernel geometries (GOLF_OSCF_GEOM) and batch sizes.
-usage: python tools/time_osc.py            -> sweeps geometries x batches in subprocesses
-       python tools/time_osc.py one B      -> one measurement in this process (env selects the variant)"""
-import os, subprocess, sys
+"""dev: time the glottal oscillator forward over batch sizes (GOLF_HIP_LIBRARY selects a variant build).
+usage: python tools/time_osc.py [B ...]     (default: 32 512)"""
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
@@ -29,16 +28,9 @@ def one(B, iters=20):
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / iters
-    print(f"geom={os.environ.get('GOLF_OSCF_GEOM', '0')} unfused={os.environ.get('GOLF_OSC_UNFUSED', '0')} B={B}: "
-          f"{us:9.1f} us/call  {us / B:7.3f} us/utterance", flush=True)
+    print(f"B={B}: {us:9.1f} us/call  {us / B:7.3f} us/utterance", flush=True)
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 2 and sys.argv[1] == "one":
-        one(int(sys.argv[2]))
-    else:
-        batches = [int(v) for v in sys.argv[1:]] or [32, 512]
-        for env in ({"GOLF_OSC_UNFUSED": "1"}, {"GOLF_OSCF_GEOM": "0"}, {"GOLF_OSCF_GEOM": "1"}, {"GOLF_OSCF_GEOM": "2"},
-                    {"GOLF_OSCF_GEOM": "3"}):
-            for B in batches:
-                subprocess.run([sys.executable, __file__, "one", str(B)], env={**os.environ, **env})
+    for B in [int(v) for v in sys.argv[1:]] or [32, 512]:
+        one(B)
