@@ -46,6 +46,10 @@ SIGNATURES = {
     "golf_lti_frames_workspace_bytes": (_sz, [_int] * 6),
     "golf_lti_frames_ola_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 7
                                     + [_vp, _sz, _vp]),
+    "golf_lti_frames_stream_state_bytes": (_sz, [_int] * 4),
+    "golf_lti_frames_ola_stream_f32": (_int, [_c_f32p, _i64, _i64, _int, _i64, _c_f32p, _i64, _int, _i64, _c_f32p, _i64, _int,
+                                              _c_f32p, _i64, _int, _c_f32p, _i64, _i64, _int] + [_int] * 4
+                                       + [_c_f32p, _vp, _sz, _vp]),
     "golf_lti_frames_bwd_workspace_bytes": (_sz, [_int] * 6),
     "golf_lti_frames_ola_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64, _int,
                                            _c_f32p, _c_f32p] + [_int] * 7 + [_vp, _vp, _sz, _vp]),

@@ -1167,3 +1167,459 @@ extern "C" int golf_biquad_frames_ola_bwd_f32(const float* gq, int64_t gq_stride
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }
+
+// ---- streaming form: golf_lti_frames_ola_stream_f32 ------------------------------------------------------------------
+// The same frames and the same overlap-add, run block by block.  A call filters frames [f0, f0+nf) -- each exactly once over
+// the life of the stream -- and writes the output samples [n0, n0+ny) that they finish.  The last S = ceil(W/hop) - 1
+// filtered frames (what an unfinished sample can still need) are carried between calls in a caller-owned (B, S, W) ring,
+// frame f at slot f % S.  Two launches:
+//   frames   the new frames into ws[b][S + f - f0], plus (extra blocks) the carried frames [f0 - S, f0) ring -> ws[b][0 .. S)
+//   OLA      the output samples from ws alone, in the one-shot's order (ff_ola_kernel), plus (extra blocks) the last
+//            min(S, nf) new frames ws -> ring
+// Neither launch reads what the same launch writes, so the copies need no ordering beyond the stream's.
+// Precision tier: per FRAME (its own kappa against GOLF_FF_KAPPA), not per wave of 4 frames as in ff_framesb_kernel: a
+// frame's bits then depend on its own inputs only, and the output does not depend on how the input is split into calls.
+namespace golf {
+
+struct FfStreamArgs {
+    const float* ex;    // window of x: samples x0 .. x0+nx-1, row stride ex_stride
+    int64_t ex_stride;
+    int xv;             // window samples that are real: min(nx, x_end - x0); the rest (and anything outside) reads 0
+    int xq, xr;         // x0 = (g0 + xq) * hop + xr, 0 <= xr < hop: window sample i lies in gain segment xq + (xr + i) / hop
+    const float* gain;  // rows g0 .. g0+ng-1, (B, ng)
+    int ng;
+    int glim;           // last gain segment (relative to g0): the one-shot's F - 2 once the utterance has ended, else ng - 2
+    const float* a;     // rows a0 .. a0+na-1, (B, na, M)
+    int na, far;        // far = f0 - a0
+    int xb;             // window sample of frame f0's position 0: f0*hop - W/2 - x0
+    int nf, S, M, hop, W;
+    const float* carry;
+    int ncin, cin_slot;   // carried frames copied into ws[b][S - ncin ..): ring slots cin_slot, cin_slot + 1, .. (mod S)
+    float* ws;          // (B, S + nf, W)
+};
+
+__device__ __forceinline__ float ff_stream_gain(const FfStreamArgs& p, const float* gb, int i, float inv_hop) {
+    const int s = p.xr + (i > 0 ? i : 0);
+    const int q = s / p.hop;
+    int n = s - q * p.hop, ft = p.xq + q;
+    if (ft > p.glim) { n += (ft - p.glim) * p.hop; ft = p.glim; }   // the one-shot's F - 2 clamp (unused rows: window bound)
+    if (ft < 0) { ft = 0; n = 0; }                                      // (samples no filtered frame reads)
+    const float g0 = gb[ft], g1 = gb[ft + 1 < p.ng ? ft + 1 : ft];
+    return fmaf((float)n, (g1 - g0) * inv_hop, g0);
+}
+
+__device__ __forceinline__ void ff_stream_copy_in(const FfStreamArgs& p, int j, int b, int tid, int nthr) {
+    const float* src = p.carry + ((size_t)b * p.S + (p.cin_slot + j) % p.S) * p.W;
+    float* dst = p.ws + ((size_t)b * (p.S + p.nf) + p.S - p.ncin + j) * p.W;
+    for (int k = tid; k < p.W; k += nthr) dst[k] = src[k];
+}
+
+// Block recursion of ff_framesb_kernel<NT, false>, frames from the windows of FfStreamArgs, the conditioning tier per frame.
+// grid (ceil(nf / 4) + ncin, B), 64 threads, dynamic LDS = the staged inputs U[3 hop + W].
+template <int NT>
+__global__ __launch_bounds__(64) void ff_stream_framesb_kernel(FfStreamArgs p, float kappa_max) {
+    constexpr int NS = (NT + 3) & ~3;
+    constexpr int NS4 = NS / 4;
+    static_assert(NS <= 24, "the output ring holds two blocks");
+    __shared__ __attribute__((aligned(16))) double Gs[4][16][NS];
+    __shared__ __attribute__((aligned(16))) float hs[4][32];
+    __shared__ __attribute__((aligned(16))) double yr[4][32];
+    extern __shared__ __attribute__((aligned(16))) float stage[];
+    const int lane = threadIdx.x, fr = lane >> 4, r = lane & 15;
+    const int b = blockIdx.y;
+    const int nw = (p.nf + 3) / 4;
+    if ((int)blockIdx.x >= nw) {
+        ff_stream_copy_in(p, blockIdx.x - nw, b, lane, 64);
+        return;
+    }
+    const int hop = p.hop, Wl = p.W;
+    const int fl = blockIdx.x * 4 + fr;     // frame f0 + fl
+    const bool mine = fl < p.nf;
+    const int flc = mine ? fl : p.nf - 1;
+    const BufRow xrow(p.ex + (size_t)b * p.ex_stride, p.xv);
+    {
+        const float inv_hop = 1.0f / (float)hop;
+        const float* gb = p.gain + (size_t)b * p.ng;
+        const int nu = 3 * hop + Wl;
+        const int ib = p.xb + blockIdx.x * 4 * hop;   // window sample of staged element 0
+        constexpr int UB = 8;
+        for (int i0 = lane; i0 < nu; i0 += 64 * UB) {
+            float xv_[UB], gv_[UB];
+#pragma unroll
+            for (int u = 0; u < UB; ++u) {
+                const int i = ib + i0 + 64 * u;
+                gv_[u] = ff_stream_gain(p, gb, i, inv_hop);
+                xv_[u] = xrow.ld(i);
+            }
+#pragma unroll
+            for (int u = 0; u < UB; ++u) {
+                const int i = i0 + 64 * u;
+                if (i < nu) stage[i] = xv_[u] * gv_[u];
+            }
+        }
+    }
+    FF_SETUP_T av[NT], v[NT];
+    {
+        const float* pa = p.a + ((size_t)b * p.na + p.far + flc) * p.M;
+        const int M = p.M;
+        float af[NT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) af[i] = pa[i < M ? i : M - 1];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            const FF_SETUP_T w = (FF_SETUP_T)af[i];
+            av[i] = i < M ? w : (FF_SETUP_T)0;
+            v[i] = i == 0 ? (FF_SETUP_T)1 : (FF_SETUP_T)0;
+        }
+    }
+    hs[fr][r] = 0.f;
+    yr[fr][r] = 0.0;
+    yr[fr][16 + r] = 0.0;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        if (r == 0) hs[fr][16 + s] = (float)v[0];
+        const FF_SETUP_T v0 = v[0];
+#pragma unroll
+        for (int j = 0; j + 1 < NT; ++j) v[j] = __builtin_fma(-av[j], v0, v[j + 1]);
+        v[NT - 1] = -av[NT - 1] * v0;
+        if (r == 0) {
+#pragma unroll
+            for (int j2 = 0; j2 < NS / 2; ++j2) {
+                double2 w2;
+                w2.x = 2 * j2 < NT ? v[(2 * j2) < NT ? 2 * j2 : 0] : 0.0;
+                w2.y = 2 * j2 + 1 < NT ? v[(2 * j2 + 1) < NT ? 2 * j2 + 1 : 0] : 0.0;
+                *reinterpret_cast<double2*>(&Gs[fr][s][2 * j2]) = w2;
+            }
+        }
+    }
+    __syncthreads();   // (the staged inputs and every frame's rows)
+    double Grow[NS];
+    float hrow[16];
+#pragma unroll
+    for (int j2 = 0; j2 < NS / 2; ++j2) {
+        const double2 w2 = *reinterpret_cast<const double2*>(&Gs[fr][r][2 * j2]);
+        Grow[2 * j2] = w2.x; Grow[2 * j2 + 1] = w2.y;
+    }
+#pragma unroll
+    for (int m = 0; m < 16; ++m) hrow[m] = hs[fr][16 + r - m];
+    // the frame's own kappa: the largest row sum of |G| over its 16 lanes (a wave holds 4 frames; each takes its own tier)
+    float kap = 0.f;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) kap += fabsf((float)Grow[j]);
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) kap = fmaxf(kap, __shfl_xor(kap, o));
+    const bool precise = !(kap <= kappa_max);   // uniform over the frame's lanes (NaN -> precise)
+    const float* xsrc = stage + (size_t)fr * hop;
+    float* orow = p.ws + ((size_t)b * (p.S + p.nf) + p.S + flc) * Wl;
+    const int nblk = Wl / 16;
+    auto xpart = [&](int k0) -> float {
+        float xv[16];
+        const float* xp = xsrc + k0;
+#pragma unroll
+        for (int m4 = 0; m4 < 4; ++m4) {
+            const float4 w4 = *reinterpret_cast<const float4*>(xp + 4 * m4);
+            xv[4 * m4] = w4.x; xv[4 * m4 + 1] = w4.y; xv[4 * m4 + 2] = w4.z; xv[4 * m4 + 3] = w4.w;
+        }
+        float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+#pragma unroll
+        for (int m = 0; m < 16; m += 4) {
+            acc0 = fmaf(hrow[m], xv[m], acc0);
+            acc1 = fmaf(hrow[m + 1], xv[m + 1], acc1);
+            acc2 = fmaf(hrow[m + 2], xv[m + 2], acc2);
+            acc3 = fmaf(hrow[m + 3], xv[m + 3], acc3);
+        }
+        return (acc0 + acc1) + (acc2 + acc3);
+    };
+    if (precise) {   // (divergent across the wave's frames: each 16-lane frame runs one of the two loops)
+        for (int blk = 0; blk < nblk; blk += 2) {
+#pragma unroll
+            for (int par = 0; par < 2; ++par) {
+                const int k0 = (blk + par) * 16;
+                double d0 = (double)xpart(k0), d1 = 0.0, d2 = 0.0, d3 = 0.0;
+#pragma unroll
+                for (int j4 = 0; j4 < NS4; ++j4) {
+                    const int i0 = ((16 * par - 4 - 4 * j4) & 31);
+                    const double2 lo = *reinterpret_cast<const double2*>(&yr[fr][i0]);
+                    const double2 hi = *reinterpret_cast<const double2*>(&yr[fr][i0 + 2]);
+                    d0 = __builtin_fma(Grow[4 * j4], hi.y, d0);
+                    d1 = __builtin_fma(Grow[4 * j4 + 1], hi.x, d1);
+                    d2 = __builtin_fma(Grow[4 * j4 + 2], lo.y, d2);
+                    d3 = __builtin_fma(Grow[4 * j4 + 3], lo.x, d3);
+                }
+                const double yd = (d0 + d1) + (d2 + d3);
+                wave_lds_fence();
+                yr[fr][16 * par + r] = yd;
+                if (mine) orow[k0 + r] = (float)yd;
+                wave_lds_fence();
+            }
+        }
+    } else {
+        float Gf[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) Gf[j] = (float)Grow[j];
+        float* yrf = reinterpret_cast<float*>(&yr[fr][0]);
+        for (int blk = 0; blk < nblk; blk += 2) {
+#pragma unroll
+            for (int par = 0; par < 2; ++par) {
+                const int k0 = (blk + par) * 16;
+                float a0 = xpart(k0), a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+                for (int j4 = 0; j4 < NS4; ++j4) {
+                    const int i0 = ((16 * par - 4 - 4 * j4) & 31);
+                    const float4 w4 = *reinterpret_cast<const float4*>(yrf + i0);
+                    a0 = fmaf(Gf[4 * j4], w4.w, a0);
+                    a1 = fmaf(Gf[4 * j4 + 1], w4.z, a1);
+                    a2 = fmaf(Gf[4 * j4 + 2], w4.y, a2);
+                    a3 = fmaf(Gf[4 * j4 + 3], w4.x, a3);
+                }
+                const float y = (a0 + a1) + (a2 + a3);
+                wave_lds_fence();
+                yrf[16 * par + r] = y;
+                if (mine) orow[k0 + r] = y;
+                wave_lds_fence();
+            }
+        }
+    }
+}
+
+// Shapes the block recursion does not take: one lane per frame, the direct form of ff_frames_kernel (fp32, the taps summed
+// in two interleaved chains).  grid (ceil(nf / 64) + ncin, B), 64 threads.
+template <int NT>
+__global__ __launch_bounds__(64) void ff_stream_frames_kernel(FfStreamArgs p) {
+    const int b = blockIdx.y;
+    const int nw = (p.nf + 63) / 64;
+    if ((int)blockIdx.x >= nw) {
+        ff_stream_copy_in(p, blockIdx.x - nw, b, threadIdx.x, 64);
+        return;
+    }
+    const int fl = blockIdx.x * 64 + threadIdx.x;
+    if (fl >= p.nf) return;
+    const float* pa = p.a + ((size_t)b * p.na + p.far + fl) * p.M;
+    float av[NT], h[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        av[i] = i < p.M ? pa[i < p.M ? i : 0] : 0.f;
+        h[i] = 0.f;                                  // h[i] = y[k - 1 - i]
+    }
+    const float inv_hop = 1.0f / (float)p.hop;
+    const float* gb = p.gain + (size_t)b * p.ng;
+    const BufRow xrow(p.ex + (size_t)b * p.ex_stride, p.xv);
+    float* out = p.ws + ((size_t)b * (p.S + p.nf) + p.S + fl) * p.W;
+    const int ib = p.xb + fl * p.hop;
+    for (int k = 0; k < p.W; ++k) {
+        const int i = ib + k;
+        const float x = xrow.ld(i) * ff_stream_gain(p, gb, i, inv_hop);
+        float ra = 0.f, rb = 0.f;
+#pragma unroll
+        for (int j = NT - 1; j >= 1; --j) {
+            if (j & 1) ra = fmaf(av[j], h[j], ra);
+            else       rb = fmaf(av[j], h[j], rb);
+        }
+        const float y = fmaf(-av[0], h[0], x - (ra + rb));
+#pragma unroll
+        for (int j = NT - 1; j >= 1; --j) h[j] = h[j - 1];
+        h[0] = y;
+        out[k] = y;
+    }
+}
+
+// Output samples n0 + i, i < ny, exactly as ff_ola_kernel forms them (frames in ascending f, fmaf, the window sum as the
+// normaliser), with the frames at ws slot f - (f0 - S); extra blocks copy the last ncout new frames into the carried ring.
+//   m = mb + i: the sample's position relative to ws slot 0 (n + W/2 - (f0 - S)*hop);  frames [fmin, fmax] exist.
+__global__ __launch_bounds__(256) void ff_stream_ola_kernel(const float* __restrict__ ws, const float* __restrict__ window,
+                                                            float* __restrict__ y, int64_t y_stride, float* __restrict__ carry,
+                                                            int ny, int mb, int fmin, int fmax, int nslot, int hop, int Wl,
+                                                            int S, int ncout, int cout_slot) {
+    const int b = blockIdx.y;
+    const int nob = (ny + 255) / 256;
+    if ((int)blockIdx.x >= nob) {
+        const int j = blockIdx.x - nob;
+        const float* src = ws + ((size_t)b * nslot + nslot - ncout + j) * Wl;
+        float* dst = carry + ((size_t)b * S + (cout_slot + j) % S) * Wl;
+        for (int k = threadIdx.x; k < Wl; k += 256) dst[k] = src[k];
+        return;
+    }
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ny) return;
+    const int m = mb + i;
+    int fhi = m / hop;
+    if (fhi > fmax) fhi = fmax;
+    int flo = (m - Wl + hop) / hop;
+    if (m - Wl + 1 <= 0) flo = 0;
+    if (flo < fmin) flo = fmin;
+    const float* wf = ws + (size_t)b * nslot * Wl;
+    float acc = 0.f, norm = 0.f;
+    if (Wl <= 4 * hop) {
+        float wk[4], vf[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int f = flo + u;
+            const int k = m - f * hop;
+            const bool ok = f <= fhi && k >= 0 && k < Wl;
+            const int kc = ok ? k : 0, fc = ok ? f : flo;
+            wk[u] = window[kc];
+            vf[u] = wf[(size_t)fc * Wl + kc];
+            if (!ok) { wk[u] = 0.f; vf[u] = 0.f; }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            acc = fmaf(wk[u], vf[u], acc);
+            norm += wk[u];
+        }
+    } else {
+        for (int f = flo; f <= fhi; ++f) {
+            const int k = m - f * hop;
+            if (k < 0 || k >= Wl) continue;
+            const float wk = window[k];
+            acc = fmaf(wk, wf[(size_t)f * Wl + k], acc);
+            norm += wk;
+        }
+    }
+    y[(size_t)b * y_stride + i] = acc / norm;
+}
+
+static int ff_stream_S(int W, int hop) { return (W + hop - 1) / hop - 1; }
+
+}  // namespace golf
+
+extern "C" size_t golf_lti_frames_stream_state_bytes(int B, int W, int hop, int M) {
+    if (B < 1 || hop < 1 || W < 2 * hop || M < 1 || M > 38) return 0;
+    return sizeof(float) * (size_t)B * ff_stream_S(W, hop) * W;
+}
+
+extern "C" int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride, int64_t x0, int nx, int64_t x_end,
+                                              const float* gain, int64_t g0, int ng, int64_t g_end, const float* a,
+                                              int64_t a0, int na, const float* window, int64_t f0, int nf, float* y,
+                                              int64_t y_stride, int64_t n0, int ny, int B, int M, int hop, int W,
+                                              float* carry, void* ws, size_t ws_bytes, void* stream) {
+    if (B < 1 || M < 1 || hop < 1 || W < 1 || nf < 0 || ny < 0 || nx < 0 || ng < 0 || na < 0 || x0 < 0 || g0 < 0 ||
+        a0 < 0 || f0 < 0 || n0 < 0)
+        return fail(GOLF_EINVAL, "lti_frames_stream: bad size or negative start");
+    if (W < 2 * hop) return fail(GOLF_EINVAL, "lti_frames_stream: window %d < 2*hop %d", W, 2 * hop);
+    if (M > 38) return fail(GOLF_EUNSUPPORTED, "lti_frames_stream: need M <= 38 (M=%d)", M);
+    if (!window || !carry || (nf > 0 && (!ex || !gain || !a)) || ((nf > 0 || ny > 0) && !ws) || (ny > 0 && !y))
+        return fail(GOLF_EINVAL, "lti_frames_stream: null pointer");
+    if ((x_end < 0) != (g_end < 0))
+        return fail(GOLF_EINVAL, "lti_frames_stream: x_end and g_end are both open (< 0) or both set");
+    const bool fin = x_end >= 0;
+    const int64_t pad = W / 2, H = hop;
+    const int S = ff_stream_S(W, hop);
+    int64_t nfr = INT64_MAX, Ty = INT64_MAX;
+    if (fin) {
+        if (x_end < 1 || g_end < 2) return fail(GOLF_EINVAL, "lti_frames_stream: x_end %lld, g_end %lld (need >= 1, >= 2)",
+                                                (long long)x_end, (long long)g_end);
+        if (x_end > (g_end - 1) * H + 1) return fail(GOLF_EINVAL, "lti_frames_stream: x_end exceeds (g_end-1)*hop+1");
+        nfr = (x_end + 2 * pad - W) / H + 1;
+        Ty = (nfr - 1) * H + W - 2 * pad;
+        if (nfr < 1 || nfr > g_end) return fail(GOLF_EINVAL, "lti_frames_stream: %lld frames vs %lld coefficient frames",
+                                                (long long)nfr, (long long)g_end);
+        if (f0 + nf > nfr) return fail(GOLF_EINVAL, "lti_frames_stream: frames past the last one (%lld)", (long long)nfr);
+        if (n0 + ny > Ty) return fail(GOLF_EINVAL, "lti_frames_stream: samples past the end (%lld)", (long long)Ty);
+    }
+    if ((nf > 0 && nx > 0 && ex_stride < nx) || (ny > 0 && y_stride < ny))
+        return fail(GOLF_EINVAL, "lti_frames_stream: row stride too small");
+    if ((int64_t)(S + nf) * W >= (1ll << 29) || nx >= (1 << 29) || (int64_t)(S + nf + 1) * H >= (1ll << 30))
+        return fail(GOLF_EUNSUPPORTED, "lti_frames_stream: call too large (%d frames, %d samples)", nf, nx);
+    // frames [f0, f0+nf): their coefficient rows, their samples and the gain rows those samples interpolate
+    auto seg = [&](int64_t t) { const int64_t s = t / H; return fin && s > g_end - 2 ? g_end - 2 : s; };
+    if (nf > 0) {
+        if (f0 < a0 || f0 + nf > a0 + na) return fail(GOLF_EINVAL, "lti_frames_stream: the a window does not cover the frames");
+        const int64_t tlo = std::max<int64_t>(0, f0 * H - pad);
+        int64_t thi = (f0 + nf - 1) * H - pad + W;
+        if (fin) thi = std::min(thi, x_end);
+        if (thi > tlo) {
+            if (x0 > tlo || x0 + nx < thi) return fail(GOLF_EINVAL, "lti_frames_stream: the excitation window does not cover "
+                                                       "samples [%lld, %lld)", (long long)tlo, (long long)thi);
+            if (g0 > seg(tlo) || seg(thi - 1) + 1 >= g0 + ng)
+                return fail(GOLF_EINVAL, "lti_frames_stream: the gain window does not cover the frames' samples");
+        }
+    }
+    // samples [n0, n0+ny): every frame they need is filtered by now, and the carried ring still holds the earliest one
+    auto flo = [&](int64_t n) { const int64_t d = n + pad - W + 1; return d <= 0 ? (int64_t)0 : (d + H - 1) / H; };
+    const int64_t fdone = f0 + nf;
+    if (ny > 0) {
+        const int64_t fhi = std::min((n0 + ny - 1 + pad) / H, nfr - 1);
+        if (fhi >= fdone) return fail(GOLF_EINVAL, "lti_frames_stream: sample %lld needs frame %lld, not filtered yet",
+                                      (long long)(n0 + ny - 1), (long long)fhi);
+        if (flo(n0) < f0 - S) return fail(GOLF_EINVAL, "lti_frames_stream: sample %lld needs frame %lld; the carry holds "
+                                          "frames from %lld", (long long)n0, (long long)flo(n0), (long long)(f0 - S));
+    }
+    if (nf > 0 && n0 > std::max<int64_t>(0, f0 * H - pad))
+        return fail(GOLF_EINVAL, "lti_frames_stream: samples before %lld were written without frame %lld", (long long)n0,
+                    (long long)f0);
+    if (!(fin && n0 + ny == Ty) && flo(n0 + ny) < fdone - S)
+        return fail(GOLF_EINVAL, "lti_frames_stream: write the samples up to %lld before filtering frame %lld (the carry "
+                    "holds %d frames)", (long long)((fdone - S) * H - pad + W - 1), (long long)(fdone - 1), S);
+    const size_t need = sizeof(float) * (size_t)B * (S + nf) * W;
+    if ((nf > 0 || ny > 0) && (ws_bytes < need || ((uintptr_t)ws & 255)))
+        return fail(GOLF_EWORKSPACE, "lti_frames_stream: workspace needs %zu bytes, 256-aligned (got %zu)", need, ws_bytes);
+    if (nf == 0 && ny == 0) return GOLF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    FfStreamArgs p;
+    p.ex = ex;
+    p.ex_stride = ex_stride;
+    p.xv = (int)std::max<int64_t>(0, fin ? std::min<int64_t>(nx, x_end - x0) : nx);
+    const int64_t xq = x0 / H - g0;
+    p.xq = (int)std::max<int64_t>(std::min<int64_t>(xq, 1 << 30), -(1 << 30));
+    p.xr = (int)(x0 % H);
+    p.gain = gain;
+    p.ng = ng;
+    p.glim = (int)std::min<int64_t>(ng - 2, fin ? g_end - 2 - g0 : INT32_MAX);
+    p.a = a;
+    p.na = na;
+    p.far = (int)(nf > 0 ? f0 - a0 : 0);
+    const int64_t xb = f0 * H - pad - x0;
+    p.xb = (int)std::max<int64_t>(std::min<int64_t>(xb, 1 << 30), -(1 << 30));
+    p.nf = nf;
+    p.S = S;
+    p.M = M;
+    p.hop = hop;
+    p.W = W;
+    p.carry = carry;
+    p.ncin = ny > 0 ? (int)std::min<int64_t>(S, f0) : 0;
+    p.cin_slot = (int)((f0 - p.ncin) % S);
+    p.ws = (float*)ws;
+    // the one-shot's kernel choice: the first (ring, taps) with M <= taps and ring <= hop, the block recursion where it fits
+    int nt_ring = 0;
+    const int rings[5][2] = {{8, 6}, {16, 14}, {24, 22}, {32, 30}, {40, 38}};
+    for (auto& rt : rings)
+        if (M <= rt[1] && rt[0] <= hop) { nt_ring = rt[1]; break; }
+    const size_t ldsb = sizeof(float) * (3 * (size_t)hop + (size_t)W);
+    const bool blocked = nt_ring > 0 && nt_ring <= 24 && ff_block_ok(W, hop, ldsb);
+    if (nf > 0 || p.ncin > 0) {
+        if (blocked) {
+#define GOLF_FFS_BLOCK(nt)                                                                                                  \
+    if (nt_ring == (nt)) {                                                                                                  \
+        static const hipError_t attr = hipFuncSetAttribute((const void*)ff_stream_framesb_kernel<nt>,                       \
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);          \
+        if (attr != hipSuccess) return fail((int)attr, "lti_frames_stream: cannot raise the dynamic LDS limit");            \
+        hipLaunchKernelGGL((ff_stream_framesb_kernel<nt>), dim3((unsigned)(ceil_div(nf, 4) + p.ncin), B), dim3(64), ldsb, \
+                           st, p, (float)GOLF_FF_KAPPA);                                                                    \
+    }
+            GOLF_FFS_BLOCK(6)
+            GOLF_FFS_BLOCK(14)
+            GOLF_FFS_BLOCK(22)
+#undef GOLF_FFS_BLOCK
+        } else {
+            const dim3 grid((unsigned)(ceil_div(nf, 64) + p.ncin), B);
+            if (M <= 6) hipLaunchKernelGGL((ff_stream_frames_kernel<6>), grid, dim3(64), 0, st, p);
+            else if (M <= 14) hipLaunchKernelGGL((ff_stream_frames_kernel<14>), grid, dim3(64), 0, st, p);
+            else if (M <= 22) hipLaunchKernelGGL((ff_stream_frames_kernel<22>), grid, dim3(64), 0, st, p);
+            else if (M <= 30) hipLaunchKernelGGL((ff_stream_frames_kernel<30>), grid, dim3(64), 0, st, p);
+            else hipLaunchKernelGGL((ff_stream_frames_kernel<38>), grid, dim3(64), 0, st, p);
+        }
+        GOLF_LAUNCH_CHECK();
+    }
+    const int ncout = (int)std::min<int64_t>(S, nf);
+    if (ny > 0 || ncout > 0) {
+        const int64_t fbase = f0 - S;
+        const int mb = (int)(n0 + pad - fbase * H);
+        const int fmin = (int)std::max<int64_t>(0, -fbase);
+        const int fmax = (int)(std::min<int64_t>(fdone, nfr) - 1 - fbase);
+        hipLaunchKernelGGL(ff_stream_ola_kernel, dim3((unsigned)(ceil_div(ny, 256) + ncout), B), dim3(256), 0, st,
+                           (const float*)ws, window, y, y_stride, carry, ny, mb, fmin, fmax, S + nf, hop, W, S, ncout,
+                           (int)((fdone - ncout) % S));
+        GOLF_LAUNCH_CHECK();
+    }
+    return GOLF_OK;
+}

@@ -417,6 +417,46 @@ def lti_frames_ola(ex, gain, a, window, hop: int) -> torch.Tensor:
     return _LTIFramesOLA.apply(ex, gain, a, window, int(hop))
 
 
+def lti_frames_stream_carry(B: int, W: int, hop: int, M: int, device) -> torch.Tensor:
+    """The zeroed (B, ceil(W/hop) - 1, W) fp32 carry of ``lti_frames_ola_stream``: the last filtered frames."""
+    nbytes = _lib.load().golf_lti_frames_stream_state_bytes(int(B), int(W), int(hop), int(M))
+    if nbytes == 0:
+        raise _lib.GolfError(f"lti_frames_ola_stream: no carry for B={B}, W={W}, hop={hop}, M={M} (W >= 2*hop, M <= 38)")
+    return torch.zeros(int(B), nbytes // (4 * int(B) * int(W)), int(W), dtype=torch.float32, device=device)
+
+
+def lti_frames_ola_stream(ex, gain, a, window, hop: int, carry=None, *, x0: int, g0: int, a0: int, f0: int, nf: int,
+                          n0: int, ny: int, x_end: int = -1, g_end: int = -1):
+    """One call of the frame-wise filter run block by block (golf_lti_frames_ola_stream_f32), global indices throughout:
+    filters frames [f0, f0+nf) and returns output samples [n0, n0+ny) as a (B, ny) fp32 tensor, together with the carry
+    (allocated when ``carry`` is None: pass None to the first call and the returned one to every later call).
+    ``ex`` (B, nx) holds samples x0 .., ``gain`` (B, ng) rows g0 .., ``a`` (B, na, M) rows a0 ..; ``x_end`` / ``g_end``: the
+    utterance's Tx and F once it has ended (-1 before).  Inference only; fp16 / bf16 tracks are cast to fp32 first."""
+    _inference_only("lti_frames_ola_stream", ex, gain, a)
+    ex, gain, a = _rows(ex.float()), gain.float().contiguous(), a.float().contiguous()
+    window = window.float().contiguous()
+    _lib.require_device(ex, gain, a, window)
+    B, nx = ex.shape
+    M, W = a.shape[2], window.numel()
+    if gain.shape[0] != B or a.shape[0] != B or gain.ndim != 2:
+        raise _lib.GolfError(f"lti_frames_ola_stream: ex {tuple(ex.shape)}, gain {tuple(gain.shape)}, a {tuple(a.shape)}")
+    if carry is None:
+        carry = lti_frames_stream_carry(B, W, hop, M, ex.device)
+    if not carry.is_cuda or carry.dtype != torch.float32 or not carry.is_contiguous() or carry.shape[0] != B:
+        raise _lib.GolfError(f"lti_frames_ola_stream: carry {tuple(carry.shape)} {carry.dtype} (from lti_frames_stream_carry)")
+    y = torch.empty(B, int(ny), dtype=torch.float32, device=ex.device)
+    S = carry.shape[1]
+    ws = _workspace(4 * B * (S + int(nf)) * W, ex.device) if nf > 0 or ny > 0 else None
+    lib = _lib.load()
+    rc = lib.golf_lti_frames_ola_stream_f32(ex.data_ptr(), ex.stride(0), int(x0), nx, int(x_end), gain.data_ptr(), int(g0),
+                                            gain.shape[1], int(g_end), a.data_ptr(), int(a0), a.shape[1], window.data_ptr(),
+                                            int(f0), int(nf), y.data_ptr(), y.stride(0), int(n0), int(ny), B, M, int(hop), W,
+                                            carry.data_ptr(), _lib.ptr(ws), 0 if ws is None else ws.numel(),
+                                            _lib.stream_ptr())
+    _lib.check(rc, "golf_lti_frames_ola_stream_f32")
+    return y, carry
+
+
 # ------------------------------------------------------------------------------------------------
 # control transform of the LPC filters: logits -> direct-form coefficients (reference models/utils.py:581-593)
 # ------------------------------------------------------------------------------------------------

@@ -207,6 +207,30 @@ int golf_lti_frames_ola_fwd_f32(const float* ex, int64_t ex_stride, const float*
                                 int B, int Tx, int F, int M, int hop, int W, int Ty,
                                 void* ws, size_t ws_bytes, void* stream);
 
+/* Streaming form (additive in ABI 6): the same frames and overlap-add, block by block, in global sample / frame indices.
+ * x[n] = ex[n]*up(gain)[n] for 0 <= n < x_end (0 elsewhere); frame f covers x[f*hop - W/2, f*hop - W/2 + W); y as above.
+ * One call filters frames [f0, f0+nf) -- each frame once over the stream -- and writes samples [n0, n0+ny) to y (B, ny).
+ *   ex      window of the excitation: global samples [x0, x0+nx), row stride ex_stride
+ *   gain    rows [g0, g0+ng) (B, ng);  a  rows [a0, a0+na) (B, na, M), both contiguous
+ *   x_end, g_end  -1 while the utterance is open; once it has ended, Tx = min(T_ex, (g_end-1)*hop+1) and F: the frame range
+ *           and the normaliser are clipped to nfr = (Tx + 2*(W/2) - W)/hop + 1 and up(gain) to segment F-2 as in the one-shot
+ *   carry   caller-owned (B, S, W) fp32 device buffer, zero-initialised, S = ceil(W/hop) - 1 (golf_lti_frames_stream_state_bytes):
+ *           the last S filtered frames, frame f at slot f % S
+ *   ws      scratch of 4*B*(S+nf)*W bytes, 256-aligned (NULL with nf = ny = 0)
+ * Requirements (refused before any launch): W >= 2*hop, M <= 38; the windows cover frames [f0, f0+nf), their samples and
+ * the gain rows those samples interpolate; the samples [n0, n0+ny) need no frame >= f0+nf (nor one older than the carry
+ * holds); frame f0 reaches no sample before n0; after the call no unwritten sample needs a frame older than f0+nf-S (write
+ * every sample the frames finish).  Each sample sums its frames in ascending f with fmaf, the window sum as its normaliser,
+ * as the one-shot does.  The block recursion serves the shapes where the one-shot uses it, with the fp64 feedback tier chosen
+ * per FRAME from its own kappa (the one-shot chooses per wave of 4 frames): a frame's bits depend on its own inputs only, so
+ * the output does not depend on how the input is split into calls.  Other shapes run a direct-form kernel; any M <= 38 and
+ * hop >= 1.  Two launches (frames, then overlap-add); none when nf = ny = 0.  No host<->device synchronisation. */
+size_t golf_lti_frames_stream_state_bytes(int B, int W, int hop, int M);
+int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride, int64_t x0, int nx, int64_t x_end,
+                                   const float* gain, int64_t g0, int ng, int64_t g_end, const float* a, int64_t a0, int na,
+                                   const float* window, int64_t f0, int nf, float* y, int64_t y_stride, int64_t n0, int ny,
+                                   int B, int M, int hop, int W, float* carry, void* ws, size_t ws_bytes, void* stream);
+
 /* Custom backward of the above (what autograd computes in the reference through conv_transpose1d, lfilter, unfold,
  * the zero pad and the gain product; closed form in oracle/golf_oracle.py::lti_frames_ola_backward, pinned by
  * tests/golden/g15):  g_q = gy/norm;  u_f = the frame's all-pole recursion run backwards in time on window*g_q;
