@@ -2520,6 +2520,180 @@ extern "C" int golf_harmonic_osc_bwd_amp_f32(const float* g_out, int64_t g_out_s
     return GOLF_OK;
 }
 
+// =============================================================================================
+// Streaming harmonic oscillator (golf_harmonic_osc_stream_f32): harm_kernel's samples of a run of coarse phase segments
+// j0 .. j0+nseg-1 from a carried Q0.64 phase.  Two launches: one workgroup per utterance scans the run's segment totals (the
+// one-shot scan's own integers, osc_phase_tile_kernel) onto the carry and writes the phase before every segment; then one
+// thread per output sample renders it as harm_kernel does, in global sample indices, with the amplitude / tscale rows read from
+// the windows the caller passes and the one-shot's end-of-track clamps applied once the track's length is known.
+// =============================================================================================
+namespace golf {
+__global__ __launch_bounds__(256) void harm_stream_phase_kernel(const float* __restrict__ phase, int64_t phase_stride, int nseg,
+                                                                int final_point, int P, u64* __restrict__ acc,
+                                                                u64* __restrict__ seg_base) {
+    __shared__ u64 wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* pb = phase + (size_t)b * phase_stride;
+    const int nall = nseg + final_point;
+    u64* ob = seg_base + (size_t)b * nall;
+    const double scale_a = 18446744073709551616.0, scale_d = scale_a / (double)P;
+    const u64 tri = (u64)P * (u64)(P - 1) / 2;
+    u64 carry = acc[b];
+    for (int base = 0; base < nall; base += 256) {
+        const int i = base + tid;
+        u64 seg = 0;   // the final point's segment is the one-shot's last (j = Tp-1): total 0
+        if (i < nseg) {
+            const float p0 = pb[i], p1 = pb[i + 1];
+            seg = (u64)P * osc_fix_a(p0, scale_a) + osc_fix_d(p0, p1, scale_d) * tri;
+        }
+        const u64 incl = wave_incl_scan(seg, lane);
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        u64 ph = carry + incl - seg, tot = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wv) ph += wsum[w];
+            tot += wsum[w];
+        }
+        __syncthreads();
+        carry += tot;
+        if (i < nall) ob[i] = ph;
+    }
+    if (tid == 0) acc[b] = carry;
+}
+
+// the row a sample interpolates from: end = -1 while the track is open, else its row count (the one-shot's clamps)
+__host__ __device__ __forceinline__ int64_t harm_stream_row(int64_t t, int hop, int64_t end) {
+    const int64_t r = t / hop;
+    return end < 0 ? r : (end >= 2 ? (r < end - 2 ? r : end - 2) : 0);
+}
+
+__global__ __launch_bounds__(HARM_THREADS) void harm_stream_kernel(
+    const float* __restrict__ phase, int64_t phase_stride, const u64* __restrict__ seg_base, int nseg, int final_point, int P,
+    int64_t j0, const float* __restrict__ amp, int64_t a_first, int na, int64_t a_end, int amp_hop,
+    const float* __restrict__ tscale, int64_t ts_stride, int64_t s_first, int64_t s_end, int ts_hop,
+    const float* __restrict__ hscale, int H, float* __restrict__ out, int64_t out_stride, int nrows_lds) {
+    extern __shared__ __attribute__((aligned(16))) float hsm[];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int nall = nseg + final_point, n = nseg * P + final_point;
+    float* hs = hsm;                     // [H] per-harmonic scale (used directly when there is no amplitude tensor)
+    float* rows = hsm + ((H + 3) & ~3);  // [nrows_lds][H] amplitude rows, per-harmonic scale already folded in
+    for (int h = tid; h < H; h += HARM_THREADS) hs[h] = hscale ? hscale[h] : 1.0f;
+    const float inv_ah = 1.0f / (float)amp_hop, inv_sh = 1.0f / (float)ts_hop;
+    const int i_lo = blockIdx.x * HARM_THREADS;
+    const int64_t t0 = j0 * P;
+    int64_t row_lo = 0;
+    if (amp) {  // stage the amplitude rows this block interpolates between (the window holds them: checked by the host)
+        row_lo = harm_stream_row(t0 + i_lo, amp_hop, a_end);
+        const float* ab = amp + ((size_t)b * na + (size_t)(row_lo - a_first)) * H;
+        const int64_t left = a_first + na - row_lo;
+        const int nr = (int)(left < nrows_lds ? left : nrows_lds);
+        for (int e = tid; e < nr * H; e += HARM_THREADS) rows[e] = ab[e] * (hscale ? hscale[e % H] : 1.0f);
+    }
+    __syncthreads();
+    const int i = i_lo + tid;
+    if (i >= n) return;
+    const int64_t t = t0 + i;
+    // the phase as harm_sample forms it: segment js of the call, sample k of it (the final point: js = nseg, k = 0, p1 = p0)
+    const float* pb = phase + (size_t)b * phase_stride;
+    const int js = i / P, k = i - js * P;
+    const float p0 = pb[js], p1 = js < nseg ? pb[js + 1] : p0;
+    const double scale_a = 18446744073709551616.0, scale_d = scale_a / (double)P;
+    const u64 a = osc_fix_a(p0, scale_a), d = osc_fix_d(p0, p1, scale_d);
+    HarmSample sm;
+    sm.Phi = seg_base[(size_t)b * nall + js] + (u64)(k + 1) * a + d * ((u64)k * (u64)(k + 1) / 2);
+    sm.p = fmaf((float)k, (p1 - p0) / (float)P, p0);
+    int64_t fa = 0;
+    float wa = 0.f;
+    if (amp && a_end != 1) { fa = harm_stream_row(t, amp_hop, a_end); wa = (float)(t - fa * amp_hop) * inv_ah; }
+    float ts = 1.0f;
+    if (tscale) {
+        const int64_t fs = harm_stream_row(t, ts_hop, s_end);
+        const float ws = s_end == 1 ? 0.f : (float)(t - fs * ts_hop) * inv_sh;
+        const float* sb = tscale + (size_t)b * ts_stride - s_first;
+        const float s0 = sb[fs], s1 = sb[s_end == 1 ? fs : fs + 1];
+        ts = fmaf(ws, s1 - s0, s0);
+    }
+    // from here on harm_kernel's arithmetic, operation for operation (without the optional phase terms)
+    int hl = sm.p > 0.f ? (int)fminf(0.5f / sm.p, (float)H) : H;
+    while (hl < H && (float)(hl + 1) * sm.p < 0.5f) ++hl;
+    while (hl > 0 && !((float)hl * sm.p < 0.5f)) --hl;
+    float rs, rc;  // rotation by theta = 2 pi Phi
+    harm_sincos(sm.Phi, rs, rc);
+    float acc = 0.f;
+    const float* r0 = amp ? rows + (size_t)(fa - row_lo) * H : hs;
+    const float* r1 = amp ? (a_end == 1 ? r0 : r0 + H) : hs;
+    for (int h0 = 1; h0 <= H; h0 += HARM_ANCHOR) {
+        float s, c;
+        harm_sincos((u64)h0 * sm.Phi, s, c);
+#pragma unroll
+        for (int q = 0; q < HARM_ANCHOR; ++q) {
+            const int h = h0 + q;
+            if (h <= H) {  // uniform
+                const float a0 = r0[h - 1];
+                const float av = fmaf(wa, r1[h - 1] - a0, a0);
+                acc = h <= hl ? fmaf(av, s, acc) : acc;
+                const float sn = fmaf(s, rc, c * rs), cn = fmaf(c, rc, -s * rs);
+                s = sn;
+                c = cn;
+            }
+        }
+    }
+    out[(size_t)b * out_stride + i] = acc * ts;
+}
+}  // namespace golf
+
+extern "C" int golf_harmonic_osc_stream_f32(const float* phase, int64_t phase_stride, int nseg, int final_point, int phase_hop,
+                                            const float* amp, int64_t a_first, int na, int64_t a_end, int amp_hop,
+                                            const float* tscale, int64_t ts_stride, int64_t s_first, int ns, int64_t s_end,
+                                            int ts_hop, const float* hscale, int H, int64_t j0, uint64_t* acc, float* out,
+                                            int64_t out_stride, int B, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "harmonic_osc_stream";
+    if (!phase || !acc || (!out && nseg + final_point > 0)) return fail(GOLF_EINVAL, "%s: null pointer", who);
+    if (B < 1 || nseg < 0 || (final_point != 0 && final_point != 1) || phase_hop < 1 || H < 1 || H > 4096 || j0 < 0)
+        return fail(GOLF_EINVAL, "%s: bad size (B=%d nseg=%d final_point=%d phase_hop=%d H=%d j0=%lld)", who, B, nseg,
+                    final_point, phase_hop, H, (long long)j0);
+    const int64_t P = phase_hop, n = (int64_t)nseg * P + final_point;
+    if (n > (int64_t)1 << 30 || (j0 + nseg + 1) * P > ((int64_t)1 << 40)) return fail(GOLF_EINVAL, "%s: call too long", who);
+    if (phase_stride < nseg + 1 || out_stride < n) return fail(GOLF_EINVAL, "%s: row stride too small", who);
+    const int64_t t_lo = j0 * P, t_hi = t_lo + n - 1;   // the global samples of the call
+    // a window [first, first+cnt) of a track at `hop`, `end` its row count once known (-1 before): the rows the call's samples
+    // interpolate must lie in it, and a closed track must reach the last sample (the one-shot's Tout)
+    auto window_ok = [&](int64_t first, int cnt, int64_t end, int hop) {
+        if (hop < 1) return false;
+        if (n == 0) return true;   // (an empty call reads no row)
+        if (first < 0 || cnt < 1 || (end >= 0 && (end < 1 || first + cnt > end))) return false;
+        if (end >= 1 && t_hi > (hop > 1 ? (end - 1) * hop : end - 1)) return false;
+        const int64_t r_lo = harm_stream_row(t_lo, hop, end), r_hi = harm_stream_row(t_hi, hop, end) + (end == 1 ? 0 : 1);
+        return r_lo >= first && r_hi < first + cnt;
+    };
+    if (amp && !window_ok(a_first, na, a_end, amp_hop))
+        return fail(GOLF_EINVAL, "%s: amplitude rows [%lld, +%d) (end %lld, hop %d) do not cover samples [%lld, %lld]", who,
+                    (long long)a_first, na, (long long)a_end, amp_hop, (long long)t_lo, (long long)t_hi);
+    if (tscale && (ts_stride < ns || !window_ok(s_first, ns, s_end, ts_hop)))
+        return fail(GOLF_EINVAL, "%s: tscale rows [%lld, +%d) (end %lld, hop %d) do not cover samples [%lld, %lld]", who,
+                    (long long)s_first, ns, (long long)s_end, ts_hop, (long long)t_lo, (long long)t_hi);
+    const int nrows = HARM_THREADS / (amp ? amp_hop : HARM_THREADS) + 3;   // harm_geom's staging, and harm_check's limit
+    if (amp && (size_t)(nrows + 1) * H * sizeof(float) > 60 * 1024)
+        return fail(GOLF_EUNSUPPORTED, "%s: amplitude hop %d too fine for %d harmonics (LDS staging); pass amplitudes "
+                    "at a coarser hop or fold them into tscale/hscale", who, amp_hop, H);
+    const int nall = nseg + final_point;
+    if (nall == 0) return GOLF_OK;
+    const size_t need = sizeof(u64) * (size_t)B * nall;
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255))
+        return fail(GOLF_EWORKSPACE, "%s: workspace needs %zu bytes, 256-aligned (got %zu)", who, need, ws_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    u64* seg_base = (u64*)ws;
+    hipLaunchKernelGGL(harm_stream_phase_kernel, dim3(B), dim3(256), 0, st, phase, phase_stride, nseg, final_point, (int)P,
+                       (u64*)acc, seg_base);
+    GOLF_LAUNCH_CHECK();
+    const size_t lds = sizeof(float) * (((H + 3) & ~3) + (size_t)(amp ? nrows : 1) * H);
+    hipLaunchKernelGGL(harm_stream_kernel, dim3((unsigned)ceil_div(n, HARM_THREADS), B), dim3(HARM_THREADS), lds, st, phase,
+                       phase_stride, (const u64*)seg_base, nseg, final_point, (int)P, j0, amp, a_first, na, a_end, amp_hop,
+                       tscale, ts_stride, s_first, s_end, ts_hop, hscale, H, out, out_stride, nrows);
+    GOLF_LAUNCH_CHECK();
+    return GOLF_OK;
+}
+
 
 // =============================================================================================
 // Running phase of the general (fully differentiable) table oscillators, golf_amd.functional.wavetable_osc:

@@ -1349,6 +1349,47 @@ def harmonic_osc(phase, H: int, phase_hop: int = 1, amp=None, amp_hop: int = 1, 
                               initial_phase)
 
 
+def harmonic_osc_stream(phase, j0: int, nseg: int, final_point: bool, phase_hop: int, H: int, acc: torch.Tensor, amp=None,
+                        a_first: int = 0, a_end: int = -1, amp_hop: int = 1, tscale=None, s_first: int = 0, s_end: int = -1,
+                        ts_hop: int = 1, hscale=None) -> torch.Tensor:
+    """``harmonic_osc``'s output samples of coarse phase segments j0 .. j0+nseg-1 (+ the utterance's last sample with
+    ``final_point``) from the carried Q0.64 phase ``acc`` ((B,) int64 holding the uint64 bits, updated in place):
+    golf_harmonic_osc_stream_f32, bit for bit the one-shot's samples at the same global indices.  ``phase`` (B, >= nseg+1)
+    holds p[j0 ..]; ``amp`` (B, na, H) rows a_first .. and ``tscale`` (B, ns) rows s_first .. of their tracks, ``a_end`` /
+    ``s_end`` the tracks' row counts once they have ended (-1 before).  Returns (B, nseg*P + final_point).  Inference only;
+    fp16 / bf16 tracks are cast to fp32 first."""
+    _inference_only("harmonic_osc_stream", phase, amp, tscale, hscale)
+    phase = _rows(phase.float())
+    amp = None if amp is None else amp.float().contiguous()
+    tscale = None if tscale is None else _rows(tscale.float())
+    hscale = None if hscale is None else hscale.float().contiguous()
+    _lib.require_device(phase, amp, tscale, hscale)
+    B = phase.shape[0]
+    if not acc.is_cuda or acc.dtype != torch.int64 or acc.shape != (B,):
+        raise _lib.GolfError(f"harmonic_osc_stream: acc must be a ({B},) int64 device tensor")
+    if phase.shape[1] < int(nseg) + 1:
+        raise _lib.GolfError(f"harmonic_osc_stream: {phase.shape[1]} phase samples for {nseg} segments")
+    if amp is not None and (amp.dim() != 3 or amp.shape[0] != B or amp.shape[2] != H):
+        raise _lib.GolfError(f"harmonic_osc_stream: amplitudes {tuple(amp.shape)} for B={B}, H={H}")
+    if tscale is not None and tscale.shape[0] != B:
+        raise _lib.GolfError(f"harmonic_osc_stream: tscale {tuple(tscale.shape)} for B={B}")
+    if hscale is not None and hscale.numel() != H:
+        raise _lib.GolfError(f"harmonic_osc_stream: hscale of {hscale.numel()} values for H={H}")
+    nall = int(nseg) + int(bool(final_point))
+    out = torch.empty(B, int(nseg) * int(phase_hop) + int(bool(final_point)), dtype=torch.float32, device=phase.device)
+    ws = _workspace(8 * B * nall, phase.device) if nall else None
+    lib = _lib.load()
+    rc = lib.golf_harmonic_osc_stream_f32(phase.data_ptr(), phase.stride(0), int(nseg), int(bool(final_point)), int(phase_hop),
+                                          _lib.ptr(amp), int(a_first), 0 if amp is None else amp.shape[1], int(a_end),
+                                          int(amp_hop), _lib.ptr(tscale), 0 if tscale is None else tscale.stride(0),
+                                          int(s_first), 0 if tscale is None else tscale.shape[1], int(s_end), int(ts_hop),
+                                          _lib.ptr(hscale), int(H), int(j0), acc.data_ptr(), out.data_ptr(),
+                                          max(1, out.stride(0)), B, _lib.ptr(ws), 0 if ws is None else ws.numel(),
+                                          _lib.stream_ptr())
+    _lib.check(rc, "golf_harmonic_osc_stream_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # frame-wise all-pole synthesis as a cascade of biquads (reference models/lpc.py:94-131)
 # ------------------------------------------------------------------------------------------------

@@ -513,6 +513,28 @@ int golf_harmonic_osc_fwd_f32(const float* phase, int64_t phase_stride, int Tp, 
                               const float* hscale, int H, float* out, int64_t out_stride, int B, int Tout,
                               void* ws, size_t ws_bytes, void* stream,
                               const float* phase_offset, int Fo, int po_hop, const float* initial_phase);
+/* Streaming harmonic oscillator (additive in ABI 6): golf_harmonic_osc_fwd_f32's output samples of coarse phase segments
+ * j0 .. j0+nseg-1, i.e. samples [j0*P, (j0+nseg)*P) with P = phase_hop, from a carried phase (golf_glottal_osc_stream_f32's
+ * contract, without oversampling):
+ *   phase  (B, >= nseg+1) rows of stride phase_stride: phase[b][i] = p[b][j0+i] (p[j0+nseg] closes the last segment)
+ *   acc    (B) uint64 DEVICE words, Q0.64 cycles: on entry the exact phase before sample j0*P, on return the phase after the
+ *          block -- the one-shot scan's integer segment sums, so any split accumulates the one-shot's phase bit for bit
+ *   final_point 1: also the utterance's last sample, k = 0 of coarse sample j0+nseg (the one-shot's (Tp-1)*P)
+ *   amp    (B, na, H) contiguous, NULL for none: rows a_first .. a_first+na-1 of the amplitude track at amp_hop;
+ *   tscale (B, >= ns) rows of stride ts_stride, NULL for none: rows s_first .. s_first+ns-1 at ts_hop;
+ *          a_end / s_end: -1 while the track is open, its total row count once known (the one-shot's clamps: the last
+ *          sample interpolates segment end-2 with weight 1, a single row is held constant)
+ *   hscale (H) or NULL; H <= 4096; out (B, nseg*P + final_point) of stride out_stride
+ *   ws     scratch of 8*B*(nseg + final_point) bytes, 256-aligned
+ * Every sample has the bits of golf_harmonic_osc_fwd_f32's sample at the same global index, for any split.  Refused before any
+ * launch: windows that do not hold the rows the samples interpolate, a closed track that ends before the last sample, and
+ * (GOLF_EUNSUPPORTED) the amplitude hops the one-shot refuses for LDS staging.  No phase_offset / initial_phase.  Two launches
+ * (segment scan, render); none when nseg + final_point = 0.  No host<->device synchronisation. */
+int golf_harmonic_osc_stream_f32(const float* phase, int64_t phase_stride, int nseg, int final_point, int phase_hop,
+                                 const float* amp, int64_t a_first, int na, int64_t a_end, int amp_hop,
+                                 const float* tscale, int64_t ts_stride, int64_t s_first, int ns, int64_t s_end, int ts_hop,
+                                 const float* hscale, int H, int64_t j0, uint64_t* acc, float* out, int64_t out_stride, int B,
+                                 void* ws, size_t ws_bytes, void* stream);
 /* d out / d Phi(t) (Phi = the running phase in cycles): 2 pi sum_h [h p < 0.5] amp(t,h) h cos(2 pi h Phi(t)); the
  * gradient w.r.t. the phase input is the transposed upsampling of the reverse cumulative sum of g_out * this (host). */
 int golf_harmonic_osc_dphase_f32(const float* phase, int64_t phase_stride, int Tp, int phase_hop,

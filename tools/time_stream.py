@@ -2,7 +2,10 @@
 Needs a GPU; run under a time limit, e.g.  timeout -k 10 600 python tools/time_stream.py [--decoder golf-ff]
 
 --decoder golf-ss (default: DecoderStream), golf-ff (FramewiseDecoderStream, the frame-wise end filter) or golf-v1
-(FramewiseDecoderStream over HarmonicPlusNoiseSynth: the frame-wise filter on the oscillator, the room filter last).
+(FramewiseDecoderStream over HarmonicPlusNoiseSynth: the frame-wise filter on the oscillator, the room filter last);
+ddsp, sawsing, pulse or glottal_d (HarmonicPlusNoiseStream over the decoders of the shipped configs in
+tests/golden/g28_shipped_configs.npz, with the inputs tests/test_stream_hpn_host.py builds: DDSP at hop 240 with a per-sample
+phase, the ISMIR'23 models at hop 120 with the phase and voicing at hop 120; pushes of one hop at B=1).
 
 For B in {1, 32} and pushes of 240 and 2400 samples (every track sliced to the same stretch of time), 2 s utterances:
   push_us     mean device time of one push (CUDA events around the push, synchronised per push: the host side is included)
@@ -34,7 +37,77 @@ def make_v1(noise):
                                   harm_filter=ff.end_filter, noise_filter=ff.noise_filter, end_filter=ff.room_filter)
 
 
+HPN = ("ddsp", "sawsing", "pulse", "glottal_d")
+
+
+def _time_stream(make_stream, args, T, push, reps):
+    """Push [lo, lo + push) of every track until T, then finish(): per-push device times, total, samples out."""
+    for _ in range(reps):
+        st = make_stream()
+        times, n_out = [], 0
+        for lo in range(0, T, push):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            y = st.push(**args(lo, min(lo + push, T)))
+            e.record()
+            e.synchronize()
+            times.append(s.elapsed_time(e) * 1e3)
+            n_out += y.shape[1]
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        n_out += st.finish().shape[1]
+        e.record()
+        e.synchronize()
+        total = sum(times) + s.elapsed_time(e) * 1e3
+    return times, total, n_out
+
+
+def run_hpn(B: int, push: int, decoder: str, T: int = 48000, reps: int = 3) -> dict:
+    """HarmonicPlusNoiseStream over a shipped harmonic-plus-noise decoder, beside the one-shot decoder."""
+    import numpy as np
+
+    tests = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+    sys.path.insert(0, tests)
+    from test_stream_hpn_host import SPECS, make_hpn_inputs, shipped
+    from test_gpu_stream_hpn import _call_args, _fixed_noise
+
+    from golf_amd.stream import HarmonicPlusNoiseStream
+
+    golden = lambda name: np.load(os.path.join(tests, "golden", name + ".npz"), allow_pickle=False)
+    x = make_hpn_inputs(decoder, B, T, device="cuda")
+    dec = shipped(golden, decoder).cuda().eval()
+    dec.noise_generator = _fixed_noise(x["noise"])
+    s = SPECS[decoder]
+    hops = dict(phase=s["P"], voicing=s["P"], amp=s["hop"], wsel=s.get("wsel"))
+
+    def args(lo, hi):
+        sl = lambda v, hop: v[:, lo // hop: hi // hop]
+        part = dict(x, harm=tuple(sl(v, s["hop"]) for v in x["harm"]),
+                    noise_ctrl=tuple(sl(v, s["hop"]) for v in x["noise_ctrl"]),
+                    **{k: sl(x[k], h) for k, h in hops.items() if k in x})
+        return dict(_call_args(decoder, part), noise=AudioTensor(x["noise"][:, lo:hi]))
+
+    with torch.no_grad():
+        times, total, n_out = _time_stream(lambda: HarmonicPlusNoiseStream(dec, B), args, T, push, reps)
+        one = []
+        for _ in range(reps + 1):
+            st, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            st.record()
+            dec(noise_generator_params=(), **_call_args(decoder, x))
+            e.record()
+            e.synchronize()
+            one.append(st.elapsed_time(e) * 1e3)
+    dur = T / SR
+    oneshot = min(one[1:])
+    return dict(decoder=decoder, B=B, push=push, pushes=len(times), samples_out=n_out,
+                push_us=round(sum(times) / len(times), 1), push_us_max=round(max(times), 1),
+                stream_total_us=round(total, 1), rtf=round(total * 1e-6 / dur, 5), oneshot_us=round(oneshot, 1),
+                oneshot_rtf=round(oneshot * 1e-6 / dur, 5))
+
+
 def run(B: int, push: int, T: int = 48000, reps: int = 3, decoder: str = "golf-ss") -> dict:
+    if decoder in HPN:
+        return run_hpn(B, push, decoder, T, reps)
     inp = make_inputs(B=B, T=T, device="cuda", with_noise_filter=True)
     if decoder == "golf-v1":
         dec = make_v1(inp["noise"]).cuda()
@@ -51,25 +124,8 @@ def run(B: int, push: int, T: int = 48000, reps: int = 3, decoder: str = "golf-s
                 "noise_filter_params": (fr("log_mag", 240),), lpc_key: (fr("gain", 240), fr("a", 240)),
                 "noise": AudioTensor(inp["noise"][:, lo:hi])}
 
-    times, total, n_out = [], 0.0, 0
     with torch.no_grad():
-        for _ in range(reps):
-            st = Stream(dec, batch_size=B)
-            times, total, n_out = [], 0.0, 0
-            for lo in range(0, T, push):
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record()
-                y = st.push(**args(lo, min(lo + push, T)))
-                e.record()
-                e.synchronize()
-                times.append(s.elapsed_time(e) * 1e3)
-                n_out += y.shape[1]
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            n_out += st.finish().shape[1]
-            e.record()
-            e.synchronize()
-            total = sum(times) + s.elapsed_time(e) * 1e3
+        times, total, n_out = _time_stream(lambda: Stream(dec, batch_size=B), args, T, push, reps)
         one = []
         for _ in range(reps + 1):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -90,9 +146,10 @@ def run(B: int, push: int, T: int = 48000, reps: int = 3, decoder: str = "golf-s
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--decoder", choices=("golf-ss", "golf-ff", "golf-v1"), default="golf-ss")
+    ap.add_argument("--decoder", choices=("golf-ss", "golf-ff", "golf-v1") + HPN, default="golf-ss")
     opt = ap.parse_args()
     assert torch.cuda.is_available(), "tools/time_stream.py needs a GPU"
+    hop = 240 if opt.decoder in ("golf-ss", "golf-ff", "golf-v1", "ddsp") else 120
     for B in (1, 32):
-        for push in (240, 2400):
+        for push in sorted({hop, 240, 2400}):
             print(json.dumps(run(B, push, decoder=opt.decoder)), flush=True)
