@@ -22,7 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from golf_amd.audiotensor import AudioTensor  # noqa: E402
-from golf_amd.stream import DecoderStream, FramewiseDecoderStream  # noqa: E402
+from golf_amd.stream import DecoderStream, FramewiseDecoderStream, HarmonicPlusNoiseStream  # noqa: E402
 from golf_amd.synthetic import make_decoder, make_inputs  # noqa: E402
 
 SR = 24000
@@ -62,16 +62,14 @@ def _time_stream(make_stream, args, T, push, reps):
     return times, total, n_out
 
 
-def run_hpn(B: int, push: int, decoder: str, T: int = 48000, reps: int = 3) -> dict:
-    """HarmonicPlusNoiseStream over a shipped harmonic-plus-noise decoder, beside the one-shot decoder."""
+def _hpn_case(B: int, T: int, decoder: str):
+    """(stream factory, push arguments of [lo, hi), one-shot call) over a shipped harmonic-plus-noise decoder."""
     import numpy as np
 
     tests = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
     sys.path.insert(0, tests)
     from test_stream_hpn_host import SPECS, make_hpn_inputs, shipped
     from test_gpu_stream_hpn import _call_args, _fixed_noise
-
-    from golf_amd.stream import HarmonicPlusNoiseStream
 
     golden = lambda name: np.load(os.path.join(tests, "golden", name + ".npz"), allow_pickle=False)
     x = make_hpn_inputs(decoder, B, T, device="cuda")
@@ -87,27 +85,11 @@ def run_hpn(B: int, push: int, decoder: str, T: int = 48000, reps: int = 3) -> d
                     **{k: sl(x[k], h) for k, h in hops.items() if k in x})
         return dict(_call_args(decoder, part), noise=AudioTensor(x["noise"][:, lo:hi]))
 
-    with torch.no_grad():
-        times, total, n_out = _time_stream(lambda: HarmonicPlusNoiseStream(dec, B), args, T, push, reps)
-        one = []
-        for _ in range(reps + 1):
-            st, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            st.record()
-            dec(noise_generator_params=(), **_call_args(decoder, x))
-            e.record()
-            e.synchronize()
-            one.append(st.elapsed_time(e) * 1e3)
-    dur = T / SR
-    oneshot = min(one[1:])
-    return dict(decoder=decoder, B=B, push=push, pushes=len(times), samples_out=n_out,
-                push_us=round(sum(times) / len(times), 1), push_us_max=round(max(times), 1),
-                stream_total_us=round(total, 1), rtf=round(total * 1e-6 / dur, 5), oneshot_us=round(oneshot, 1),
-                oneshot_rtf=round(oneshot * 1e-6 / dur, 5))
+    return (lambda: HarmonicPlusNoiseStream(dec, B)), args, (lambda: dec(noise_generator_params=(), **_call_args(decoder, x)))
 
 
-def run(B: int, push: int, T: int = 48000, reps: int = 3, decoder: str = "golf-ss") -> dict:
-    if decoder in HPN:
-        return run_hpn(B, push, decoder, T, reps)
+def _golf_case(B: int, T: int, decoder: str):
+    """The same for golf-ss, golf-ff and golf-v1 over make_decoder's modules."""
     inp = make_inputs(B=B, T=T, device="cuda", with_noise_filter=True)
     if decoder == "golf-v1":
         dec = make_v1(inp["noise"]).cuda()
@@ -124,23 +106,30 @@ def run(B: int, push: int, T: int = 48000, reps: int = 3, decoder: str = "golf-s
                 "noise_filter_params": (fr("log_mag", 240),), lpc_key: (fr("gain", 240), fr("a", 240)),
                 "noise": AudioTensor(inp["noise"][:, lo:hi])}
 
+    full = lambda k, hop: AudioTensor(inp[k], hop)
+    one_shot = lambda: dec(phase=AudioTensor(inp["phase"]), harm_oscillator_params=(full("wsel", w_hop),),
+                           noise_generator_params=(), noise_filter_params=(full("log_mag", 240),),
+                           **{lpc_key: (full("gain", 240), full("a", 240))})
+    return (lambda: Stream(dec, batch_size=B)), args, one_shot
+
+
+def run(B: int, push: int, T: int = 48000, reps: int = 3, decoder: str = "golf-ss") -> dict:
+    make_stream, args, one_shot = (_hpn_case if decoder in HPN else _golf_case)(B, T, decoder)
     with torch.no_grad():
-        times, total, n_out = _time_stream(lambda: Stream(dec, batch_size=B), args, T, push, reps)
+        times, total, n_out = _time_stream(make_stream, args, T, push, reps)
         one = []
         for _ in range(reps + 1):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
-            dec(phase=AudioTensor(inp["phase"]), harm_oscillator_params=(AudioTensor(inp["wsel"], w_hop),),
-                noise_generator_params=(), noise_filter_params=(AudioTensor(inp["log_mag"], 240),),
-                **{lpc_key: (AudioTensor(inp["gain"], 240), AudioTensor(inp["a"], 240))})
+            one_shot()
             e.record()
             e.synchronize()
             one.append(s.elapsed_time(e) * 1e3)
     dur = T / SR
     oneshot = min(one[1:])
     out = dict(B=B, push=push, pushes=len(times), samples_out=n_out, push_us=round(sum(times) / len(times), 1),
-                push_us_max=round(max(times), 1), stream_total_us=round(total, 1), rtf=round(total * 1e-6 / dur, 5),
-                oneshot_us=round(oneshot, 1), oneshot_rtf=round(oneshot * 1e-6 / dur, 5))
+               push_us_max=round(max(times), 1), stream_total_us=round(total, 1), rtf=round(total * 1e-6 / dur, 5),
+               oneshot_us=round(oneshot, 1), oneshot_rtf=round(oneshot * 1e-6 / dur, 5))
     return out if decoder == "golf-ss" else dict(decoder=decoder, **out)
 
 
