@@ -18,7 +18,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_ff.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip")
+SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_ff.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
+           "stft_filter.hip")
 
 _c_f32p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -50,6 +51,10 @@ SIGNATURES = {
     "golf_lti_frames_ola_stream_f32": (_int, [_c_f32p, _i64, _i64, _int, _i64, _c_f32p, _i64, _int, _i64, _c_f32p, _i64, _int,
                                               _c_f32p, _i64, _int, _c_f32p, _i64, _i64, _int] + [_int] * 4
                                        + [_c_f32p, _vp, _sz, _vp]),
+    "golf_stft_filter_stream_state_bytes": (_sz, [_int] * 3),
+    "golf_stft_filter_frames_stream_f32": (_int, [_c_f32p, _i64, _i64, _int, _i64, _c_f32p, _i64, _int, _int, _i64, _c_f32p,
+                                                  _i64, _int, _c_f32p, _i64, _i64, _int, _int, _int, _int, _c_f32p, _vp, _sz,
+                                                  _vp]),
     "golf_lti_frames_bwd_workspace_bytes": (_sz, [_int] * 6),
     "golf_lti_frames_ola_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64, _int,
                                            _c_f32p, _c_f32p] + [_int] * 7 + [_vp, _vp, _sz, _vp]),

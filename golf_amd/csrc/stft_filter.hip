@@ -1,0 +1,374 @@
+// STFT-domain frame filter, block by block: the arithmetic of LTVCepFilter (NHV) and DiffWorldSPFilter (WORLD) --
+// torch.stft(center, reflect) -> multiply by a per-frame response -> torch.istft -- one frame at a time, with the frames an
+// unfinished output sample can still need carried between calls.
+//
+//   frame f   covers input samples [f*hop - n/2, f*hop + n/2); an index i < 0 reads x[-i], and once the utterance has ended
+//             (x_end = T) an index i >= T reads x[2(T-1) - i]
+//   u_f     = Re IFFT(FFT(w * frame_f) * H_f),  H_f given on bins 0 .. n/2 and extended by Hermitian symmetry
+//   y[m]    = sum_f w[k] u_f[k] / sum_f w[k]^2,  k = m + n/2 - f*hop, over the frames 0 <= f < frames that cover m
+//
+// Two launches, the layout of golf_lti_frames_ola_stream_f32 (lpc_ff.hip):
+//   frames   the new frames into ws[b][S + f - f0], plus (extra blocks) the carried frames [f0 - S, f0) ring -> ws[b][0 .. S)
+//   OLA      the output samples from ws alone, frames in ascending f with fmaf (the synthesis window is applied here, so a
+//            frame is rounded once), plus (extra blocks) the last min(S, nf) new frames ws -> ring
+// Neither launch reads what the same launch writes.  A frame is transformed by one group of n/4 lanes from its own samples
+// and its own response row, so its bits -- and with the fixed summation order every output sample -- do not depend on how
+// the input is split into calls.
+//
+// The transform: a Stockham radix-4 FFT in LDS (one radix-2 stage last when log2 n is odd), n/4 lanes per frame, one
+// butterfly per lane and stage, so n = 1024 runs 5 stages instead of radix-2's 10 and every stage costs two barriers.  Frames
+// of n <= 128 share a 64-lane block (4 or 2 frames per wave); n >= 256 takes one block of n/4 lanes per frame.  LDS holds the
+// frame as separate re / im arrays (b32 accesses bank on (a/4) % 32 over 32-lane groups): a stage reads elements
+// j + r*n/4 -- consecutive lanes, consecutive banks -- and writes base(j) + r*Ns.  Unpadded, the writes of the stages with
+// Ns = 1 and Ns = 4 would land on 8 banks (4-way); element i is therefore stored at i + 4*(i >> 5), which makes the Ns = 4
+// stage conflict-free, and the Ns = 1 stage writes its four consecutive elements as one 16-byte store.  Ns = 16 stays 2-way,
+// Ns >= 64 is conflict-free.  n = 1024: 2 * 1152 floats for the frame + 2 * 1024 for the twiddles = 17 KB per block.
+// Twiddles: exp(-2 pi i t / n) for t < n, formed once per block with sincospif (its argument 2t/n is exact) and kept in LDS;
+// no fast-math sine or cosine.
+#include <algorithm>
+#include <climits>
+
+#include "common.h"
+
+namespace golf {
+
+struct StftArgs {
+    const float* x;      // window of the input: samples x0 .. x0+nx-1, row stride x_stride
+    int64_t x_stride;
+    int xl;              // -x0: window index below which a sample is reflected about global sample 0
+    int xe;              // x_end - x0: window index from which a sample is reflected about x_end - 1 (INT_MAX/2 while open)
+    int xb;              // window index of frame f0's position 0: f0*hop - n/2 - x0
+    const float* h;      // response rows h0 .. h0+nh-1: (B, nh, n/2+1) real or (B, nh, n/2+1, 2) interleaved complex
+    int nh, hr, h_kind;  // hr = f0 - h0
+    const float* window;
+    int nf, S, hop, n, lg, fpb;   // lg = log2 n; fpb: frames per block
+    const float* carry;
+    int ncin, cin_slot;  // carried frames copied into ws[b][S - ncin ..): ring slots cin_slot, cin_slot + 1, .. (mod S)
+    float* ws;           // (B, S + nf, n)
+};
+
+__device__ __forceinline__ int stft_pad(int i) { return i + ((i >> 5) << 2); }
+
+// One radix-4 stage (sub-transforms of length Ns = 1 << ls done) of the lane's frame, in place: read, barrier, write, barrier.
+template <bool INV>
+__device__ __forceinline__ void stft_radix4(float* re, float* im, const float* twc, const float* tws, int j, int q, int ls,
+                                            int lg) {
+    const int Ns = 1 << ls;
+    const int k = j & (Ns - 1);
+    const int t1 = k << (lg - ls - 2);
+    float vr[4], vi[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = stft_pad(j + r * q);
+        vr[r] = re[i];
+        vi[r] = im[i];
+    }
+#pragma unroll
+    for (int r = 1; r < 4; ++r) {
+        const float c = twc[r * t1], s = INV ? -tws[r * t1] : tws[r * t1];
+        const float a = vr[r], b = vi[r];
+        vr[r] = fmaf(a, c, -b * s);
+        vi[r] = fmaf(a, s, b * c);
+    }
+    const float a0r = vr[0] + vr[2], a0i = vi[0] + vi[2], a1r = vr[0] - vr[2], a1i = vi[0] - vi[2];
+    const float a2r = vr[1] + vr[3], a2i = vi[1] + vi[3], a3r = vr[1] - vr[3], a3i = vi[1] - vi[3];
+    // forward: bin 1 = a1 - i a3, bin 3 = a1 + i a3; the inverse swaps them
+    const float rr = INV ? -a3i : a3i, ri = INV ? a3r : -a3r;
+    float orr[4] = {a0r + a2r, a1r + rr, a0r - a2r, a1r - rr};
+    float oi[4] = {a0i + a2i, a1i + ri, a0i - a2i, a1i - ri};
+    __syncthreads();
+    const int base = ((j >> ls) << (ls + 2)) + k;
+    if (ls == 0) {   // four consecutive elements (stft_pad keeps groups of 4 together, 16-byte aligned)
+        const int i = stft_pad(base);
+        *reinterpret_cast<float4*>(re + i) = make_float4(orr[0], orr[1], orr[2], orr[3]);
+        *reinterpret_cast<float4*>(im + i) = make_float4(oi[0], oi[1], oi[2], oi[3]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = stft_pad(base + r * Ns);
+            re[i] = orr[r];
+            im[i] = oi[r];
+        }
+    }
+    __syncthreads();
+}
+
+// The last stage when log2 n is odd: radix 2 over Ns = n/2; a lane takes the butterflies j and j + n/4.
+template <bool INV>
+__device__ __forceinline__ void stft_radix2_last(float* re, float* im, const float* twc, const float* tws, int j, int q) {
+    float ar[2], ai[2], br[2], bi[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int k = j + u * q;
+        const int i0 = stft_pad(k), i1 = stft_pad(k + 2 * q);
+        const float c = twc[k], s = INV ? -tws[k] : tws[k];
+        const float a = re[i1], b = im[i1];
+        ar[u] = re[i0];
+        ai[u] = im[i0];
+        br[u] = fmaf(a, c, -b * s);
+        bi[u] = fmaf(a, s, b * c);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int k = j + u * q;
+        const int i0 = stft_pad(k), i1 = stft_pad(k + 2 * q);
+        re[i0] = ar[u] + br[u];
+        im[i0] = ai[u] + bi[u];
+        re[i1] = ar[u] - br[u];
+        im[i1] = ai[u] - bi[u];
+    }
+    __syncthreads();
+}
+
+template <bool INV>
+__device__ __forceinline__ void stft_fft(float* re, float* im, const float* twc, const float* tws, int j, int q, int lg) {
+    int ls = 0;
+    for (; ls + 2 <= lg; ls += 2) stft_radix4<INV>(re, im, twc, tws, j, q, ls, lg);
+    if (ls < lg) stft_radix2_last<INV>(re, im, twc, tws, j, q);
+}
+
+// grid (ceil(nf / fpb) + ncin, B), fpb * n/4 threads, dynamic LDS = 2 n (twiddles) + fpb * 2 * (n + n/8) floats.
+__global__ __launch_bounds__(512) void stft_frames_kernel(StftArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int n = p.n, q = n >> 2, lg = p.lg;
+    const int b = blockIdx.y;
+    const int nblk = (p.nf + p.fpb - 1) / p.fpb;
+    if ((int)blockIdx.x >= nblk) {
+        const int jc = blockIdx.x - nblk;
+        const float* src = p.carry + ((size_t)b * p.S + (p.cin_slot + jc) % p.S) * n;
+        float* dst = p.ws + ((size_t)b * (p.S + p.nf) + p.S - p.ncin + jc) * n;
+        for (int k = threadIdx.x; k < n; k += blockDim.x) dst[k] = src[k];
+        return;
+    }
+    const int P = n + (n >> 3);
+    float* twc = lds;
+    float* tws = lds + n;
+    const int g = threadIdx.x >> (lg - 2), j = threadIdx.x & (q - 1);
+    float* re = lds + 2 * n + (size_t)g * 2 * P;
+    float* im = re + P;
+    const int fl = blockIdx.x * p.fpb + g;   // frame f0 + fl
+    const bool mine = fl < p.nf;
+    const int flc = mine ? fl : p.nf - 1;    // (a group past the last frame repeats it and writes nothing)
+    {
+        const float step = -2.0f / (float)n;   // exact: n is a power of two
+        for (int t = threadIdx.x; t < n; t += blockDim.x) {
+            float s, c;
+            sincospif((float)t * step, &s, &c);
+            twc[t] = c;
+            tws[t] = s;
+        }
+    }
+    {
+        const float* xrow = p.x + (size_t)b * p.x_stride;
+        const int sb = p.xb + flc * p.hop;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = j + u * q;
+            int r = sb + k;
+            if (r < p.xl) r = 2 * p.xl - r;
+            if (r >= p.xe) r = 2 * (p.xe - 1) - r;
+            re[stft_pad(k)] = xrow[r] * p.window[k];
+            im[stft_pad(k)] = 0.f;
+        }
+    }
+    __syncthreads();
+    stft_fft<false>(re, im, twc, tws, j, q, lg);
+    {
+        // bins j + u*n/4 are the ones this lane reads in the inverse's first stage: no barrier in between
+        const int nb = (n >> 1) + 1;
+        const float* hrow = p.h + ((size_t)b * p.nh + p.hr + flc) * nb * (p.h_kind ? 2 : 1);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = j + u * q;
+            const int kk = k <= (n >> 1) ? k : n - k;
+            float hre, him = 0.f;
+            if (p.h_kind) {
+                const float2 hv = *reinterpret_cast<const float2*>(hrow + 2 * kk);
+                hre = hv.x;
+                him = k <= (n >> 1) ? hv.y : -hv.y;
+            } else {
+                hre = hrow[kk];
+            }
+            const int i = stft_pad(k);
+            const float a = re[i], c = im[i];
+            re[i] = fmaf(a, hre, -c * him);
+            im[i] = fmaf(a, him, c * hre);
+        }
+    }
+    stft_fft<true>(re, im, twc, tws, j, q, lg);
+    if (mine) {
+        float* orow = p.ws + ((size_t)b * (p.S + p.nf) + p.S + fl) * n;
+        const float inv_n = 1.0f / (float)n;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = j + u * q;
+            orow[k] = re[stft_pad(k)] * inv_n;
+        }
+    }
+}
+
+// Output samples n0 + i, i < ny, from the frames at ws slot f - (f0 - S); extra blocks copy the last ncout new frames into the
+// carried ring.  m = mb + i: the sample's position relative to ws slot 0 (sample + n/2 - (f0 - S)*hop); slots [fmin, fmax]
+// hold frames that exist.
+__global__ __launch_bounds__(256) void stft_ola_kernel(const float* __restrict__ ws, const float* __restrict__ window,
+                                                       float* __restrict__ y, int64_t y_stride, float* __restrict__ carry,
+                                                       int ny, int mb, int fmin, int fmax, int nslot, int hop, int n, int S,
+                                                       int ncout, int cout_slot) {
+    const int b = blockIdx.y;
+    const int nob = (ny + 255) / 256;
+    if ((int)blockIdx.x >= nob) {
+        const int jc = blockIdx.x - nob;
+        const float* src = ws + ((size_t)b * nslot + nslot - ncout + jc) * n;
+        float* dst = carry + ((size_t)b * S + (cout_slot + jc) % S) * n;
+        for (int k = threadIdx.x; k < n; k += 256) dst[k] = src[k];
+        return;
+    }
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ny) return;
+    const int m = mb + i;
+    int fhi = m / hop;
+    if (fhi > fmax) fhi = fmax;
+    int flo = m - n + 1 <= 0 ? 0 : (m - n + hop) / hop;
+    if (flo < fmin) flo = fmin;
+    const float* wf = ws + (size_t)b * nslot * n;
+    float acc = 0.f, norm = 0.f;
+    for (int f = flo; f <= fhi; ++f) {
+        const int k = m - f * hop;
+        const float wk = window[k];
+        acc = fmaf(wk, wf[(size_t)f * n + k], acc);
+        norm = fmaf(wk, wk, norm);
+    }
+    y[(size_t)b * y_stride + i] = acc / norm;
+}
+
+static int stft_log2(int n) {   // log2 n for a power of two in [64, 2048], else 0
+    for (int lg = 6; lg <= 11; ++lg)
+        if (n == (1 << lg)) return lg;
+    return 0;
+}
+
+static int stft_S(int n, int hop) { return (n + hop - 1) / hop - 1; }
+
+}  // namespace golf
+
+using namespace golf;
+
+extern "C" size_t golf_stft_filter_stream_state_bytes(int B, int n_fft, int hop) {
+    if (B < 1 || hop < 1 || !stft_log2(n_fft) || n_fft < 2 * hop) return 0;
+    return sizeof(float) * (size_t)B * stft_S(n_fft, hop) * n_fft;
+}
+
+extern "C" int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stride, int64_t x0, int nx, int64_t x_end,
+                                                  const float* h, int64_t h0, int nh, int h_kind, int64_t frames_end,
+                                                  const float* window, int64_t f0, int nf, float* y, int64_t y_stride,
+                                                  int64_t n0, int ny, int B, int n_fft, int hop, float* carry, void* ws,
+                                                  size_t ws_bytes, void* stream) {
+    if (B < 1 || hop < 1 || n_fft < 1 || nf < 0 || ny < 0 || nx < 0 || nh < 0 || x0 < 0 || h0 < 0 || f0 < 0 || n0 < 0 ||
+        (h_kind != 0 && h_kind != 1))
+        return fail(GOLF_EINVAL, "stft_filter_stream: bad size, kind or negative start");
+    const int lg = stft_log2(n_fft);
+    if (!lg) return fail(GOLF_EUNSUPPORTED, "stft_filter_stream: n_fft %d is not a power of two in [64, 2048]", n_fft);
+    if (n_fft < 2 * hop) return fail(GOLF_EINVAL, "stft_filter_stream: n_fft %d < 2*hop %d", n_fft, 2 * hop);
+    if (!window || !carry || (nf > 0 && (!x || !h)) || ((nf > 0 || ny > 0) && !ws) || (ny > 0 && !y))
+        return fail(GOLF_EINVAL, "stft_filter_stream: null pointer");
+    if ((x_end < 0) != (frames_end < 0))
+        return fail(GOLF_EINVAL, "stft_filter_stream: x_end and frames_end are both open (< 0) or both set");
+    const bool fin = x_end >= 0;
+    const int64_t W = n_fft, pad = n_fft / 2, H = hop;
+    const int S = stft_S(n_fft, hop);
+    int64_t nfr = INT64_MAX, Ty = INT64_MAX;
+    if (fin) {
+        if (x_end <= pad) return fail(GOLF_EINVAL, "stft_filter_stream: x_end %lld cannot be reflect-padded by n_fft/2 = %lld",
+                                      (long long)x_end, (long long)pad);
+        if (frames_end < 1 || frames_end > 1 + x_end / H)
+            return fail(GOLF_EINVAL, "stft_filter_stream: frames_end %lld outside [1, 1 + x_end/hop = %lld]",
+                        (long long)frames_end, (long long)(1 + x_end / H));
+        nfr = frames_end;
+        Ty = (nfr - 1) * H;
+        if (f0 + nf > nfr) return fail(GOLF_EINVAL, "stft_filter_stream: frames past the last one (%lld)", (long long)nfr);
+        if (n0 + ny > Ty) return fail(GOLF_EINVAL, "stft_filter_stream: samples past the end (%lld)", (long long)Ty);
+    }
+    if ((nf > 0 && nx > 0 && x_stride < nx) || (ny > 0 && y_stride < ny))
+        return fail(GOLF_EINVAL, "stft_filter_stream: row stride too small");
+    if ((int64_t)(S + nf) * W >= (1ll << 29) || nx >= (1 << 29) || (int64_t)(S + nf + 1) * H >= (1ll << 29) ||
+        (int64_t)nh * (pad + 1) >= (1ll << 29))
+        return fail(GOLF_EUNSUPPORTED, "stft_filter_stream: call too large (%d frames, %d samples)", nf, nx);
+    // frames [f0, f0+nf): their response rows and the samples they read, reflections included
+    if (nf > 0) {
+        if (f0 < h0 || f0 + nf > h0 + nh)
+            return fail(GOLF_EINVAL, "stft_filter_stream: the response window does not cover the frames");
+        const int64_t s0 = f0 * H - pad, e1 = (f0 + nf - 1) * H + pad;   // first frame's start, last frame's end (exclusive)
+        int64_t lo = std::max<int64_t>(0, s0), hi = e1 - 1;
+        if (s0 < 0) hi = std::max(hi, -s0);                              // x[-i]
+        if (fin && e1 > x_end) {                                         // x[2(T-1) - i], i up to e1 - 1
+            lo = std::min(lo, 2 * (x_end - 1) - (e1 - 1));
+            hi = std::min(hi, x_end - 1);
+            if (s0 < 0) hi = std::max(hi, std::min(-s0, x_end - 1));
+        }
+        if (x0 > lo || x0 + nx <= hi)
+            return fail(GOLF_EINVAL, "stft_filter_stream: the input window does not cover samples [%lld, %lld]",
+                        (long long)lo, (long long)hi);
+    }
+    // samples [n0, n0+ny): every frame they need is filtered by now, and the carried ring still holds the earliest one
+    auto flo = [&](int64_t m) { const int64_t d = m + pad - W + 1; return d <= 0 ? (int64_t)0 : (d + H - 1) / H; };
+    const int64_t fdone = f0 + nf;
+    if (ny > 0) {
+        const int64_t fhi = std::min((n0 + ny - 1 + pad) / H, nfr - 1);
+        if (fhi >= fdone) return fail(GOLF_EINVAL, "stft_filter_stream: sample %lld needs frame %lld, not filtered yet",
+                                      (long long)(n0 + ny - 1), (long long)fhi);
+        if (flo(n0) < f0 - S) return fail(GOLF_EINVAL, "stft_filter_stream: sample %lld needs frame %lld; the carry holds "
+                                          "frames from %lld", (long long)n0, (long long)flo(n0), (long long)(f0 - S));
+    }
+    if (nf > 0 && n0 > std::max<int64_t>(0, f0 * H - pad))
+        return fail(GOLF_EINVAL, "stft_filter_stream: samples before %lld were written without frame %lld", (long long)n0,
+                    (long long)f0);
+    if (!(fin && n0 + ny == Ty) && flo(n0 + ny) < fdone - S)
+        return fail(GOLF_EINVAL, "stft_filter_stream: write the samples up to %lld before filtering frame %lld (the carry "
+                    "holds %d frames)", (long long)((fdone - S) * H - pad + W - 1), (long long)(fdone - 1), S);
+    const size_t need = sizeof(float) * (size_t)B * (S + nf) * W;
+    if ((nf > 0 || ny > 0) && (ws_bytes < need || ((uintptr_t)ws & 255)))
+        return fail(GOLF_EWORKSPACE, "stft_filter_stream: workspace needs %zu bytes, 256-aligned (got %zu)", need, ws_bytes);
+    if (nf == 0 && ny == 0) return GOLF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int lim = 1 << 30;
+    StftArgs p;
+    p.x = x;
+    p.x_stride = x_stride;
+    p.xl = (int)std::max<int64_t>(-x0, -lim);
+    p.xe = fin ? (int)std::min<int64_t>(x_end - x0, lim) : lim;
+    p.xb = (int)std::max<int64_t>(std::min<int64_t>(f0 * H - pad - x0, lim), -lim);
+    p.h = h;
+    p.nh = nh;
+    p.hr = (int)(nf > 0 ? f0 - h0 : 0);
+    p.h_kind = h_kind;
+    p.window = window;
+    p.nf = nf;
+    p.S = S;
+    p.hop = hop;
+    p.n = n_fft;
+    p.lg = lg;
+    p.fpb = n_fft >= 256 ? 1 : 256 / n_fft;   // 64-lane blocks at least
+    p.carry = carry;
+    p.ncin = ny > 0 ? (int)std::min<int64_t>(S, f0) : 0;
+    p.cin_slot = p.ncin ? (int)((f0 - p.ncin) % S) : 0;
+    p.ws = (float*)ws;
+    if (nf > 0 || p.ncin > 0) {
+        const int threads = p.fpb * (n_fft / 4);
+        const size_t ldsb = sizeof(float) * (2 * (size_t)n_fft + (size_t)p.fpb * 2 * (n_fft + n_fft / 8));
+        hipLaunchKernelGGL(stft_frames_kernel, dim3((unsigned)(ceil_div(nf, p.fpb) + p.ncin), B), dim3(threads), ldsb, st, p);
+        GOLF_LAUNCH_CHECK();
+    }
+    const int ncout = (int)std::min<int64_t>(S, nf);
+    if (ny > 0 || ncout > 0) {
+        const int64_t fbase = f0 - S;
+        const int mb = (int)(n0 + pad - fbase * H);
+        const int fmin = (int)std::max<int64_t>(0, -fbase);
+        const int fmax = (int)(std::min<int64_t>(fdone, nfr) - 1 - fbase);
+        hipLaunchKernelGGL(stft_ola_kernel, dim3((unsigned)(ceil_div(ny, 256) + ncout), B), dim3(256), 0, st,
+                           (const float*)ws, window, y, y_stride, carry, ny, mb, fmin, fmax, S + nf, hop, n_fft, S, ncout,
+                           ncout ? (int)((fdone - ncout) % S) : 0);
+        GOLF_LAUNCH_CHECK();
+    }
+    return GOLF_OK;
+}

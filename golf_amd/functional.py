@@ -457,6 +457,61 @@ def lti_frames_ola_stream(ex, gain, a, window, hop: int, carry=None, *, x0: int,
     return y, carry
 
 
+def stft_filter_stream_carry(B: int, n_fft: int, hop: int, device) -> torch.Tensor:
+    """The zeroed (B, ceil(n_fft/hop) - 1, n_fft) fp32 carry of ``stft_filter_stream``: the last filtered frames."""
+    nbytes = _lib.load().golf_stft_filter_stream_state_bytes(int(B), int(n_fft), int(hop))
+    if nbytes == 0:
+        raise _lib.GolfError(f"stft_filter_stream: no carry for B={B}, n_fft={n_fft}, hop={hop} (n_fft a power of two in "
+                             "[64, 2048], n_fft >= 2*hop)")
+    return torch.zeros(int(B), nbytes // (4 * int(B) * int(n_fft)), int(n_fft), dtype=torch.float32, device=device)
+
+
+def stft_filter_stream(x, H, window, hop: int, carry=None, *, x0: int, h0: int, f0: int, nf: int, n0: int, ny: int,
+                       x_end: int = -1, frames_end: int = -1):
+    """One call of the STFT-domain frame filter run block by block (golf_stft_filter_frames_stream_f32), global indices
+    throughout: filters frames [f0, f0+nf) and returns output samples [n0, n0+ny) as a (B, ny) fp32 tensor, together with
+    the carry (allocated when ``carry`` is None: pass None to the first call and the returned one to every later call).
+    ``x`` (B, nx) holds samples x0 ..; ``H`` (B, nh, n_fft/2+1), real or complex, holds the response rows h0 .. on bins
+    0 .. n_fft/2; ``x_end`` / ``frames_end``: the utterance's length and frame count once it has ended (-1 before).
+    Inference only; fp16 / bf16 tracks are cast to fp32 first."""
+    _inference_only("stft_filter_stream", x, H)
+    x, window = _rows(x.float()), window.float().contiguous()
+    cplx = H.is_complex()
+    Hf = torch.view_as_real(H.to(torch.complex64).contiguous()) if cplx else H.float().contiguous()
+    _lib.require_device(x, Hf, window)
+    B, nx = x.shape
+    n = window.numel()
+    if H.ndim != 3 or H.shape[0] != B or H.shape[2] != n // 2 + 1:
+        raise _lib.GolfError(f"stft_filter_stream: x {tuple(x.shape)}, H {tuple(H.shape)}, n_fft {n}")
+    if carry is None:
+        carry = stft_filter_stream_carry(B, n, hop, x.device)
+    if not carry.is_cuda or carry.dtype != torch.float32 or not carry.is_contiguous() or carry.shape[0] != B:
+        raise _lib.GolfError(f"stft_filter_stream: carry {tuple(carry.shape)} {carry.dtype} (from stft_filter_stream_carry)")
+    y = torch.empty(B, int(ny), dtype=torch.float32, device=x.device)
+    S = carry.shape[1]
+    ws = _workspace(4 * B * (S + int(nf)) * n, x.device) if nf > 0 or ny > 0 else None
+    lib = _lib.load()
+    rc = lib.golf_stft_filter_frames_stream_f32(x.data_ptr(), x.stride(0), int(x0), nx, int(x_end), Hf.data_ptr(), int(h0),
+                                                H.shape[1], int(cplx), int(frames_end), window.data_ptr(), int(f0), int(nf),
+                                                y.data_ptr(), y.stride(0), int(n0), int(ny), B, n, int(hop),
+                                                carry.data_ptr(), _lib.ptr(ws), 0 if ws is None else ws.numel(),
+                                                _lib.stream_ptr())
+    _lib.check(rc, "golf_stft_filter_frames_stream_f32")
+    return y, carry
+
+
+def stft_filter_frames(x, H, window, hop: int) -> torch.Tensor:
+    """The whole utterance through ``stft_filter_stream`` in a single call with the end markers set: ``x`` (B, T), ``H``
+    (B, F, n_fft/2+1) -> (B, hop*(frames-1)), frames = min(1 + T//hop, F).  What LTVCepFilter / DiffWorldSPFilter compute with
+    torch.stft / torch.istft; the tests compare the kernel against them through this."""
+    T, F, n = x.shape[1], H.shape[1], window.numel()
+    if T <= n // 2:
+        raise _lib.GolfError(f"stft_filter_frames: {T} samples cannot be reflect-padded by n_fft/2 = {n // 2}")
+    frames = min(1 + T // int(hop), F)
+    return stft_filter_stream(x, H, window, hop, None, x0=0, h0=0, f0=0, nf=frames, n0=0, ny=int(hop) * (frames - 1),
+                              x_end=T, frames_end=frames)[0]
+
+
 # ------------------------------------------------------------------------------------------------
 # control transform of the LPC filters: logits -> direct-form coefficients (reference models/utils.py:581-593)
 # ------------------------------------------------------------------------------------------------

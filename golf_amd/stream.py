@@ -16,21 +16,28 @@ The streams are built from one set of stages.  A stage owns its tracks and what 
                     frames still to come: golf_ltv_fir_frames_fwd_f32 over a window that starts ceil(P/hop) frames early,
                     those frames dropped) or the frame-wise LPC filter (its last ceil(W/hop) - 1 filtered frames:
                     golf_lti_frames_ola_stream_f32, every frame filtered once, as soon as its samples and controls are there)
+                    or an STFT-domain filter, LTVCepFilter / DiffWorldSPFilter (its last ceil(n_fft/hop) - 1 filtered frames,
+                    its input from one sample before the next frame's start, the response rows of the frames still to come,
+                    formed by the module's own code as the controls arrive: golf_stft_filter_frames_stream_f32)
   _AllPoleStage     the sample-wise all-pole end filter: the last M outputs (golf_ltv_allpole_fwd_state_f32)
   _Room             the LTI room filter: its last ``lead`` input samples (golf_lti_fir_f32 over an overlap window)
 All of it is device memory; ``push`` reads nothing back from the device.  The bookkeeping is host integers derived from the
 pushed lengths alone, composed from one set of primitives (source open / length / lookahead, branch open / final / lookahead).
 
-Two wirings put the stages together, and three public classes check what they accept, parse ``push`` and pick a wiring:
+Two wirings put the stages together, and four public classes check what they accept, parse ``push`` and pick a wiring:
   _Series     source + filtered noise -> end filter -> room filter.  ``DecoderStream`` (golf-ss: the all-pole end filter, whole
               LPC hops emitted) and ``FramewiseDecoderStream`` on golf-ff (a frame-wise branch on the running sum).
               Bookkeeping: ``emit_count`` / ``final_lengths`` / ``stream_latency`` over ``StreamGeometry``.
+              ``SpectralDecoderStream`` (WORLD: a harmonic source, the STFT-domain end filter as a branch on the running
+              sum).  Bookkeeping: ``spectral_emit_count`` / ``spectral_final_lengths`` / ``spectral_stream_latency`` over
+              ``SpectralGeometry``.
   _Parallel   a branch on the source + a branch on the noise, summed over the shorter one -> room filter.
-              ``HarmonicPlusNoiseStream`` (DDSP, the ISMIR'23 ddsp / sawsing / pulse / glottal_d vocoders, golf-v1) and
-              ``FramewiseDecoderStream`` on golf-v1.  Bookkeeping: ``hpn_emit_count`` / ``hpn_final_lengths`` /
-              ``hpn_stream_latency`` over ``HPNGeometry``.
-``open_stream`` returns ``FramewiseDecoderStream`` or ``DecoderStream``, whichever fits a decoder; ``HarmonicPlusNoiseStream`` is
-opened explicitly.
+              ``HarmonicPlusNoiseStream`` (DDSP, the ISMIR'23 ddsp / sawsing / pulse / glottal_d vocoders, golf-v1, and NHV:
+              the STFT-domain filter as the harmonic branch) and ``FramewiseDecoderStream`` on golf-v1.  Bookkeeping:
+              ``hpn_emit_count`` / ``hpn_final_lengths`` / ``hpn_stream_latency`` over ``HPNGeometry``.
+``open_stream`` returns whichever class fits a decoder: ``SpectralDecoderStream`` or ``HarmonicPlusNoiseStream`` for a decoder
+with an STFT-domain filter (WORLD, NHV), else ``FramewiseDecoderStream`` or ``DecoderStream``; ``HarmonicPlusNoiseStream`` is
+opened explicitly for the other harmonic-plus-noise decoders.
 """
 from __future__ import annotations
 
@@ -46,19 +53,20 @@ from . import functional as GF
 from .audiotensor import AudioTensor
 
 __all__ = ["BranchGeometry", "DecoderStream", "FramewiseDecoderStream", "HPNGeometry", "HarmonicPlusNoiseStream",
-           "StreamGeometry", "emit_count", "final_lengths", "hpn_emit_count", "hpn_final_lengths", "hpn_stream_latency",
-           "open_stream", "stream_latency"]
+           "SpectralDecoderStream", "SpectralGeometry", "StreamGeometry", "emit_count", "final_lengths", "hpn_emit_count",
+           "hpn_final_lengths", "hpn_stream_latency", "open_stream", "spectral_emit_count", "spectral_final_lengths",
+           "spectral_stream_latency", "stream_latency"]
 
 
 # ---- geometries ------------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class BranchGeometry:
     """One filter stage on a track: a branch of a harmonic-plus-noise decoder, or a noise / end filter of a source-filter one."""
-    kind: str = "pass"     # "pass" (PassThrough) | "fir" (LTVZeroPhaseFIRFilter) | "frames" (LTVMinimumPhaseFilter);
-    #                        within this module also "allpole": the sample-wise end filter of golf-ss
-    hop: int = 1           # hop of its controls: the log magnitudes, or gain / a
+    kind: str = "pass"     # "pass" (PassThrough) | "fir" (LTVZeroPhaseFIRFilter) | "frames" (LTVMinimumPhaseFilter) | "stft"
+    #                        (LTVCepFilter, DiffWorldSPFilter); within this module also "allpole": the sample-wise end filter
+    hop: int = 1           # hop of its controls: the log magnitudes, gain / a, or the cepstra / mel envelope
     taps: int = 0          # fir: N = 2*(n_mag-1)
-    window: int = 0        # frames: W
+    window: int = 0        # frames: W; stft: n_fft
     centred: bool = True   # frames: False shifts the input by hop//2 and reflect-pads the output by as much
 
     @property
@@ -122,6 +130,20 @@ class HPNGeometry:
     noise: BranchGeometry = field(default_factory=BranchGeometry)
 
 
+@dataclass(frozen=True)
+class SpectralGeometry:
+    """What the bookkeeping of ``SpectralDecoderStream`` depends on: a harmonic source + filtered noise -> end filter."""
+    phase_hop: int
+    amp_hop: int = 0           # hop of the amplitude rows; 0: no amplitude track
+    noise: BranchGeometry = field(default_factory=BranchGeometry)
+    end: BranchGeometry = field(default_factory=BranchGeometry)
+    source: str = "harmonic"
+
+    @property
+    def window(self) -> int:
+        return self.end.window
+
+
 # ---- bookkeeping primitives: sources -------------------------------------------------------------------------------------------
 # The glottal source's functions take either geometry: they read ``phase_hop``, ``os``, ``half`` and ``w_hop`` alone.
 def _glottal_len(g, n_phase: int) -> int:
@@ -182,9 +204,17 @@ def _branch_open(b: BranchGeometry, n_in: int, ctrl: Tuple[int, ...]) -> Tuple[i
       fir      frame f reads its input up to (f+1)*hop - 1 + R
       frames   frame f reads x up to f*hop - pad + W - 1, a[f], and gain rows up to seg + 1 for the segment seg of its last
                sample, (f*hop - pad + W - 1) // hop = f + c; sample n is finished once its last frame, (n + pad) // hop, is
-      allpole  whole LPC hops: frame E/hop must be there to close the last sample's frame"""
+      allpole  whole LPC hops: frame E/hop must be there to close the last sample's frame
+      stft     frame f reads x up to f*hop + pad - 1 (no reflection at the right edge while the input is open; frame 0 reads
+               x[pad] through its left reflection) and response row f; sample n is finished once its last frame,
+               (n + pad) // hop, is"""
     if b.kind == "pass":
         return n_in, 0, n_in, n_in
+    if b.kind == "stft":
+        pad = b.window // 2
+        nfr = min(ctrl[0], (n_in - pad) // b.hop + 1) if n_in > pad else 0
+        n_y = max(0, nfr * b.hop - pad)
+        return n_y, nfr, n_y, n_in
     if b.kind == "fir":
         f = max(0, min(ctrl[0], (n_in - b.reach) // b.hop))
         return f * b.hop, f, f * b.hop, n_in
@@ -211,6 +241,12 @@ def _branch_final(b: BranchGeometry, n_in: int, ctrl: Tuple[int, ...],
             raise _lib.GolfError(short.format(n_in))
         return dict(out=min(span // b.hop + 1, ctrl[0]) * b.hop)
     F = ctrl[0]
+    if b.kind == "stft":   # torch.stft(center=True, reflect) / istft: frames = min(1 + T // hop, F), hop * (frames - 1) samples
+        nfr = min(1 + n_in // b.hop, F)
+        if n_in <= b.window // 2 or nfr < 2:   # (the one-shot raises too: in torch.stft's reflect pad, or in torch.istft)
+            raise _lib.GolfError(f"STFT-domain filter: {n_in} input samples with {F} control frames cannot be reflect-padded "
+                                 f"by n_fft/2 = {b.window // 2} or make fewer than two frames")
+        return dict(out=b.hop * (nfr - 1), filter_in=n_in, frames=nfr)
     if b.kind == "allpole":
         return dict(out=GF.ss_output_length(n_in, F, b.hop) if F >= 1 and n_in >= 1 else 0)
     x = n_in - b.shift
@@ -230,6 +266,8 @@ def _branch_lookahead(b: BranchGeometry, L_in: int) -> int:
         return b.hop - 1 + b.reach + L_in
     if b.kind == "allpole":
         return b.hop - 1 + L_in   # the emission granularity (whole LPC frames)
+    if b.kind == "stft":          # sample t waits for frame (t + pad) // hop, whose samples reach t + n_fft - 1
+        return b.window - 1 + L_in
     pad, s = b.window // 2, b.shift
     c = (b.window - pad - 1) // b.hop
     q = max(b.window - 1 + L_in, pad - s + b.hop * (c + 1))
@@ -332,16 +370,60 @@ def hpn_stream_latency(g: HPNGeometry) -> int:
       noise             max(P - 1, A - 1): the samples the one-shot is certain to draw
       FIR branch        + fir_hop - 1 + R  (R = N-1-(N-1)//2 samples read past the one written)
       frame-wise branch max(W - 1 + input, pad - s + hop * ((W - pad - 1) // hop + 1)) + 2 s   (s = hop//2 without centring)
-    and the output waits for both branches.  DDSP (phase at hop 1, amplitudes at 240, FIR 510 at 240): 239 + 239 + 255 = 733."""
+      STFT branch       + n_fft - 1  (the last frame that covers a sample reaches n_fft - 1 samples past it)
+    and the output waits for both branches.  DDSP (phase at hop 1, amplitudes at 240, FIR 510 at 240): 239 + 239 + 255 = 733.  NHV (phase
+    at hop 1, n_fft 1024 on the pulse train, FIR 510 at 240): max(1023 + 1, 239 + 255) = 1024."""
+    L_src, L_nz = _source_lookahead(g)
+    return max(_branch_lookahead(g.harm, L_src), _branch_lookahead(g.noise, L_nz))
+
+
+def _source_lookahead(g) -> Tuple[int, int]:
+    """(source, noise): the input time past a sample of the source, and of the noise the one-shot is certain to draw, by
+    which it is determined (``hpn_stream_latency``).  ``g``: HPNGeometry or SpectralGeometry."""
     P = g.phase_hop
     if g.source == "glottal" and g.os > 1:
-        L_src, L_nz = _glottal_lookahead(g), P - 1
-    else:   # (a glottal source without a decimator: the table-select rows as amplitudes; ``stream_latency`` keeps the
-        #      looser ``_glottal_lookahead`` there)
-        A = g.w_hop if g.source == "glottal" else g.amp_hop
-        L_src = P + A - math.gcd(P, A) if A else P
-        L_nz = P - 1 if g.source == "glottal" else max(P - 1, A - 1 if A else 0)
-    return max(_branch_lookahead(g.harm, L_src), _branch_lookahead(g.noise, L_nz))
+        return _glottal_lookahead(g), P - 1
+    # (a glottal source without a decimator: the table-select rows as amplitudes; ``stream_latency`` keeps the looser
+    #  ``_glottal_lookahead`` there)
+    A = g.w_hop if g.source == "glottal" else g.amp_hop
+    return P + A - math.gcd(P, A) if A else P, P - 1 if g.source == "glottal" else max(P - 1, A - 1 if A else 0)
+
+
+def _spectral_open(g: SpectralGeometry, n_phase: int, n_src: Optional[int], n_noise: Optional[int],
+                   noise_ctrl: Tuple[int, ...], end_ctrl: Tuple[int, ...]) -> Tuple[int, int, int, int, int]:
+    """(oscillator segments, its samples, noise samples, filtered noise samples, E) while the utterance is open."""
+    nseg, n_osc = _source_open(g, n_phase, n_src)
+    n_nz_in = _noise_len(_source_len(g, n_phase, n_src), n_noise)
+    n_nz = _branch_open(g.noise, n_nz_in, noise_ctrl)[0]
+    return nseg, n_osc, n_nz_in, n_nz, _branch_open(g.end, min(n_osc, n_nz), end_ctrl)[0]
+
+
+def spectral_emit_count(g: SpectralGeometry, n_phase: int, n_src: Optional[int], n_noise: Optional[int],
+                        noise_ctrl: Tuple[int, ...], end_ctrl: Tuple[int, ...]) -> int:
+    """E: the output samples [0, E) ``SpectralDecoderStream`` emits once these many steps of each track have been pushed
+    (arguments as ``hpn_emit_count``; ``end_ctrl``: the end filter's control rows).  The end filter runs on the sum of the
+    source and the filtered noise as far as both are known; a sample is out once every STFT frame that covers it is ready."""
+    return _spectral_open(g, n_phase, n_src, n_noise, noise_ctrl, end_ctrl)[4]
+
+
+def spectral_final_lengths(g: SpectralGeometry, n_phase: int, n_src: Optional[int], n_noise: Optional[int],
+                           noise_ctrl: Tuple[int, ...], end_ctrl: Tuple[int, ...]) -> dict:
+    """Lengths of the one-shot decoder's stages once the inputs have ended: oscillator, noise, filtered noise, their sum
+    (``source`` = ``filter_in``), the end filter's frames and the output."""
+    osc = _source_len(g, n_phase, n_src)
+    noise = _noise_len(osc, n_noise)
+    nz = _branch_final(g.noise, noise, noise_ctrl,
+                       "SpectralDecoderStream: {} noise samples are shorter than one noise-filter frame span")["out"]
+    src = min(osc, nz)
+    return dict(osc=osc, noise=noise, noise_filter=nz, source=src, **_branch_final(g.end, src, end_ctrl))
+
+
+def spectral_stream_latency(g: SpectralGeometry) -> int:
+    """Worst-case lookahead of ``SpectralDecoderStream`` in samples, composed as ``hpn_stream_latency`` composes it: the end
+    filter's n_fft - 1 on top of the later of the source and the filtered noise.  WORLD (n_fft 1024, phase at hop 1, FIR 510
+    at hop 240): 1023 + max(1, 239 + 255) = 1517."""
+    L_src, L_nz = _source_lookahead(g)
+    return _branch_lookahead(g.end, max(L_src, _branch_lookahead(g.noise, L_nz)))
 
 
 # ---- tracks --------------------------------------------------------------------------------------------------------------------
@@ -630,6 +712,13 @@ class _BranchStage:
             self._win = module._window.detach().float().to(dev).contiguous()
             self._filtered = self._n_x = 0
             self._carry = None
+        elif b.kind == "stft":
+            self._module = module
+            self._H = _Track()
+            self._win = module._window.detach().float().to(dev).contiguous()
+            self._filtered = 0
+            self._carry = None
+            self._width = None
 
     @staticmethod
     def geometry(kind: str, module, params, who: str, role: str = "") -> BranchGeometry:
@@ -643,11 +732,15 @@ class _BranchStage:
             if W < 2 * hop:
                 raise ValueError(f"{who}: {role}window {W} < 2*hop {2 * hop}")
             return BranchGeometry("frames", hop=hop, window=W, centred=bool(module.centred))
+        if kind == "stft":
+            if int(params[0].hop_length) != int(module.hop_length):
+                raise ValueError(f"{who}: {role}controls at hop {params[0].hop_length}, the filter's hop is {module.hop_length}")
+            return BranchGeometry("stft", hop=int(module.hop_length), window=int(module.n_fft))
         return BranchGeometry()
 
     def ctrl(self) -> Tuple[int, ...]:
         """The control rows pushed so far: () / (log_mag,) / (gain, a)."""
-        if self.b.kind == "fir":
+        if self.b.kind in ("fir", "stft"):
             return (self.n_ctrl,)
         return (self._g.end, self._a.end) if self.b.kind == "frames" else ()
 
@@ -656,8 +749,26 @@ class _BranchStage:
             raise ValueError(f"{who}.push: the FIR bins changed between pushes")
         if self.b.kind == "frames" and self._a.data is not None and params[1].shape[2] != self._a.data.shape[2]:
             raise ValueError(f"{who}.push: the LPC order changed between pushes")
+        if self.b.kind == "stft" and self._width not in (None, int(params[0].shape[2])):
+            raise ValueError(f"{who}.push: the width of the STFT-domain filter's controls changed between pushes")
+
+    def _response(self, ctrl: torch.Tensor) -> torch.Tensor:
+        """(B, rows, n_fft/2 + 1) response rows from control rows, by the module's own code: the rows of the one-shot's H."""
+        from .filters import LTVCepFilter
+
+        m = self._module
+        if isinstance(m, LTVCepFilter):
+            return m.frequency_response(ctrl)[:, : m.n_fft // 2 + 1].transpose(1, 2).contiguous()
+        return torch.sqrt(ctrl @ m.fb)
 
     def append(self, params) -> None:
+        if self.b.kind == "stft":
+            c = params[0]
+            self._width = int(c.shape[2])
+            if c.shape[1]:
+                self._H.append(self._response(_f32(c, self._dev)))
+            self.n_ctrl += c.shape[1]
+            return
         if self.b.kind == "fir":
             lm = params[0]
             if lm.shape[1]:
@@ -681,6 +792,29 @@ class _BranchStage:
             if final:
                 self.check_final(who)
             self._run_frames(n_in, final, fin)
+        elif self.b.kind == "stft":
+            self._run_stft(n_in, final, fin)
+
+    def _run_stft(self, n_in: int, final: bool, fin) -> None:
+        """Filter the STFT frames that are ready and write the samples they finish (golf_stft_filter_frames_stream_f32)."""
+        b = self.b
+        if final:
+            n_y, nfr = fin["out"], fin["frames"]
+        else:
+            n_y, nfr = _branch_open(b, n_in, self.ctrl())[:2]
+        f0, n0 = self._frames, self._filtered
+        if nfr <= f0 and n_y <= n0:
+            return
+        y, self._carry = GF.stft_filter_stream(
+            self.src.get(self.src.start, self.src.end), self._H.data, self._win, b.hop, self._carry, x0=self.src.start,
+            h0=self._H.start, f0=f0, nf=max(0, nfr - f0), n0=n0, ny=max(0, n_y - n0), x_end=n_in if final else -1,
+            frames_end=nfr if final else -1)
+        self._frames, self._filtered = max(f0, nfr), max(n0, n_y)
+        # the next frame starts at frames*hop - pad; should it turn out to be the utterance's last, of a length that is a
+        # multiple of hop, its right reflection reads one sample before that
+        self.src.drop_before(max(0, self._frames * b.hop - b.window // 2 - 1))
+        self._H.drop_before(self._frames)
+        self.out.append(y, fresh=True)
 
     def _run_fir(self, n_in: int, final: bool, fin) -> None:
         b = self.b
@@ -808,60 +942,86 @@ def _check_tracks(want, B: int, who: str) -> None:
 
 
 class _Series:
-    """source + filtered noise -> LPC end filter -> room filter: golf-ss (``lpc`` None: the sample-wise all-pole filter) and
-    golf-ff (``lpc``: the frame-wise filter module).  Built from the tracks of the first push; every push after it passes
-    ``check``, ``append`` and ``advance`` with the same arguments ``(phase, wsel, gain, a, lm, noise)``, ``lm`` None without a
-    noise filter.  ``checks_first``: at finish, the tracks' own faults are reported before those of the lengths."""
+    """source + filtered noise -> end filter -> room filter: golf-ss (``lpc`` None: the sample-wise all-pole filter), golf-ff
+    (``lpc``: the frame-wise filter module) and, on a harmonic source, WORLD (``lpc``: the STFT-domain filter module).  Built
+    from the tracks of the first push; every push after it passes ``check``, ``append`` and ``advance`` with the same
+    arguments ``(phase, osc_params, end_params, lm, noise)`` -- ``osc_params`` (wsel,) for the glottal table, ``end_params``
+    (gain, a) or the STFT-domain filter's (controls,), ``lm`` None without a noise filter.  ``checks_first``: at finish, the
+    tracks' own faults are reported before those of the lengths.  The glottal source keeps its books with ``StreamGeometry``
+    (``_series_open`` / ``final_lengths``), the harmonic one with ``SpectralGeometry``."""
 
-    def __init__(self, who: str, decoder, lpc, B: int, generated_noise: bool, checks_first: bool, phase, wsel, gain, a, lm,
-                 noise):
+    def __init__(self, who: str, decoder, lpc, B: int, generated_noise: bool, checks_first: bool, phase, osc_params,
+                 end_params, lm, noise, refuse=None):
         dev = phase.device
         _require_device(phase, who)
-        b_lpc = _BranchStage.geometry("frames", lpc, (gain, a), who) if lpc is not None else None
-        if lpc is None and int(gain.hop_length) != int(a.hop_length):
-            raise ValueError(f"{who}: gain at hop {gain.hop_length}, a at hop {a.hop_length}")
+        osc = decoder.harm_oscillator
+        b_lpc = _BranchStage.geometry(_branch_kind(lpc), lpc, end_params, who) if lpc is not None else None
+        if lpc is None and int(end_params[0].hop_length) != int(end_params[1].hop_length):
+            raise ValueError(f"{who}: gain at hop {end_params[0].hop_length}, a at hop {end_params[1].hop_length}")
         b_nz = _BranchStage.geometry("fir" if lm is not None else "pass", decoder.noise_filter, (lm,), who)
-        g = StreamGeometry(hop=int(a.hop_length), phase_hop=int(phase.hop_length), w_hop=int(wsel.hop_length),
-                           fir_taps=b_nz.taps, fir_hop=b_nz.hop, window=b_lpc.window if b_lpc else 0,
-                           **_GlottalSource.decimator(decoder.harm_oscillator))
+        if _is_glottal(osc):
+            g = StreamGeometry(hop=int(end_params[1].hop_length), phase_hop=int(phase.hop_length),
+                               w_hop=int(osc_params[0].hop_length), fir_taps=b_nz.taps, fir_hop=b_nz.hop,
+                               window=b_lpc.window if b_lpc else 0, **_GlottalSource.decimator(osc))
+            self.source = _GlottalSource(osc, g, B, dev)
+            self._end_names = ("gain", "a")
+        else:
+            self.source = _HarmonicSource(osc, int(phase.hop_length), osc_params, B, dev, False, refuse)
+            g = SpectralGeometry(phase_hop=int(phase.hop_length), amp_hop=self.source.amp_hop, noise=b_nz, end=b_lpc)
+            self._end_names = ("end filter track",) * len(end_params)
         self.who, self.B, self.geometry, self.checks_first, self._dev = who, B, g, checks_first, dev
-        self.source = _GlottalSource(decoder.harm_oscillator, g, B, dev)
         self.noise = _Noise(B, dev, noise is not None, generated_noise)
         self.noise_filter = _BranchStage(b_nz, decoder.noise_filter, self.noise.out, B, dev)
         if lpc is None:
-            self.lpc = _AllPoleStage(g.hop, int(a.shape[2]), B, dev)
+            self.lpc = _AllPoleStage(g.hop, int(end_params[1].shape[2]), B, dev)
         else:   # its input: the running sum osc + filtered noise, as far as both are known
             self.mix = _Track()
             self.lpc = _BranchStage(b_lpc, lpc, self.mix, B, dev)
         self.room = _Room(decoder.room_filter, B, dev) if _room_kind(decoder.room_filter) == "lti" else None
         self.emitted = 0
 
-    def check(self, phase, wsel, gain, a, lm, noise) -> None:
-        g = self.geometry
-        want = [(phase, g.phase_hop, "phase"), (wsel, g.w_hop, "table select"), (gain, g.hop, "gain"), (a, g.hop, "a")]
+    def check(self, phase, osc_params, end_params, lm, noise) -> None:
+        g, src = self.geometry, self.source
+        hop = g.hop if isinstance(g, StreamGeometry) else g.end.hop
+        want = [(phase, g.phase_hop, "phase")]
+        if src.rows_hop:
+            want.append((osc_params[0], src.rows_hop, src.rows_name))
+        want += [(t, hop, name) for t, name in zip(end_params, self._end_names)]
         if lm is not None:
-            want.append((lm, g.fir_hop, "log_mag"))
+            want.append((lm, self.noise_filter.b.hop, "log_mag"))
         if noise is not None:
             want.append((noise, 1, "noise"))
         _check_tracks(want, self.B, self.who)
-        self.lpc.check((gain, a), self.who)
+        src.check(osc_params, self.who)
+        self.lpc.check(end_params, self.who)
         self.noise_filter.check((lm,), self.who)
         self.noise.check(noise, self.who)
 
-    def append(self, phase, wsel, gain, a, lm, noise) -> None:
-        self.source.append(phase, None, (wsel,))
-        self.lpc.append((gain, a))
+    def append(self, phase, osc_params, end_params, lm, noise) -> None:
+        self.source.append(phase, None, osc_params)
+        self.lpc.append(end_params)
         self.noise.append(noise)
         self.noise_filter.append((lm,))
 
+    def _open_lengths(self) -> Tuple[int, int, int, int, int]:
+        g, src = self.geometry, self.source
+        if isinstance(g, StreamGeometry):
+            return _series_open(g, src.ph.end, src.w.end, self.noise.pushed, self.noise_filter.n_ctrl, *self.lpc.ctrl())
+        return _spectral_open(g, src.ph.end, src.rows(), self.noise.pushed, self.noise_filter.ctrl(), self.lpc.ctrl())
+
     def _final_lengths(self) -> dict:
+        g, src = self.geometry, self.source
+        if not isinstance(g, StreamGeometry):
+            src.check_final(self.who)
+            return spectral_final_lengths(g, src.ph.end, src.rows(), self.noise.pushed, self.noise_filter.ctrl(),
+                                          self.lpc.ctrl())
         n_gain, n_a = self.lpc.ctrl()
         if self.checks_first:
             self.lpc.check_final(self.who)
-            self.source.check_final(self.who)
-        fl = final_lengths(self.geometry, self.source.ph.end, self.noise.pushed, self.noise_filter.n_ctrl, min(n_gain, n_a))
+            src.check_final(self.who)
+        fl = final_lengths(g, src.ph.end, self.noise.pushed, self.noise_filter.n_ctrl, min(n_gain, n_a))
         self.lpc.check_final(self.who)
-        self.source.check_final(self.who)
+        src.check_final(self.who)
         return fl
 
     def advance(self, final: bool) -> torch.Tensor:
@@ -872,8 +1032,7 @@ class _Series:
             n_mix = fl.get("filter_in")
         else:
             fl = None
-            nseg, n_osc, n_noise, n_nz, E = _series_open(g, src.ph.end, src.w.end, self.noise.pushed, nzf.n_ctrl,
-                                                         *lpc.ctrl())
+            nseg, n_osc, n_noise, n_nz, E = self._open_lengths()
             n_mix = min(n_osc, n_nz)
         src.run(nseg, n_osc, final)
         self.noise.run(n_noise)
@@ -993,15 +1152,30 @@ def _is_glottal(osc) -> bool:
 
 
 def _branch_kind(f) -> Optional[str]:
-    """"pass" / "fir" / "frames" for PassThrough, the plain zero-phase FIR and the frame-wise LPC filter; None otherwise."""
+    """"pass" / "fir" / "frames" / "stft" for PassThrough, the plain zero-phase FIR, the frame-wise LPC filter and the
+    STFT-domain filters (LTVCepFilter, DiffWorldSPFilter); None otherwise."""
     from .ctrl import PassThrough
-    from .filters import LTVMinimumPhaseFilter, LTVZeroPhaseFIRFilter
+    from .filters import DiffWorldSPFilter, LTVCepFilter, LTVMinimumPhaseFilter, LTVZeroPhaseFIRFilter
 
     if type(f) is PassThrough:
         return "pass"
     if _plain(f, LTVZeroPhaseFIRFilter):
         return "fir"
+    if type(f) in (LTVCepFilter, DiffWorldSPFilter):
+        return "stft"
     return "frames" if type(f) is LTVMinimumPhaseFilter else None
+
+
+def _stft_unsupported(f) -> Optional[str]:
+    """What golf_stft_filter_frames_stream_f32 does not take of an STFT-domain filter module, or None."""
+    n, hop = int(f.n_fft), int(f.hop_length)
+    if not getattr(f, "center", True):
+        return f"{type(f).__name__} with center=False"
+    if n & (n - 1) or not 64 <= n <= 2048:
+        return f"{type(f).__name__} with n_fft {n} (a power of two in [64, 2048] is needed)"
+    if n < 2 * hop:
+        return f"{type(f).__name__} with n_fft {n} < 2*hop {2 * hop}"
+    return None
 
 
 def _room_kind(f) -> Optional[str]:
@@ -1055,6 +1229,8 @@ class _Stream:
         if self._pipe is None:
             raise RuntimeError(f"{self._who}.latency: the hops are fixed by the first push")
         g = self.geometry
+        if isinstance(g, SpectralGeometry):
+            return spectral_stream_latency(g)
         return stream_latency(g) if isinstance(g, StreamGeometry) else hpn_stream_latency(g)
 
     def _geometry(self):
@@ -1147,8 +1323,9 @@ class DecoderStream(_Stream):
         if len(end_filter_params) != 2 or len(noise_filter_params) != (1 if self.has_fir else 0):
             raise ValueError("DecoderStream.push: end_filter_params=(gain, a) and noise_filter_params=(log_mag,) (or () "
                              "without a noise filter) are required")
-        args = (phase, harm_oscillator_params[0], *end_filter_params, noise_filter_params[0] if self.has_fir else None, noise)
-        return self._push(args, noise, args)
+        lm = noise_filter_params[0] if self.has_fir else None
+        return self._push((phase, *harm_oscillator_params, *end_filter_params, lm, noise), noise,
+                          (phase, harm_oscillator_params, end_filter_params, lm, noise))
 
     def _open(self, *args) -> _Series:
         return _Series(self._who, self.decoder, None, self.B, self.generated_noise, False, *args)
@@ -1220,8 +1397,9 @@ class FramewiseDecoderStream(_Stream):
         if self.hpn:
             args = (phase, harm_oscillator_params, lpc_params, noise_filter_params, noise, None)
             return self._push((phase, *harm_oscillator_params, *lpc_params, *noise_filter_params, noise), noise, args)
-        args = (phase, harm_oscillator_params[0], *lpc_params, noise_filter_params[0] if self.has_fir else None, noise)
-        return self._push(args, noise, args)
+        lm = noise_filter_params[0] if self.has_fir else None
+        return self._push((phase, *harm_oscillator_params, *lpc_params, lm, noise), noise,
+                          (phase, harm_oscillator_params, lpc_params, lm, noise))
 
     def _open(self, *args):
         if not self.hpn:
@@ -1245,14 +1423,17 @@ class HarmonicPlusNoiseStream(_Stream):
 
     with the one-shot call's arguments sliced: ``harm_oscillator_params`` (amplitudes,) for HarmonicOscillator,
     AdditiveSynthesizer and V1AdditiveSynthesizer, () for SawToothOscillator and AdditivePulseTrain, (wsel,) for the glottal
-    table; each branch's params () / (log_mag,) / (gain, a) for PassThrough / LTVZeroPhaseFIRFilter / LTVMinimumPhaseFilter;
+    table; each branch's params () / (log_mag,) / (gain, a) / (ceps,) or (mel_sp,) for PassThrough / LTVZeroPhaseFIRFilter /
+    LTVMinimumPhaseFilter / the STFT-domain filters LTVCepFilter or DiffWorldSPFilter (NHV: ``harm_filter_params=(ceps,)``);
     ``voicing`` (at the phase's hop) multiplies the phase as the one-shot does.  Same contract as ``DecoderStream``: each push
     returns the (B, n) fp32 samples the inputs pushed so far determine (``hpn_emit_count``), ``finish()`` the rest;
-    ``latency`` and ``counts()`` as there.  ``open_stream`` does not return this class: open it explicitly.
+    ``latency`` and ``counts()`` as there.  ``open_stream`` returns this class for a decoder with an STFT-domain branch (NHV)
+    only: open it explicitly otherwise.
     Inference only; one stream for the whole batch."""
     _COVERS = ("it covers HarmonicPlusNoiseSynth with the harmonic oscillator bank -- HarmonicOscillator, AdditiveSynthesizer, "
                "V1AdditiveSynthesizer, SawToothOscillator, AdditivePulseTrain -- or an indexed glottal table; PassThrough, "
-               "LTVZeroPhaseFIRFilter or LTVMinimumPhaseFilter on each branch; standard normal noise or noise pushed with "
+               "LTVZeroPhaseFIRFilter, LTVMinimumPhaseFilter, LTVCepFilter or DiffWorldSPFilter (centred, n_fft a power of two "
+               "in [64, 2048]) on each branch; standard normal noise or noise pushed with "
                "every block; PassThrough or LTIAcousticFilter as the end filter; voicing at the phase's hop")
 
     def __init__(self, decoder, batch_size: int):
@@ -1278,6 +1459,8 @@ class HarmonicPlusNoiseStream(_Stream):
             if self._kinds[role] is None:
                 self._refuse(f"the {role} {type(f).__name__}"
                              + (" (the sample-wise LPC filter)" if type(f).__name__ == "LTVMinimumPhaseFilterPrecise" else ""))
+            if self._kinds[role] == "stft" and _stft_unsupported(f):
+                self._refuse(f"the {role} " + _stft_unsupported(f))
         if _room_kind(decoder.end_filter) is None:
             self._refuse(f"the end filter {type(decoder.end_filter).__name__}")
         super().__init__(decoder, batch_size)
@@ -1299,7 +1482,7 @@ class HarmonicPlusNoiseStream(_Stream):
         if len(harm_oscillator_params) != n_osc:
             self._refuse(f"{len(harm_oscillator_params)} oscillator parameters for {type(osc).__name__}"
                          f" (it takes {n_osc}; initial_phase / phase_offset are not streamed)")
-        want = {"pass": 0, "fir": 1, "frames": 2}
+        want = {"pass": 0, "fir": 1, "frames": 2, "stft": 1}
         for name, params, role in (("harm_filter_params", harm_filter_params, "harmonic filter"),
                                    ("noise_filter_params", noise_filter_params, "noise filter")):
             if len(params) != want[self._kinds[role]]:
@@ -1316,12 +1499,91 @@ class HarmonicPlusNoiseStream(_Stream):
         return _Parallel(self._who, self._refuse, self.decoder, kinds, self.B, self.generated_noise, False, *args)
 
 
-def open_stream(decoder, batch_size: int):
-    """A streaming synthesiser for ``decoder``: ``FramewiseDecoderStream`` for the decoders built on the frame-wise LPC filter
-    (golf-ff's end filter, golf-v1's harmonic filter), ``DecoderStream`` otherwise (golf-ss)."""
-    from .filters import LTVMinimumPhaseFilter
-    from .sf import HarmonicPlusNoiseSynth
+class SpectralDecoderStream(_Stream):
+    """Block-by-block synthesis with a ``SourceFilterSynth`` on a harmonic source whose end filter works in the STFT domain:
+    the WORLD baseline (AdditivePulseTrain + filtered noise -> DiffWorldSPFilter -> room filter).
 
+        ``push(phase, harm_oscillator_params=(), noise_filter_params=(log_mag,), end_filter_params=(mel_sp,), noise=None)``
+
+    with the one-shot call's arguments sliced (``harm_oscillator_params`` (amplitudes,) for the oscillators that take them).
+    Same contract as ``DecoderStream``: each push returns the (B, n) fp32 samples the inputs pushed so far determine
+    (``spectral_emit_count``), ``finish()`` the rest -- it raises ``GolfError`` for an utterance too short to be
+    reflect-padded, as the one-shot does; ``latency`` (``spectral_stream_latency``) and ``counts()`` as there.  Every STFT
+    frame is filtered once, by golf_stft_filter_frames_stream_f32, which carries the last ceil(n_fft/hop) - 1 of them.
+    Inference only; one stream for the whole batch."""
+    _COVERS = ("it covers SourceFilterSynth with the harmonic oscillator bank -- HarmonicOscillator, AdditiveSynthesizer, "
+               "V1AdditiveSynthesizer, SawToothOscillator, AdditivePulseTrain --, standard normal noise or noise pushed with "
+               "every block, the zero-phase FIR noise filter or none, LTVCepFilter or DiffWorldSPFilter (centred, n_fft a "
+               "power of two in [64, 2048]) as the end filter, the LTI room filter or none")
+
+    def __init__(self, decoder, batch_size: int):
+        from .sf import SourceFilterSynth
+        from .synth import (AdditivePulseTrain, AdditiveSynthesizer, HarmonicOscillator, SawToothOscillator,
+                            V1AdditiveSynthesizer)
+
+        if not _plain(decoder, SourceFilterSynth):
+            self._refuse(type(decoder).__name__)
+        if decoder.subtract_harmonics:
+            self._refuse("subtract_harmonics=True")
+        osc, ef = decoder.harm_oscillator, decoder.end_filter
+        if type(osc) not in (HarmonicOscillator, AdditiveSynthesizer, V1AdditiveSynthesizer, SawToothOscillator,
+                             AdditivePulseTrain):
+            self._refuse(f"the oscillator {type(osc).__name__}")
+        if not _value_independent(decoder.noise_generator):
+            self._refuse(f"the noise generator {type(decoder.noise_generator).__name__}")
+        if _branch_kind(decoder.noise_filter) not in ("pass", "fir"):
+            self._refuse(f"the noise filter {type(decoder.noise_filter).__name__}")
+        if _branch_kind(ef) != "stft":
+            self._refuse(f"the end filter {type(ef).__name__}")
+        if _stft_unsupported(ef):
+            self._refuse("the end filter " + _stft_unsupported(ef))
+        if _room_kind(decoder.room_filter) is None:
+            self._refuse(f"the room filter {type(decoder.room_filter).__name__}")
+        super().__init__(decoder, batch_size)
+        self.has_fir = _branch_kind(decoder.noise_filter) == "fir"
+
+    def counts(self) -> dict:
+        """Steps pushed so far per track (host integers)."""
+        p = self._pipe
+        return dict(phase=p.source.n_phase_pushed, oscillator=p.source.rows(),
+                    noise=None if self.generated_noise else p.noise.pushed, noise_filter=p.noise_filter.ctrl(),
+                    end_filter=p.lpc.ctrl())
+
+    def push(self, phase: AudioTensor, harm_oscillator_params: Tuple[AudioTensor, ...] = (),
+             noise_generator_params: Tuple = (), noise_filter_params: Tuple[AudioTensor, ...] = (),
+             end_filter_params: Tuple[AudioTensor, ...] = (), noise: AudioTensor = None, voicing=None,
+             **other_params) -> torch.Tensor:
+        self._begin_push(noise_generator_params, voicing)
+        osc = self.decoder.harm_oscillator
+        n_osc = 1 if _HarmonicSource.takes_amplitudes(osc) else 0
+        if len(harm_oscillator_params) != n_osc:
+            self._refuse(f"{len(harm_oscillator_params)} oscillator parameters for {type(osc).__name__}"
+                         f" (it takes {n_osc}; initial_phase / phase_offset are not streamed)")
+        if len(end_filter_params) != 1 or len(noise_filter_params) != (1 if self.has_fir else 0):
+            raise ValueError("SpectralDecoderStream.push: end_filter_params=(controls,) and noise_filter_params=(log_mag,) "
+                             "(or () without a noise filter) are required")
+        lm = noise_filter_params[0] if self.has_fir else None
+        return self._push((phase, *harm_oscillator_params, *end_filter_params, lm, noise), noise,
+                          (phase, harm_oscillator_params, end_filter_params, lm, noise))
+
+    def _open(self, *args) -> _Series:
+        return _Series(self._who, self.decoder, self.decoder.end_filter, self.B, self.generated_noise, True, *args,
+                       refuse=self._refuse)
+
+
+def open_stream(decoder, batch_size: int):
+    """A streaming synthesiser for ``decoder``: ``SpectralDecoderStream`` for a ``SourceFilterSynth`` whose end filter works in
+    the STFT domain (WORLD), ``HarmonicPlusNoiseStream`` for a ``HarmonicPlusNoiseSynth`` with such a branch (NHV),
+    ``FramewiseDecoderStream`` for the decoders built on the frame-wise LPC filter (golf-ff's end filter, golf-v1's harmonic
+    filter), ``DecoderStream`` otherwise (golf-ss)."""
+    from .filters import LTVMinimumPhaseFilter
+    from .sf import HarmonicPlusNoiseSynth, SourceFilterSynth
+
+    if isinstance(decoder, SourceFilterSynth) and _branch_kind(decoder.end_filter) == "stft":
+        return SpectralDecoderStream(decoder, batch_size)
+    if isinstance(decoder, HarmonicPlusNoiseSynth) and "stft" in (_branch_kind(decoder.harm_filter),
+                                                                  _branch_kind(decoder.noise_filter)):
+        return HarmonicPlusNoiseStream(decoder, batch_size)
     if isinstance(decoder, HarmonicPlusNoiseSynth) or isinstance(getattr(decoder, "end_filter", None), LTVMinimumPhaseFilter):
         return FramewiseDecoderStream(decoder, batch_size)
     return DecoderStream(decoder, batch_size)

@@ -231,6 +231,37 @@ int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride, int64_t x
                                    const float* window, int64_t f0, int nf, float* y, int64_t y_stride, int64_t n0, int ny,
                                    int B, int M, int hop, int W, float* carry, void* ws, size_t ws_bytes, void* stream);
 
+/* STFT-domain frame filter, streaming form (additive in ABI 6): the arithmetic of LTVCepFilter (NHV) and DiffWorldSPFilter
+ * (WORLD) -- torch.stft(center=True, reflect) -> multiply by a per-frame response -> torch.istft -- frame by frame, in global
+ * sample / frame indices.  With n = n_fft, w = window:
+ *   frame f covers x[f*hop - n/2, f*hop + n/2); an index i < 0 reads x[-i]; once the utterance has ended an index i >= x_end
+ *   reads x[2(x_end-1) - i];   u_f = Re IFFT(FFT(w * frame_f) * H_f);
+ *   y[m] = sum_f w[k]*u_f[k] / sum_f w[k]^2,  k = m + n/2 - f*hop, over the frames 0 <= f < frames that cover m.
+ * One call filters frames [f0, f0+nf) -- each frame once over the stream -- and writes samples [n0, n0+ny) to y (B, ny).
+ *   x       window of the input: global samples [x0, x0+nx), row stride x_stride
+ *   h       response rows [h0, h0+nh) on bins 0 .. n/2, contiguous: (B, nh, n/2+1) real (h_kind 0) or (B, nh, n/2+1, 2)
+ *           interleaved complex (h_kind 1); bins above n/2 follow by Hermitian symmetry
+ *   x_end, frames_end  -1 while the utterance is open; once it has ended, its length T > n/2 and frames = min(1 + T/hop, F)
+ *           (at most 1 + T/hop): they switch on the right reflection and clip the frame range and the normaliser; the
+ *           output then ends at hop*(frames-1)
+ *   carry   caller-owned (B, S, n) fp32 device buffer, zero-initialised, S = ceil(n/hop) - 1
+ *           (golf_stft_filter_stream_state_bytes): the last S filtered frames, frame f at slot f % S
+ *   ws      scratch of 4*B*(S+nf)*n bytes, 256-aligned (NULL with nf = ny = 0)
+ * Refused before any launch: null pointers; n not a power of two in [64, 2048] (GOLF_EUNSUPPORTED); n < 2*hop; windows that
+ * do not cover frames [f0, f0+nf), the samples they read (reflections included: the last frame of an utterance whose length
+ * is a multiple of hop reads x[T-1-n/2], one sample before its own span) or their response rows; samples [n0, n0+ny) that
+ * need a frame >= f0+nf or one older than the carry holds; frame f0 reaching a sample before n0; leaving unwritten a sample
+ * that needs a frame older than f0+nf-S; x_end <= n/2.
+ * The transform is a radix-4 Stockham FFT in LDS with twiddles from sincospif; a frame's bits depend on its own samples and
+ * its own response row only, and each sample sums its frames in ascending f with fmaf, the normaliser in the same order, so
+ * the output does not depend on how the input is split into calls.  Two launches (frames, then overlap-add); none when
+ * nf = ny = 0.  No host<->device synchronisation. */
+size_t golf_stft_filter_stream_state_bytes(int B, int n_fft, int hop);
+int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stride, int64_t x0, int nx, int64_t x_end, const float* h,
+                                       int64_t h0, int nh, int h_kind, int64_t frames_end, const float* window, int64_t f0,
+                                       int nf, float* y, int64_t y_stride, int64_t n0, int ny, int B, int n_fft, int hop,
+                                       float* carry, void* ws, size_t ws_bytes, void* stream);
+
 /* Custom backward of the above (what autograd computes in the reference through conv_transpose1d, lfilter, unfold,
  * the zero pad and the gain product; closed form in oracle/golf_oracle.py::lti_frames_ola_backward, pinned by
  * tests/golden/g15):  g_q = gy/norm;  u_f = the frame's all-pole recursion run backwards in time on window*g_q;
