@@ -28,7 +28,7 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // ---- chunk plan shared by forward and backward of the sample-wise filter -------------------
 struct SsPlan {
-    int W;      // ring/unroll width: W >= M+1, hop % W == 0  (0 => generic fallback)
+    int W;      // ring/unroll width: W >= M+1, hop % W == 0  (0 => no ring plan: lpc_any.hip)
     int NT;     // taps computed (>= M, zero padded)
     int L;      // chunk length: L % W == 0 and (L % hop == 0 || hop % L == 0)
     int NC;     // chunks per utterance = ceil(T/L)
@@ -48,5 +48,15 @@ struct SsPlan {
     size_t off_gflag;   // merged chunk pass (lpc_fwdq2m_kernel): [B][NG] "defect response published" + [B] "fp64 states ready" words
 };
 bool make_ss_plan(int B, int T, int F, int M, int hop, SsPlan* p, int mode = 0);
+
+// ---- sample-wise filter for the shapes without a plan (lpc_any.hip): any 1 <= M <= 64, hop >= 1, F >= 1 ---------------------
+size_t any_ws_bytes(int B, int T);   // the backward's workspace: g (B, T)
+// state == nullptr: y[<0] = 0; else state (B, M) in and out (golf_ltv_allpole_fwd_state_f32)
+int launch_any_fwd(const float* ex, int64_t ex_stride, const float* gain, const float* a, float* y, int64_t y_stride, int B,
+                   int T, int F, int M, int hop, float* state, hipStream_t st);
+// tail: g_ex[b][T .. T + tail) is zeroed (GOLF_SS_ZERO_TAIL)
+int launch_any_bwd(const float* gy, int64_t gy_stride, const float* y, int64_t y_stride, const float* ex, int64_t ex_stride,
+                   const float* gain, const float* a, float* g_ex, int64_t g_ex_stride, float* g_gain, float* g_a, int B, int T,
+                   int F, int M, int hop, char* ws, int64_t tail, hipStream_t st);
 
 }  // namespace golf

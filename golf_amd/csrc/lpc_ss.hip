@@ -3225,68 +3225,6 @@ __global__ void lpc_grad_reduce_kernel(const float* __restrict__ pa, const float
     else g_gain[(size_t)b * F + f] = acc;
 }
 
-// ------------------------------------------------------------------------------------------
-// Generic fallback (any hop / M <= 64 / F >= 1): one lane per utterance, serial in t, history read
-// back from the output row.  Correct for every shape, slow; only used when no W divides hop.
-// ------------------------------------------------------------------------------------------
-__global__ void lpc_ss_generic_kernel(const float* __restrict__ ex, int64_t ex_stride, const float* __restrict__ gain,
-                                      const float* __restrict__ a, float* y, int64_t y_stride, int B, int T, int F,
-                                      int M, int hop) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const float* exb = ex + (size_t)b * ex_stride;
-    volatile float* yb = y + (size_t)b * y_stride;
-    const float inv_hop = 1.0f / (float)hop;
-    for (int t = 0; t < T; ++t) {
-        int f = F >= 2 ? t / hop : 0;
-        if (F >= 2 && f > F - 2) f = F - 2;
-        const float n = (float)(t - f * hop);
-        const float* pa0 = a + ((size_t)b * F + f) * M;
-        const float* pa1 = F >= 2 ? pa0 + M : pa0;
-        const float g0 = gain[(size_t)b * F + f];
-        const float g1 = F >= 2 ? gain[(size_t)b * F + f + 1] : g0;
-        float acc = exb[t] * fmaf(n, (g1 - g0) * inv_hop, g0);
-        float ra = 0.f;
-        for (int i = M - 1; i >= 0; --i) {
-            if (t - 1 - i < 0) continue;
-            const float cf = fmaf(n, (pa1[i] - pa0[i]) * inv_hop, pa0[i]);
-            ra = fmaf(cf, yb[t - 1 - i], ra);
-        }
-        yb[t] = acc - ra;
-    }
-}
-
-// The same with a carried state (golf_ltv_allpole_fwd_state_f32): y[<0] = state[b][-1-t'], every tap taken in the order above;
-// afterwards the row's last M outputs (for T < M: with the old state shifted in) replace the state, highest index first so that
-// no entry is overwritten before it is read.
-__global__ void lpc_ss_generic_state_kernel(const float* __restrict__ ex, int64_t ex_stride, const float* __restrict__ gain,
-                                            const float* __restrict__ a, float* y, int64_t y_stride, int B, int T, int F,
-                                            int M, int hop, float* state) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const float* exb = ex + (size_t)b * ex_stride;
-    volatile float* yb = y + (size_t)b * y_stride;
-    float* sb = state + (size_t)b * M;
-    const float inv_hop = 1.0f / (float)hop;
-    for (int t = 0; t < T; ++t) {
-        int f = F >= 2 ? t / hop : 0;
-        if (F >= 2 && f > F - 2) f = F - 2;
-        const float n = (float)(t - f * hop);
-        const float* pa0 = a + ((size_t)b * F + f) * M;
-        const float* pa1 = F >= 2 ? pa0 + M : pa0;
-        const float g0 = gain[(size_t)b * F + f];
-        const float g1 = F >= 2 ? gain[(size_t)b * F + f + 1] : g0;
-        float acc = exb[t] * fmaf(n, (g1 - g0) * inv_hop, g0);
-        float ra = 0.f;
-        for (int i = M - 1; i >= 0; --i) {
-            const float cf = fmaf(n, (pa1[i] - pa0[i]) * inv_hop, pa0[i]);
-            ra = fmaf(cf, t - 1 - i >= 0 ? yb[t - 1 - i] : sb[i - t], ra);
-        }
-        yb[t] = acc - ra;
-    }
-    for (int i = M - 1; i >= 0; --i) sb[i] = i < T ? yb[T - 1 - i] : sb[i - T];
-}
-
 // a-5 inverse filter: fully parallel FIR with interpolated coefficients.
 __global__ void lpc_inverse_kernel(const float* __restrict__ y, int64_t y_stride, const float* __restrict__ a,
                                    float* __restrict__ e, int64_t e_stride, int B, int T, int F, int M, int hop) {
@@ -3940,7 +3878,7 @@ static int check_ss_args(int B, int T, int F, int M, int hop) {
 extern "C" size_t golf_ltv_allpole_workspace_bytes_ex(int B, int T, int F, int M, int hop, int flags) {
     SsPlan p;
     if (B < 1 || T < 1 || F < 1 || M < 1 || hop < 1) return 0;
-    if (!plan_fast(B, T, F, M, hop, &p, flags)) return 256;
+    if (!plan_fast(B, T, F, M, hop, &p, flags)) return any_ws_bytes(B, T);   // no ring plan: the adjoint's g (lpc_any.hip)
     return p.total;
 }
 
@@ -3955,7 +3893,7 @@ extern "C" int golf_ltv_allpole_transitions_f32(const float* a, int B, int T, in
     if (int rc = check_ss_args(B, T, F, M, hop)) return rc;
     if (!a) return fail(GOLF_EINVAL, "ltv_allpole_transitions: null pointer");
     SsPlan p;
-    if (!plan_fast(B, T, F, M, hop, &p, flags)) return GOLF_OK;  // generic path has no transition matrices
+    if (!plan_fast(B, T, F, M, hop, &p, flags)) return GOLF_OK;  // no ring plan (lpc_any.hip): no transition matrices
     if (p.serial) return GOLF_OK;                                 // nor has the batch-parallel serial path
     if (!ws || ws_bytes < p.total || ((uintptr_t)ws & 255))
         return fail(GOLF_EWORKSPACE, "ltv_allpole_transitions: workspace needs %zu bytes, 256-aligned (got %zu)",
@@ -3972,7 +3910,7 @@ extern "C" int golf_ltv_allpole_status_u32(const void* ws, size_t ws_bytes, int 
     if (!out) return fail(GOLF_EINVAL, "ltv_allpole_status: null pointer");
     hipStream_t st = (hipStream_t)stream;
     SsPlan p;
-    // the serial / generic algorithms have no transition matrices: nothing is ever recomputed, all four words are 0
+    // the serial and the wave-per-utterance algorithms have no transition matrices: nothing is recomputed, all four words are 0
     if (!plan_fast(B, T, F, M, hop, &p, flags) || p.serial || p.NP <= 0) {
         hipLaunchKernelGGL(lpc_status_zero_kernel, dim3(1), dim3(64), 0, st, (unsigned*)out);
         GOLF_LAUNCH_CHECK();
@@ -3997,12 +3935,8 @@ extern "C" int golf_ltv_allpole_fwd_f32(const float* ex, int64_t ex_stride, cons
     if (ex_stride < T || y_stride < T) return fail(GOLF_EINVAL, "ltv_allpole_fwd: row stride < T");
     hipStream_t st = (hipStream_t)stream;
     SsPlan p;
-    if (!plan_fast(B, T, F, M, hop, &p, flags)) {
-        hipLaunchKernelGGL(lpc_ss_generic_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, st, ex, ex_stride, gain,
-                           a, y, y_stride, B, T, F, M, hop);
-        GOLF_LAUNCH_CHECK();
-        return GOLF_OK;
-    }
+    if (!plan_fast(B, T, F, M, hop, &p, flags))   // no ring plan for (M, hop, F): one wave per utterance, no workspace
+        return launch_any_fwd(ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, nullptr, st);
     if (p.serial && !serial_strides_ok(ex_stride, y_stride)) {
         if (flags & GOLF_SS_SERIAL) return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd: serial path needs row strides < 2^24");
         plan_fast(B, T, F, M, hop, &p, GOLF_SS_CHUNKED);
@@ -4028,12 +3962,8 @@ extern "C" int golf_ltv_allpole_fwd_state_f32(const float* ex, int64_t ex_stride
     if (ex_stride < T || y_stride < T) return fail(GOLF_EINVAL, "ltv_allpole_fwd_state: row stride < T");
     hipStream_t st = (hipStream_t)stream;
     SsPlan p;
-    if (!make_ss_plan(B, T, F, M, hop, &p, GOLF_SS_SERIAL)) {
-        hipLaunchKernelGGL(lpc_ss_generic_state_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, st, ex, ex_stride, gain,
-                           a, y, y_stride, B, T, F, M, hop, state);
-        GOLF_LAUNCH_CHECK();
-        return GOLF_OK;
-    }
+    if (!make_ss_plan(B, T, F, M, hop, &p, GOLF_SS_SERIAL))
+        return launch_any_fwd(ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state, st);
     if (!serial_strides_ok(ex_stride, y_stride))
         return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd_state: serial path needs row strides < 2^24");
     GOLF_SS_DISPATCH(launch_serial_fwd_state, p, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state, st)
@@ -4050,14 +3980,17 @@ extern "C" int golf_ltv_allpole_bwd_f32(const float* gy, int64_t gy_stride, cons
     if (gy_stride < T || y_stride < T || ex_stride < T || g_ex_stride < T)
         return fail(GOLF_EINVAL, "ltv_allpole_bwd: row stride < T");
     SsPlan p;
-    if (!plan_fast(B, T, F, M, hop, &p, flags))
-        return fail(GOLF_EUNSUPPORTED,
-                    "ltv_allpole_bwd: needs a ring width W in {8,16,24,32,40} with W >= M+1 and hop %% W == 0 "
-                    "(M=%d hop=%d)", M, hop);
+    hipStream_t st = (hipStream_t)stream;
+    if (!plan_fast(B, T, F, M, hop, &p, flags)) {   // no ring plan: adjoint by one wave per utterance, g in the workspace
+        if (!ws || ws_bytes < any_ws_bytes(B, T) || ((uintptr_t)ws & 255))
+            return fail(GOLF_EWORKSPACE, "ltv_allpole_bwd: workspace needs %zu bytes, 256-aligned (got %zu)",
+                        any_ws_bytes(B, T), ws_bytes);
+        return launch_any_bwd(gy, gy_stride, y, y_stride, ex, ex_stride, gain, a, g_ex, g_ex_stride, g_gain, g_a, B, T, F, M,
+                              hop, (char*)ws, (flags & GOLF_SS_ZERO_TAIL) ? g_ex_stride - (int64_t)T : 0, st);
+    }
     if (!ws || ws_bytes < p.total || ((uintptr_t)ws & 255))
         return fail(GOLF_EWORKSPACE, "ltv_allpole_bwd: workspace needs %zu bytes, 256-aligned (got %zu)", p.total,
                     ws_bytes);
-    hipStream_t st = (hipStream_t)stream;
     const int64_t tail64 = (flags & GOLF_SS_ZERO_TAIL) ? g_ex_stride - (int64_t)T : 0;
     if (tail64 > 0x7fffffff) return fail(GOLF_EINVAL, "ltv_allpole_bwd: GOLF_SS_ZERO_TAIL with a row stride beyond 2^31");
     const int tail = (int)tail64;

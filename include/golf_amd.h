@@ -55,6 +55,16 @@ const char* golf_target_arch(void);
  *   y    (B, T)   row stride y_stride       requires 1 <= T <= (F-1)*hop+1, 1 <= M <= 64
  *   ws   scratch of golf_ltv_allpole_workspace_bytes(); it also carries the per-chunk transition
  *        matrices the backward pass reuses — keep it alive (unmodified) until the backward ran.
+ *
+ *   Two families of kernels serve this entry and the three below.  The RING kernels (time-chunked scan, batch-parallel
+ *   serial recursion) need a ring width W in {8,16,24,32,40} with hop % W == 0, M <= W - 2 and F >= 2.  Every other shape
+ *   -- any 1 <= M <= 64, hop >= 1, F >= 1: hop 100 / 220 / 300 / 441, orders 39..64, a single frame -- runs on the
+ *   WAVE-PER-UTTERANCE kernels (csrc/lpc_any.hip): one wavefront per utterance, one lane per tap, the recursion in scatter
+ *   form (a broadcast, a lane shift and an FMA per sample), fp32, 64-bit row addressing (no 2^24 stride limit), about the
+ *   time per sample of GOLF_SS_SERIAL whatever the batch size below the chip's wave slots.  For such a shape the forward
+ *   needs no workspace (ws may be NULL), the GOLF_SS_SERIAL / _CHUNKED / _FLAT_SCAN bits are ignored, the transitions call
+ *   is a no-op and the status words are 0; the backward keeps its intermediate g (B, T) in ws, which
+ *   golf_ltv_allpole_workspace_bytes_ex sizes accordingly.
  * ------------------------------------------------------------------------------------------- */
 size_t golf_ltv_allpole_workspace_bytes(int B, int T, int F, int M, int hop);
 /* The same for a forced algorithm (GOLF_SS_SERIAL / GOLF_SS_CHUNKED in `flags`; 0 = default selection). */
@@ -136,11 +146,12 @@ int golf_ltv_allpole_fwd_f32(const float* ex, int64_t ex_stride, const float* ga
 /* Streaming form (additive in ABI 6): the same recursion, up() interpolation and T <= (F-1)*hop+1 rule, but y[<0] is not 0:
  *   y[b][-1-i] = state[b][i],  state (B, M) fp32 DEVICE buffer, in and out (the oracle's `zi`, sample_wise_lpc(x, A, zi)).
  * On return state[b][i] = y[b][T-1-i], the block's last M outputs (for T < M the old state shifted in behind them), so that
- * the next block continues the recursion.  Always the serial recursion (GOLF_SS_SERIAL: 8 or 4 lanes per utterance by batch
- * size; the generic kernel where no ring fits (M, hop)), and the per-tap summation order does not depend on where a block
+ * the next block continues the recursion.  Always a serial recursion (GOLF_SS_SERIAL: 8 or 4 lanes per utterance by batch
+ * size; where no ring fits (M, hop, F) the wave-per-utterance kernel, which replays the M state values through its update
+ * before the first sample), and the per-tap summation order does not depend on where a block
  * starts: blocks that start on frame boundaries, each given the frames it spans (frame 0 = the frame of its first sample),
- * chained through `state` from zeros, give the same bits as one golf_ltv_allpole_fwd_f32(.., GOLF_SS_SERIAL) over the whole.
- * No workspace; the row strides must stay below 2^24 on the ring path. */
+ * chained through `state` from zeros, give the same bits as one golf_ltv_allpole_fwd_f32(.., GOLF_SS_SERIAL) over the whole
+ * -- on either family of kernels.  No workspace; the row strides must stay below 2^24 on the ring path. */
 int golf_ltv_allpole_fwd_state_f32(const float* ex, int64_t ex_stride, const float* gain, const float* a,
                                    float* y, int64_t y_stride, int B, int T, int F, int M, int hop,
                                    float* state, void* stream);
@@ -160,7 +171,8 @@ int golf_ltv_allpole_fwd_state_f32(const float* ex, int64_t ex_stride, const flo
  *           it (GOLF_SS_FLAT_SCAN / _CHUNKED bits that differ between the two calls): its gradients are void.  Call this
  *           function after the backward to see it.
  *   out[3]  the largest |entry| over all transition matrices of the batch, as the bits of an fp32
- * (B,T,F,M,hop,flags) as given to the forward.  The serial / generic algorithms form no matrices: all four words 0. */
+ * (B,T,F,M,hop,flags) as given to the forward.  The serial and the wave-per-utterance algorithms form no matrices: all four
+ * words 0. */
 int golf_ltv_allpole_status_u32(const void* ws, size_t ws_bytes, int B, int T, int F, int M, int hop, int flags,
                                 uint32_t* out, void* stream);
 
@@ -171,7 +183,11 @@ int golf_ltv_allpole_status_u32(const void* ws, size_t ws_bytes, int B, int T, i
  *     g_gain[f] = up^T(g*ex)[f]         g_a[f,i] = up^T(-g[t]*y[t-1-i])[f,i]
  *   gy,y (B,T) with strides; ws = the forward's workspace (same B,T,F,M,hop); flags = the forward's
  *   GOLF_SS_SERIAL / GOLF_SS_CHUNKED bits (ABI 2);
- *   g_ex (B,T) stride g_ex_stride, g_gain (B,F), g_a (B,F,M) are fully overwritten. */
+ *   g_ex (B,T) stride g_ex_stride, g_gain (B,F), g_a (B,F,M) are fully overwritten.
+ *   Shapes without a ring (see above): the reverse-time recursion runs in the transposed form, lam_k = fma(-A[t,k], g[t],
+ *   lam_{k+1}), one wave per utterance, into ws; one workgroup per (utterance, frame) then forms g_ex and the hat-weighted
+ *   correlations in a fixed order -- no atomics, the gradients are bit-reproducible.  GOLF_EWORKSPACE when ws is smaller than
+ *   golf_ltv_allpole_workspace_bytes_ex(B,T,F,M,hop,flags); M > 64 stays GOLF_EUNSUPPORTED. */
 int golf_ltv_allpole_bwd_f32(const float* gy, int64_t gy_stride, const float* y, int64_t y_stride,
                              const float* ex, int64_t ex_stride, const float* gain, const float* a,
                              float* g_ex, int64_t g_ex_stride, float* g_gain, float* g_a,
