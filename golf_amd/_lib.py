@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_ff.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
+SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
            "stft_filter.hip")
 
 _c_f32p = ctypes.c_void_p

@@ -59,4 +59,11 @@ int launch_any_bwd(const float* gy, int64_t gy_stride, const float* y, int64_t y
                    const float* gain, const float* a, float* g_ex, int64_t g_ex_stride, float* g_gain, float* g_a, int B, int T,
                    int F, int M, int hop, char* ws, int64_t tail, hipStream_t st);
 
+// ---- frame-wise filter for the shapes the ring chain does not serve (lpc_ff_any.hip): any 1 <= M <= 64, hop >= 1, W >= 1 ----
+// rev == false: x = ex (B rows of Tx, stride x_stride), wf <- y_f;  rev == true: x = g_q (Tx = Ty), wf <- u_f.  wf (B, nfr, W)
+int launch_ff_any_frames(bool rev, const float* x, int64_t x_stride, const float* gain, const float* a, const float* window,
+                         float* wf, int B, int Tx, int F, int M, int hop, int W, int nfr, hipStream_t st);
+// g_a (B, F, M) fully written (zeros for the frames >= nfr) from u_f and y_f (B, nfr, W)
+int launch_ff_any_grad_a(const float* uf, const float* yf, float* g_a, int B, int F, int M, int W, int nfr, hipStream_t st);
+
 }  // namespace golf

@@ -15,8 +15,13 @@
 //           LTI all-pole filter is the filter itself applied to the time-reversed signal)
 //       B2  g_a[f,i] = -sum_k u_f[k] * y_f[k-1-i]   (one wave per frame)
 //       B3  g_x = overlap-add of the u_f; g_ex = g_x * G; hat-weighted partial sums of g_x * ex -> g_gain
+// The recursion kernels here need a ring width w in {8,16,24,32,40} with M <= w - 2 and w <= hop (and B1 / B2 a window that is
+// a multiple of w); F1, B1 and B2 of every other shape -- orders 39 .. 64, hops below the ring width, other windows in the
+// backward -- are the wave-per-frame kernels of lpc_ff_any.hip, between the same F2, B0 and B3.
 #include "common.h"
 #include "device_common.h"
+
+#include <climits>
 
 namespace golf {
 
@@ -779,14 +784,21 @@ static bool ff_block_ok(int Wl, int hop, size_t lds_bytes) {
     return Wl % 32 == 0 && hop % 4 == 0 && lds_bytes <= 56 * 1024;
 }
 
+// W > 0: the ring chain (quad adjoint + wave-per-frame g_a) where the window is a multiple of the ring width W and the g_a
+// kernel's LDS rows (two whole frames per wave, four waves) fit the 64 KB a launch gets without asking for more -- past
+// W ~ 2030 they do not; every other window, and W == 0 (no ring for this order and hop), takes the adjoint and the g_a
+// kernel of lpc_ff_any.hip between the same B0 / B3 kernels.
 template <int W, int NT>
 static int launch_ff_bwd(const float* gy, int64_t gy_stride, const float* ex, int64_t ex_stride, const float* gain,
                          const float* a, const float* window, float* g_ex, int64_t g_ex_stride, float* g_gain,
                          float* g_a, int B, int Tx, int Tfull, int F, int M, int hop, int Wl, int Ty, int nfr,
                          const float* yf, char* ws, hipStream_t st, int g_ex_len) {
-    if (Wl % W != 0 || (int64_t)nfr * Wl >= (1ll << 29) || Wl > 16384)
-        return fail(GOLF_EUNSUPPORTED, "lti_frames_bwd: window length %d must be a multiple of the ring width %d "
-                    "(and <= 16384)", Wl, W);
+    bool ring = false;
+    if constexpr (W > 0)
+        ring = Wl % W == 0 && (int64_t)nfr * Wl < (1ll << 29) && Wl <= 16384 &&
+               4 * sizeof(float) * (2 * (size_t)Wl + NT + 8) <= 64 * 1024;
+    if (!ring && (int64_t)B * F > INT_MAX)
+        return fail(GOLF_EUNSUPPORTED, "lti_frames_bwd: B*F=%lld beyond 2^31", (long long)B * F);
     const FfBwdPlan p = ff_bwd_plan(B, F, Wl, nfr, Ty);
     float* gq = (float*)(ws + p.off_gq);
     float* uf = (float*)(ws + p.off_uf);
@@ -795,17 +807,27 @@ static int launch_ff_bwd(const float* gy, int64_t gy_stride, const float* ex, in
     hipLaunchKernelGGL(ff_gq_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, gy, gy_stride, window, gq, B,
                        Ty, hop, Wl, nfr);
     GOLF_LAUNCH_CHECK();
-    // the adjoint stays on the quad kernel: the block recursion's adjoint (ff_framesb_kernel<NT, true>) stages 4 whole frames
-    // of window * g_q per wave instead of their union and measured 56 us against the quads' 45 at B = 32
-    hipLaunchKernelGGL((ff_framesq_kernel<W, NT, true>), dim3((unsigned)ceil_div(nfr, 16), B), dim3(64),
-                       sizeof(float) * (size_t)Wl, st, (const float*)gq, (int64_t)Ty, gain, a, window, uf, Ty, F, M,
-                       hop, Wl, nfr);
-    GOLF_LAUNCH_CHECK();
-    const int nq = B * F;
-    const int RS = 2 * Wl + NT + 8;
-    hipLaunchKernelGGL((ff_grad_a_kernel<NT>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), 4 * RS * sizeof(float), st,
-                       (const float*)uf, yf, g_a, F, M, Wl, nfr, nq, RS);
-    GOLF_LAUNCH_CHECK();
+    if constexpr (W > 0) {
+        if (ring) {
+            // the adjoint stays on the quad kernel: the block recursion's adjoint (ff_framesb_kernel<NT, true>) stages 4 whole
+            // frames of window * g_q per wave instead of their union and measured 56 us against the quads' 45 at B = 32
+            hipLaunchKernelGGL((ff_framesq_kernel<W, NT, true>), dim3((unsigned)ceil_div(nfr, 16), B), dim3(64),
+                               sizeof(float) * (size_t)Wl, st, (const float*)gq, (int64_t)Ty, gain, a, window, uf, Ty, F, M,
+                               hop, Wl, nfr);
+            GOLF_LAUNCH_CHECK();
+            const int nq = B * F;
+            const int RS = 2 * Wl + NT + 8;
+            hipLaunchKernelGGL((ff_grad_a_kernel<NT>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), 4 * RS * sizeof(float), st,
+                               (const float*)uf, yf, g_a, F, M, Wl, nfr, nq, RS);
+            GOLF_LAUNCH_CHECK();
+        }
+    }
+    if (!ring) {
+        int rc = launch_ff_any_frames(true, gq, Ty, gain, a, window, uf, B, Ty, F, M, hop, Wl, nfr, st);
+        if (rc != GOLF_OK) return rc;
+        rc = launch_ff_any_grad_a(uf, yf, g_a, B, F, M, Wl, nfr, st);
+        if (rc != GOLF_OK) return rc;
+    }
     hipLaunchKernelGGL(ff_bwd_ola_kernel, dim3((unsigned)(F - 1), B), dim3(256), 0, st, (const float*)uf, ex,
                        ex_stride, gain, g_ex, g_ex_stride, part, Tx, Tfull, F, hop, Wl, nfr, g_ex_len);
     GOLF_LAUNCH_CHECK();
@@ -841,6 +863,21 @@ static int launch_ff(const float* ex, int64_t ex_stride, const float* gain, cons
                            gain, a, window, wf, Tx, F, M, hop, Wl, nfr, nq);
     }
     GOLF_LAUNCH_CHECK();
+    const int64_t n = (int64_t)B * Ty;
+    hipLaunchKernelGGL(ff_ola_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, (const float*)wf, window, y,
+                       y_stride, B, Ty, hop, Wl, nfr, Wl / 2);
+    GOLF_LAUNCH_CHECK();
+    return GOLF_OK;
+}
+
+// No ring for this order and hop (M in 39 .. 64, or hop below the ring width M needs): one wave per frame (lpc_ff_any.hip),
+// then the same overlap-add.
+static int launch_ff_any(const float* ex, int64_t ex_stride, const float* gain, const float* a, const float* window,
+                         float* y, int64_t y_stride, int B, int Tx, int F, int M, int hop, int Wl, int Ty, int nfr,
+                         float* wf, hipStream_t st) {
+    if ((int64_t)B * nfr > INT_MAX) return fail(GOLF_EUNSUPPORTED, "lti_frames: B*frames=%lld beyond 2^31", (long long)B * nfr);
+    const int rc = launch_ff_any_frames(false, ex, ex_stride, gain, a, window, wf, B, Tx, F, M, hop, Wl, nfr, st);
+    if (rc != GOLF_OK) return rc;
     const int64_t n = (int64_t)B * Ty;
     hipLaunchKernelGGL(ff_ola_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, (const float*)wf, window, y,
                        y_stride, B, Ty, hop, Wl, nfr, Wl / 2);
@@ -894,7 +931,8 @@ extern "C" int golf_lti_frames_ola_fwd_f32(const float* ex, int64_t ex_stride, c
     GOLF_FF_TRY(32, 30)
     GOLF_FF_TRY(40, 38)
 #undef GOLF_FF_TRY
-    return fail(GOLF_EUNSUPPORTED, "lti_frames: need M <= 38 and hop >= ring width (M=%d hop=%d)", M, hop);
+    if (M <= 64) return launch_ff_any(ex, ex_stride, gain, a, window, y, y_stride, B, Tx, F, M, hop, W, Ty, nfr, wf, st);
+    return fail(GOLF_EUNSUPPORTED, "lti_frames: need M <= 64 (M=%d)", M);
 }
 
 extern "C" size_t golf_lti_frames_bwd_workspace_bytes(int B, int Tx, int F, int M, int hop, int W) {
@@ -939,7 +977,10 @@ extern "C" int golf_lti_frames_ola_bwd_f32(const float* gy, int64_t gy_stride, c
     GOLF_FF_TRY(32, 30)
     GOLF_FF_TRY(40, 38)
 #undef GOLF_FF_TRY
-    return fail(GOLF_EUNSUPPORTED, "lti_frames_bwd: need M <= 38 and hop >= ring width (M=%d hop=%d)", M, hop);
+    if (M <= 64)
+        return launch_ff_bwd<0, 0>(gy, gy_stride, ex, ex_stride, gain, a, window, g_ex, g_ex_stride, g_gain, g_a, B, Tx, Tfull,
+                                   F, M, hop, W, Ty, nfr, (const float*)ws_fwd, (char*)ws, st, g_ex_len);
+    return fail(GOLF_EUNSUPPORTED, "lti_frames_bwd: need M <= 64 (M=%d)", M);
 }
 
 // ---- backward of the cascade (the reference is differentiable through its K lfilter calls,

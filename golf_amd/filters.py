@@ -159,7 +159,10 @@ class LTVMinimumPhaseFilterPrecise(LTVFilterInterface):
 class LTVMinimumPhaseFilter(LTVMinimumPhaseFilterPrecise):
     """GOLF-ff end filter: per-frame LTI all-pole + windowed overlap-add
     (reference models/filters.py:116-184); custom backward w.r.t. ex, gain and a
-    (golf_lti_frames_ola_{fwd,bwd}_f32)."""
+    (golf_lti_frames_ola_{fwd,bwd}_f32).  Runs and trains at any ``lpc_order`` up to 64, any hop and any even
+    ``window_length >= 2*hop``: the recipe shapes (order <= 38, hop >= the ring width above the order, window a multiple of
+    it) on the ring kernels, every other shape on the wave-per-frame kernels (``functional.ff_on_ring_grid``).  The
+    streaming form (``stream.py``) keeps order <= 38."""
 
     def prefetch(self, *args, **kwargs) -> None:  # the frame-wise filter has no excitation-independent phase
         return None

@@ -365,6 +365,28 @@ def ff_output_length(Tx: int, F: int, hop: int, W: int):
     return Tx, nfr, Ty
 
 
+# (ring width, largest order it serves) of the frame-wise filter's ring kernels (csrc/lpc_ff.hip GOLF_FF_TRY): the first ring
+# with M <= order whose width fits into one hop.  Every other shape runs -- and trains -- on the wave-per-frame kernels of
+# csrc/lpc_ff_any.hip.
+FF_RINGS = SS_RINGS
+
+
+def ff_on_ring_grid(M: int, hop: int, W: int = None, backward: bool = False) -> bool:
+    """True when the frame-wise filter runs (lpc order, hop) -- for ``backward=True``: differentiates (lpc order, hop, window
+    length W) -- on the ring kernels of csrc/lpc_ff.hip; False: the wave-per-frame kernels of csrc/lpc_ff_any.hip (any
+    1 <= M <= 64, hop >= 1).  The forward has a ring kernel for every window; the backward's ring chain needs a window that
+    is a multiple of the ring width, and short enough (about 2030 samples) for its g_a kernel to stage two whole frames per
+    wave in LDS.  Restates the routing of golf_lti_frames_ola_{fwd,bwd}_f32 for tools and tests."""
+    ring = next((ring for ring, order in FF_RINGS if M <= order and ring <= hop), None)
+    if ring is None:
+        return False
+    if not backward:
+        return True
+    if W is None:
+        raise ValueError("ff_on_ring_grid(backward=True) needs the window length")
+    return W % ring == 0 and 16 * (2 * W + ring + 6) <= 64 * 1024
+
+
 class _LTIFramesOLA(torch.autograd.Function):
     @staticmethod
     @_amp_fwd
@@ -414,6 +436,9 @@ class _LTIFramesOLA(torch.autograd.Function):
 
 
 def lti_frames_ola(ex, gain, a, window, hop: int) -> torch.Tensor:
+    """Frame-wise LTI all-pole filter + windowed overlap-add (include/golf_amd.h a-4): ex (B, Tx), gain (B, F), a (B, F, M),
+    window (W,), W even and >= 2*hop; differentiable w.r.t. ex, gain and a.  Any order 1 <= M <= 64 and any hop >= 1: the
+    ring kernels where ``ff_on_ring_grid`` holds, one wave per frame elsewhere; M > 64 raises GolfError."""
     return _LTIFramesOLA.apply(ex, gain, a, window, int(hop))
 
 

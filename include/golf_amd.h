@@ -215,7 +215,12 @@ int golf_ltv_inverse_bwd_f32(const float* g_e, int64_t g_e_stride, const float* 
  *   y[n] = sum_f window[k]*filt_f[k] / sum_f window[k],  n = f*hop - W/2 + k,  n in [0, Ty),
  *   Ty = (nfr-1)*hop + W - 2*(W/2).
  *   window (W) fp32; requires W >= 2*hop.  `centred==0` handling (drop hop/2, reflect pad) is done
- *   by the host wrapper.  ws: golf_lti_frames_workspace_bytes(). */
+ *   by the host wrapper.  ws: golf_lti_frames_workspace_bytes().
+ *   Shapes: any order 1 <= M <= 64, any hop >= 1, any even W >= 2*hop (M > 64: GOLF_EUNSUPPORTED).  Where a ring width
+ *   w in {8,16,24,32,40} has M <= w - 2 and w <= hop, the frames run on the ring kernels of lpc_ff.hip (the block
+ *   recursion for M <= 22, W % 32 == 0, hop % 4 == 0; the quad kernel for W % w == 0; a lane per frame otherwise); every
+ *   other shape (M in 39 .. 64, or hop below the ring width M needs) runs one wave per frame with one lane per tap
+ *   (lpc_ff_any.hip).  The overlap-add is the same kernel for all of them. */
 size_t golf_lti_frames_workspace_bytes(int B, int Tx, int F, int M, int hop, int W);
 
 int golf_lti_frames_ola_fwd_f32(const float* ex, int64_t ex_stride, const float* gain, const float* a,
@@ -285,7 +290,10 @@ int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stride, int64_t
  *   ws_fwd = the forward's workspace, unmodified (it holds the filtered frames y_f);
  *   ws     = scratch of golf_lti_frames_bwd_workspace_bytes();
  *   g_ex (B, g_ex_len >= Tx) is fully written (zeros past Tx and past sample (F-1)*hop: ABI 5); g_gain (B,F) and
- *   g_a (B,F,M) are fully overwritten.  Requires W % ring width == 0 (the fast path of the forward). */
+ *   g_a (B,F,M) are fully overwritten.  Any shape the forward accepts: the ring chain (quad adjoint, wave-per-frame g_a)
+ *   where a ring exists, W % ring width == 0 and the g_a kernel's LDS rows fit (16*(2*W + ring + 6) <= 65536 bytes); the
+ *   wave-per-frame adjoint and the tiled g_a kernel of lpc_ff_any.hip everywhere else.  Every sum runs in a fixed order on
+ *   both chains: the gradients are bit-reproducible. */
 size_t golf_lti_frames_bwd_workspace_bytes(int B, int Tx, int F, int M, int hop, int W);
 int golf_lti_frames_ola_bwd_f32(const float* gy, int64_t gy_stride, const float* ex, int64_t ex_stride,
                                 const float* gain, const float* a, const float* window, float* g_ex,
