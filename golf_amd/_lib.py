@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
+SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
            "stft_filter.hip")
 
 _c_f32p = ctypes.c_void_p
@@ -38,6 +38,9 @@ SIGNATURES = {
     "golf_ltv_allpole_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 5
                                  + [_vp, _sz, _int, _vp, _vp]),
     "golf_ltv_allpole_fwd_state_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 5 + [_c_f32p, _vp]),
+    "golf_ltv_allpole_head_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 5 + [_vp]),
+    "golf_ltv_allpole_head_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64, _int,
+                                             _c_f32p, _c_f32p, _c_f32p] + [_int] * 5 + [_vp]),
     "golf_ltv_allpole_status_u32": (_int, [_vp, _sz] + [_int] * 6 + [_vp, _vp]),
     "golf_ltv_allpole_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64,
                                         _c_f32p, _c_f32p] + [_int] * 5 + [_vp, _sz, _int, _vp]),

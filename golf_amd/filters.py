@@ -127,7 +127,10 @@ class LTVMinimumPhaseFilterPrecise(LTVFilterInterface):
                 warnings.warn(f"golf_amd: sample-wise LPC filter reported {', '.join(bad)} (status {w})", RuntimeWarning)
         return getattr(self, "_health_last", None)
 
-    def forward(self, ex: AudioTensor, gain: AudioTensor, a: AudioTensor) -> AudioTensor:
+    def forward(self, ex: AudioTensor, gain: AudioTensor, a: AudioTensor, zi: Tensor = None, return_zf: bool = False):
+        """``zi``: optional initial state, a plain (B, M) tensor with y[b, -1-j] = zi[b, j]; ``return_zf=True`` returns
+        ``(AudioTensor, zf)`` with zf (B, M) the final state -- the ``zi`` of the segment that follows, differentiable
+        (not in the reference module; torchlpc.sample_wise_lpc's ``zi``).  Without them: the reference's call."""
         hop = _check_filter_inputs(ex, gain, a)
         prepared, self._prepared = getattr(self, "_prepared", None), None
         x = ex.as_tensor()
@@ -135,7 +138,10 @@ class LTVMinimumPhaseFilterPrecise(LTVFilterInterface):
         if self.health_check and x.is_cuda and not torch.cuda.is_current_stream_capturing():
             self.health()
             st = torch.zeros(4, dtype=torch.int32, device=x.device)
-        y = GF.ltv_allpole_ss(x, gain.as_tensor(), a.as_tensor(), hop, prepared, status=st)
+        if zi is None and not return_zf:
+            y = GF.ltv_allpole_ss(x, gain.as_tensor(), a.as_tensor(), hop, prepared, status=st)
+        else:
+            y, zf = GF.ltv_allpole_ss(x, gain.as_tensor(), a.as_tensor(), hop, prepared, status=st, zi=zi, return_zf=True)
         if st is not None:
             host = torch.empty(4, dtype=torch.int32, pin_memory=True)
             host.copy_(st, non_blocking=True)
@@ -145,6 +151,8 @@ class LTVMinimumPhaseFilterPrecise(LTVFilterInterface):
             q.append((host, ev))
             if len(q) > 64:      # (a caller that never comes back to look: keep the newest)
                 del q[0]
+        if return_zf:
+            return AudioTensor(y), zf
         return AudioTensor(y)
 
     def reverse(self, ex: AudioTensor, y: AudioTensor, gain: AudioTensor, a: AudioTensor

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["ltv_allpole_ss", "ltv_allpole_prepare", "ltv_inverse", "lti_frames_ola", "glottal_osc",
+__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lti_frames_ola", "glottal_osc",
            "ss_output_length", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
            "zero_phase_fir_filter_precise",
@@ -219,6 +219,48 @@ class _LTVAllPoleSS(torch.autograd.Function):
         return g_ex, g_gain, g_a, None, None, None, None, None, None
 
 
+class _LTVAllPoleHead(torch.autograd.Function):
+    """xh = ex*up(gain) - c, c the part of the first min(M, T) samples' recursion that reads the initial state ``zi`` (B, M)
+    (golf_ltv_allpole_head_{fwd,bwd}_f32): the zero-state filter of xh with gain == 1 IS the filter of ex from zi."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, ex, gain, a, zi, hop, T):
+        _lib.require_device(ex, gain, a, zi)
+        lib = _lib.load()
+        ex = _rows(ex)
+        gain, a, zi = gain.contiguous(), a.contiguous(), zi.contiguous()
+        B, F, M = a.shape
+        assert ex.shape[0] == B and gain.shape == (B, F) and zi.shape == (B, M) and 1 <= T <= ex.shape[1]
+        xh = torch.empty(B, T, dtype=torch.float32, device=ex.device)
+        rc = lib.golf_ltv_allpole_head_fwd_f32(ex.data_ptr(), ex.stride(0), gain.data_ptr(), a.data_ptr(), zi.data_ptr(),
+                                               xh.data_ptr(), xh.stride(0), B, T, F, M, hop, _lib.stream_ptr())
+        _lib.check(rc, "golf_ltv_allpole_head_fwd_f32")
+        ctx.hop = hop
+        ctx.save_for_backward(ex, gain, a, zi)
+        return xh
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, q):
+        ex, gain, a, zi = ctx.saved_tensors
+        lib = _lib.load()
+        B, Tx = ex.shape
+        F, M = a.shape[1], a.shape[2]
+        q = _rows(q.float())
+        T = q.shape[1]
+        want_ex, want_gain, want_a, want_zi = ctx.needs_input_grad[:4]
+        g_ex = torch.empty(B, Tx, dtype=torch.float32, device=ex.device) if want_ex else None
+        g_gain = torch.empty_like(gain) if want_gain else None
+        g_a = torch.empty_like(a) if want_a else None
+        g_zi = torch.empty_like(zi) if want_zi else None
+        rc = lib.golf_ltv_allpole_head_bwd_f32(q.data_ptr(), q.stride(0), ex.data_ptr(), ex.stride(0), gain.data_ptr(),
+                                               a.data_ptr(), zi.data_ptr(), _lib.ptr(g_ex), Tx, Tx, _lib.ptr(g_gain),
+                                               _lib.ptr(g_a), _lib.ptr(g_zi), B, T, F, M, ctx.hop, _lib.stream_ptr())
+        _lib.check(rc, "golf_ltv_allpole_head_bwd_f32")
+        return g_ex, g_gain, g_a, g_zi, None, None
+
+
 SS_MODES = {None: 0, "auto": 0, "serial": 8, "chunked": 16, "flat-scan": 16 | 32}   # GOLF_SS_SERIAL / _CHUNKED / _FLAT_SCAN
 # Set by a caller that keeps several batches in flight (bench.py's pipelined loop, a serving loop): GOLF_SS_THROUGHPUT
 # is added to every sample-wise filter call.  Bit-identical results WITHIN one algorithm (the flag only changes the launch
@@ -239,7 +281,8 @@ SS_SERIAL_MAX_STRIDE = 1 << 24   # the serial kernels address 16 rows through on
 
 def ltv_allpole_ss(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: int,
                    prepared: "PreparedTransitions" = None, fast_inference: bool = True,
-                   mode: str = None, status: torch.Tensor = None, length: int = None) -> torch.Tensor:
+                   mode: str = None, status: torch.Tensor = None, length: int = None,
+                   zi: torch.Tensor = None, return_zf: bool = False):
     """y[t] = ex[t]*up(gain)[t] - sum_i up(a)[t,i] y[t-1-i]; ex (B,Tx), gain (B,F), a (B,F,M) at hop.
     Output (B, min(Tx,(F-1)*hop+1)).  Differentiable w.r.t. ex, gain, a (custom HIP backward).
     ``prepared``: handle from ltv_allpole_prepare(a, hop, T) (ignored if it does not match).
@@ -259,7 +302,19 @@ def ltv_allpole_ss(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: i
     own backward, GOLF_SS_ZERO_TAIL).
     ``status``: optional int32 device tensor of >= 4 elements that receives, asynchronously, the conditioning / health
     words of this call (decode with ss_status): utterances with recomputed chunk maps, utterances on the fp64 boundary
-    scan, non-finite output flag, largest transition-matrix entry."""
+    scan, non-finite output flag, largest transition-matrix entry.
+    ``zi``: initial state (B, M) fp32, y[b, -1-j] = zi[b, j] (torchlpc.sample_wise_lpc's ``zi``); None = zeros, and then the
+    call is exactly the one without the argument: same launches, same bits.  With ``zi`` the state enters as a correction of
+    the first min(M, T) excitation samples (golf_ltv_allpole_head_fwd_f32) in front of the same filter, so every plan and every
+    ``mode`` serves it, and the result is differentiable w.r.t. ``zi`` as well.
+    ``return_zf``: return ``(y, zf)`` with zf (B, M) the final state, zf[b, j] = y[b, T-1-j] (for T < M the initial state
+    shifted in behind the T outputs): the ``zi`` of the block that follows.  It stays in the graph, so a chain of blocks is
+    differentiable through the state (ltv_allpole_ss_blocks)."""
+    if zi is not None:
+        if zi.dim() != 2 or a.dim() != 3 or tuple(zi.shape) != (a.shape[0], a.shape[2]):
+            raise _lib.GolfError(f"ltv_allpole_ss: zi {tuple(zi.shape)} for a {tuple(a.shape)}: a (B, M) initial state required")
+        if zi.device != ex.device or not zi.is_floating_point() or (zi.dtype != torch.float32 and not torch.is_autocast_enabled()):
+            raise _lib.GolfError(f"ltv_allpole_ss: zi must be an fp32 tensor on {ex.device} (got {zi.dtype} on {zi.device})")
     if ex.dim() == 2 and (ex.shape[0] == 0 or ex.shape[1] == 0):
         # an empty batch / zero samples: what the reference's tensor ops return (an empty result that stays in the graph);
         # the C ABI itself rejects non-positive sizes
@@ -267,8 +322,75 @@ def ltv_allpole_ss(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: i
         T = ss_output_length(ex.shape[1], a.shape[1], int(hop)) if ex.shape[1] else 0
         if length is not None:
             T = min(T, max(int(length), 0))
-        return ex[:, :T] * 1.0 + 0.0 * (gain.sum() + a.sum())
-    return _LTVAllPoleSS.apply(ex, gain, a, int(hop), prepared, bool(fast_inference), SS_MODES[mode], status, length)
+        y = ex[:, :T] * 1.0 + 0.0 * (gain.sum() + a.sum())
+        return (y, _final_state(y, zi, a.shape[2])) if return_zf else y
+    if zi is None:
+        y = _LTVAllPoleSS.apply(ex, gain, a, int(hop), prepared, bool(fast_inference), SS_MODES[mode], status, length)
+    else:
+        T = ss_output_length(ex.shape[1], a.shape[1], int(hop))
+        if length is not None:
+            T = min(T, int(length))
+            if T < 1:
+                raise _lib.GolfError(f"ltv_allpole_ss: length={length} leaves nothing to filter")
+        xh = _LTVAllPoleHead.apply(ex, gain, a, zi, int(hop), T)
+        # (the maps of `prepared`, the mode and the status words depend on `a` alone: they pass through)
+        y = _LTVAllPoleSS.apply(xh, torch.ones_like(gain, dtype=torch.float32), a, int(hop), prepared, bool(fast_inference),
+                                SS_MODES[mode], status, length)
+    return (y, _final_state(y, zi, a.shape[2])) if return_zf else y
+
+
+def _final_state(y: torch.Tensor, zi, M: int) -> torch.Tensor:
+    """zf (B, M): zf[:, j] = y[:, T-1-j] for j < T, the initial state shifted by T behind them.  Plain indexing: autograd adds
+    the cotangent of zf into y's (and zi's) by itself."""
+    T = y.shape[1]
+    if T >= M:
+        return y[:, T - M:].flip(1)
+    old = zi[:, :M - T].to(y.dtype) if zi is not None else y.new_zeros(y.shape[0], M - T)
+    return torch.cat([y.flip(1), old], 1)
+
+
+def ltv_allpole_ss_blocks(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: int, frames_per_block: int,
+                          zi: torch.Tensor = None, detach_state: bool = False, length: int = None, **kw):
+    """ltv_allpole_ss over blocks of ``frames_per_block`` frames chained through the state: returns ``(y, zf)``, y what the
+    one-shot call returns (up to fp32 rounding: a block's plan sees another utterance length) and zf (B, M) the final state.
+    Block k filters the samples [k*n*hop, (k+1)*n*hop), n = frames_per_block, with the frames k*n .. (k+1)*n (a block needs
+    the frame that ends it for the interpolation); the last block ends with the utterance, sample (F-1)*hop included.
+    ``detach_state=True`` cuts the gradient at every block boundary (truncated back-propagation through time): same y.
+    ``zi``: the state in front of the first block.  ``**kw``: fast_inference / mode / status of ltv_allpole_ss."""
+    hop, n = int(hop), int(frames_per_block)
+    if n < 1:
+        raise _lib.GolfError(f"ltv_allpole_ss_blocks: frames_per_block={frames_per_block} must be >= 1")
+    if "prepared" in kw or "return_zf" in kw:
+        raise _lib.GolfError("ltv_allpole_ss_blocks: `prepared` / `return_zf` do not apply to a chain of blocks")
+    F = a.shape[1]
+    T = ss_output_length(ex.shape[1], F, hop)
+    if length is not None:
+        T = min(T, max(int(length), 0))
+    if ex.shape[0] == 0 or T == 0:
+        return ltv_allpole_ss(ex, gain, a, hop, length=length, zi=zi, return_zf=True, **kw)
+    parts, state = [], zi
+    for f0, f1, t0, t1 in ss_block_bounds(T, F, hop, n):
+        y, state = ltv_allpole_ss(ex[:, t0:t1], gain[:, f0:f1 + 1], a[:, f0:f1 + 1], hop, zi=state, return_zf=True, **kw)
+        parts.append(y)
+        if detach_state:
+            state = state.detach()
+    return (parts[0] if len(parts) == 1 else torch.cat(parts, 1)), state
+
+
+def ss_block_bounds(T: int, F: int, hop: int, frames_per_block: int):
+    """[(f0, f1, t0, t1)] of ltv_allpole_ss_blocks: block k takes the frames f0 .. f1 inclusive and the samples [t0, t1) of an
+    utterance of T <= (F-1)*hop+1 output samples.  Blocks start on frame boundaries; only the last one holds the sample that
+    ends its last frame; frames past the T-th sample get no block."""
+    if F == 1:
+        return [(0, 0, 0, min(T, 1))]
+    out = []
+    for f0 in range(0, F - 1, frames_per_block):
+        f1 = min(f0 + frames_per_block, F - 1)
+        t0, t1 = f0 * hop, min(f1 * hop + (1 if f1 == F - 1 else 0), T)
+        if t0 >= T:
+            break
+        out.append((f0, f1, t0, t1))
+    return out
 
 
 def _inference_only(what: str, *tensors) -> None:
@@ -276,12 +398,25 @@ def _inference_only(what: str, *tensors) -> None:
         raise NotImplementedError(f"golf_amd: {what} is inference only (an input requires grad)")
 
 
-def ltv_allpole_ss_state(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: int, state: torch.Tensor) -> torch.Tensor:
+def ltv_allpole_ss_state(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: int, state: torch.Tensor,
+                         mode: str = "serial") -> torch.Tensor:
     """ltv_allpole_ss from a carried state (golf_ltv_allpole_fwd_state_f32): y[b, -1-i] = state[b, i],
     output (B, min(Tx, (F-1)*hop+1)); ``state`` (B, M) fp32 is updated in place to the block's last M outputs.  Inference only.
-    Always the serial recursion: blocks that start on frame boundaries, chained through ``state`` from zeros, give the bits of
-    ``ltv_allpole_ss(..., mode="serial")`` over the whole."""
+    ``mode="serial"`` (the default) is always the serial recursion: blocks that start on frame boundaries, chained through
+    ``state`` from zeros, give the bits of ``ltv_allpole_ss(..., mode="serial")`` over the whole.  Any other ``mode`` of
+    ltv_allpole_ss (None / "auto", "chunked", "flat-scan") runs ``ltv_allpole_ss(zi=state, return_zf=True)`` on that plan --
+    the fast ones for long blocks -- and copies the final state into ``state``: the same accuracy class, but ONLY "serial"
+    gives bits that do not depend on where the blocks are cut.  For a state that carries gradients call ltv_allpole_ss(zi=...)
+    itself."""
     _inference_only("ltv_allpole_ss_state", ex, gain, a)
+    if mode != "serial":
+        if tuple(state.shape) != (a.shape[0], a.shape[2]) or not state.is_contiguous():
+            raise _lib.GolfError(f"ltv_allpole_ss_state: a {tuple(a.shape)}, state {tuple(state.shape)} "
+                                 "(contiguous (B, M) required)")
+        with torch.no_grad():
+            y, zf = ltv_allpole_ss(ex, gain, a, hop, mode=mode, zi=state, return_zf=True)
+            state.copy_(zf)
+        return y
     ex, gain, a = _rows(ex.float()), gain.float().contiguous(), a.float().contiguous()   # (autocast: fp16/bf16 tracks first)
     _lib.require_device(ex, gain, a, state)
     B, Tx = ex.shape

@@ -156,6 +156,34 @@ int golf_ltv_allpole_fwd_state_f32(const float* ex, int64_t ex_stride, const flo
                                    float* y, int64_t y_stride, int B, int T, int F, int M, int hop,
                                    float* state, void* stream);
 
+/* Initial state on every plan (additive in ABI 6).  A filter that starts from y[b][-1-j] = zi[b][j] is EXACTLY the zero-state
+ * filter of an excitation whose first H = min(M, T) samples carry a correction, so golf_ltv_allpole_fwd_f32 / _bwd_f32 serve an
+ * initial state on whichever plan they pick (time-chunked scan with its conditioning tiers, merged pass, serial, wave per
+ * utterance) around these two memory-bound calls:
+ *     c[t]  = sum_{i=t}^{M-1} A[t,i]*zi[i-t]            (t < H, else 0)
+ *     xh[t] = ex[t]*G[t] - c[t]                          (0 <= t < T)
+ *     y     = golf_ltv_allpole_fwd_f32(xh, gain == 1, a) ;   final state zf[j] = y[T-1-j] (j < T), zi[j-T] (j >= T)
+ * The gain is applied here and never divided out of the head: it may hold an exact 0.
+ *   ex (B, >=T) stride ex_stride   gain (B,F)   a (B,F,M)   zi (B,M)   xh (B,T) stride xh_stride, fully written
+ *   1 <= T <= (F-1)*hop+1, 1 <= M <= 64.  One launch, no workspace.  A lane moves 4 consecutive samples with 16-byte accesses
+ *   where the row address allows it (rows may be strided views with any start offset). */
+int golf_ltv_allpole_head_fwd_f32(const float* ex, int64_t ex_stride, const float* gain, const float* a, const float* zi,
+                                  float* xh, int64_t xh_stride, int B, int T, int F, int M, int hop, void* stream);
+
+/* Backward of the head (additive in ABI 6).  q (B, >=T) is what golf_ltv_allpole_bwd_f32 returned as g_ex for xh (gain == 1:
+ * the reverse-time recursion g itself):
+ *     g_ex[t]       = q[t]*G[t] (t < T), 0 (T <= t < Tx)         g_ex (B,Tx) stride g_ex_stride, fully written
+ *     g_gain[f]     = up^T(q*ex)[f]                              (B,F)
+ *     g_a_head[f,i] = up^T(-q[t]*zi[i-t])[f,i], t < H, i >= t    (B,F,M), zeros outside the head's frames; ADD it to the g_a
+ *                                                                of golf_ltv_allpole_bwd_f32
+ *     g_zi[j]       = -sum_{t < H, t+j < M} q[t]*A[t,t+j]        (B,M); the cotangent of zf[j+T] (j+T < M) is the caller's to add
+ * Any of the four outputs may be NULL (not wanted); g_a_head or g_zi needs both a and zi.  At most two launches: g_ex
+ * elementwise; then single-wave workgroups, one per (b,f) that GATHERS g_gain over the < 2 hop samples with a weight for the
+ * frame, and one per utterance for g_a_head and g_zi.  Fixed summation order, no atomics: bit-reproducible. */
+int golf_ltv_allpole_head_bwd_f32(const float* q, int64_t q_stride, const float* ex, int64_t ex_stride, const float* gain,
+                                  const float* a, const float* zi, float* g_ex, int64_t g_ex_stride, int Tx, float* g_gain,
+                                  float* g_a_head, float* g_zi, int B, int T, int F, int M, int hop, void* stream);
+
 /* Conditioning and health status of the forward that last used `ws` (ABI 3).  The reference's sequential fp32
  * recursion degrades gracefully when an interpolated filter comes close to instability (models/filters.py:99-113 ->
  * torchlpc.sample_wise_lpc); the time-chunked algorithm keeps that behaviour by recomputing the
