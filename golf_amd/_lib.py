@@ -19,7 +19,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
-           "stft_filter.hip")
+           "stft_filter.hip", "minphase_fir.hip")
 
 _c_f32p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -116,6 +116,14 @@ SIGNATURES = {
     "golf_ltv_fir_frames_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _int, _c_f32p, _i64] + [_int] * 6 + [_vp]),
     "golf_ltv_fir_frames_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _int, _c_f32p, _i64, _c_f32p]
                                     + [_int] * 6 + [_vp]),
+    "golf_min_phase_fir_basis_bytes": (_sz, [_int]),
+    "golf_min_phase_fir_basis_f32": (_int, [_int, _vp, _sz, _vp]),
+    "golf_min_phase_fir_kernels_f32": (_int, [_c_f32p, _c_f32p, _vp, _c_f32p, _int, _int, _vp]),
+    "golf_min_phase_fir_kernels_bwd_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _vp, _c_f32p, _int, _int, _vp]),
+    "golf_ltv_fir_frames_causal_length": (_int, [_int] * 4),
+    "golf_ltv_fir_frames_causal_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _int, _c_f32p, _i64] + [_int] * 6 + [_vp]),
+    "golf_ltv_fir_frames_causal_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _int, _c_f32p, _i64, _c_f32p]
+                                           + [_int] * 6 + [_vp]),
     "golf_lti_fir_f32": (_int, [_c_f32p, _i64, _c_f32p, _int, _int, _c_f32p, _i64, _int, _int, _vp]),
     "golf_lti_fir_taps_grad_workspace_bytes": (_sz, [_int] * 3),
     "golf_lti_fir_taps_grad_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _int, _int, _int, _int, _vp, _sz,

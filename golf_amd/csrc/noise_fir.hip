@@ -118,6 +118,9 @@ __device__ __forceinline__ f32x4 fir_finish(const FirAcc& A) {
 // ------------------------------------------------------------------------------------------------------------
 // forward: unit = (utterance b, frame f, pass c over the frame's hop outputs)
 // ------------------------------------------------------------------------------------------------------------
+// CAUSAL (the minimum-phase filter, reference models/filters.py:254-283): y[b, f*hop+n] = sum_{j<N} kernel[b,f,j] * ex[b, f*hop+n-j].
+// The same correlation with the row's taps taken in reverse order (zero padded to ntaps) and the signal ntaps-1 samples back.
+template <bool CAUSAL>
 __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_fwd_kernel(
     const float* __restrict__ ex, int64_t ex_stride, const float* __restrict__ kern, int KS, float* __restrict__ y,
     int64_t y_stride, int B, int T, int nfr, int F, int N, int hop, int npass, int RS, int frame0) {
@@ -128,8 +131,8 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_fwd_kernel(
     if (unit >= B * nfr * npass) return;
     const int c = unit % npass, f = (unit / npass) % nfr, b = unit / (npass * nfr);
     float* sig = fir_lds + wv * RS;
-    const int P = (N - 1) >> 1;
     const int ntaps = (N + 3) & ~3;  // kernel rows are zero padded to KS >= ntaps
+    const int P = CAUSAL ? ntaps - 1 : (N - 1) >> 1;
     const int span = 256 + ntaps + 4;
     const int t0 = f * hop + c * FIR_TILE;  // first output of this pass
     const BufRow xr(ex + b * ex_stride, T);
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_fwd_kernel(
     wave_lds_fence();
     FirAcc A;
     fir_zero(A);
-    fir_accum(A, sig, kern + (size_t)(b * F + f + frame0) * KS, ntaps, lane);  // output frame f uses kernel row f + frame0
+    fir_accum<CAUSAL>(A, sig, kern + (size_t)(b * F + f + frame0) * KS, ntaps, lane);  // output frame f uses kernel row f + frame0
     const f32x4 r = fir_finish(A);
     const BufRow yr(y + b * y_stride, nfr * hop);
     const int o = 4 * lane;
@@ -152,6 +155,8 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_fwd_kernel(
 // backward w.r.t. the kernels: g_kern[b,f,k] = sum_{n<hop} gy[b,f*hop+n] * pad(ex)[b, f*hop+n+k]
 // unit = (b, f, pass c over the N taps); taps of the core = the frame's hop gradient samples
 // ------------------------------------------------------------------------------------------------------------
+// CAUSAL: g_kern[b,f,j] = sum_{n<hop} gy[b,f*hop+n] * ex[b, f*hop+n-j]; the pass runs over k = N-1-j, stored mirrored.
+template <bool CAUSAL>
 __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_bwd_kern_kernel(
     const float* __restrict__ gy, int64_t gy_stride, const float* __restrict__ ex, int64_t ex_stride,
     float* __restrict__ g_kern, int KS, int B, int T, int nfr, int F, int N, int hop, int npass, int RS, int frame0) {
@@ -170,7 +175,7 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_bwd_kern_kernel(
     f32x4 r = {0.f, 0.f, 0.f, 0.f};
     if (f >= 0 && f < nfr && k0 < N) {  // wave-uniform (a pass that holds padding taps only has nothing to correlate)
         float* sig = fir_lds + wv * RS;
-        const int P = (N - 1) >> 1;
+        const int P = CAUSAL ? N - 1 : (N - 1) >> 1;
         const int span = 256 + hop + 4;
         const BufRow xr(ex + b * ex_stride, T);
         fir_stage<false>(sig, xr, f * hop + k0 - P, span, lane);
@@ -179,6 +184,14 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_bwd_kern_kernel(
         fir_zero(A);
         fir_accum(A, sig, gy + b * gy_stride + (size_t)f * hop, hop, lane);
         r = fir_finish(A);
+    }
+    if (CAUSAL) {  // tap j = N-1-k for k < N; the padding taps [N, KS) keep their place
+        const int k = k0 + o;
+        gr.st(o + 0 < limz ? (o + 0 < lim ? N - 1 - k - 0 : k + 0) : -1, o + 0 < lim ? r.x : 0.f);
+        gr.st(o + 1 < limz ? (o + 1 < lim ? N - 1 - k - 1 : k + 1) : -1, o + 1 < lim ? r.y : 0.f);
+        gr.st(o + 2 < limz ? (o + 2 < lim ? N - 1 - k - 2 : k + 2) : -1, o + 2 < lim ? r.z : 0.f);
+        gr.st(o + 3 < limz ? (o + 3 < lim ? N - 1 - k - 3 : k + 3) : -1, o + 3 < lim ? r.w : 0.f);
+        return;
     }
     gr.st(o + 0 < limz ? k0 + o + 0 : -1, o + 0 < lim ? r.x : 0.f);
     gr.st(o + 1 < limz ? k0 + o + 1 : -1, o + 1 < lim ? r.y : 0.f);
@@ -193,6 +206,8 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_bwd_kern_kernel(
 // the tap index: sig_f[i] = kernel[f][m_hi - f*hop - i] (0 outside the kernel), taps = gy of frame f; the frames
 // whose support reaches the tile are accumulated one after the other.
 // ------------------------------------------------------------------------------------------------------------
+// CAUSAL: P = N-1 and the row read forwards (kernel'[i] = kernel[N-1-i] is what the correlation form above applies).
+template <bool CAUSAL>
 __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_bwd_ex_kernel(
     const float* __restrict__ gy, int64_t gy_stride, const float* __restrict__ kern, int KS,
     float* __restrict__ g_ex, int64_t g_ex_stride, int B, int T, int nfr, int F, int N, int hop, int TILE,
@@ -204,7 +219,7 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_bwd_ex_kernel(
     if (unit >= B * ntile) return;
     const int tile = tile_lo + unit % ntile, b = unit / ntile;
     float* sig = fir_lds + wv * RS;
-    const int P = (N - 1) >> 1;
+    const int P = CAUSAL ? N - 1 : (N - 1) >> 1;
     const int m_lo = tile * TILE, m_hi = m_lo + TILE - 1;
     int f_lo = m_lo - (N - 1) - (hop - 1);  // f*hop >= this
     f_lo = f_lo <= 0 ? 0 : (f_lo + hop - 1) / hop;
@@ -215,7 +230,8 @@ __global__ __launch_bounds__(64 * FIR_WAVES) void fir_frames_bwd_ex_kernel(
     for (int f = f_lo; f <= f_hi; ++f) {
         const BufRow kr(kern + (size_t)(b * F + f + frame0) * KS, N);
         wave_lds_fence();
-        fir_stage<true>(sig, kr, m_hi - f * hop, span, lane);
+        if (CAUSAL) fir_stage<false>(sig, kr, N - 1 - (m_hi - f * hop), span, lane);
+        else fir_stage<true>(sig, kr, m_hi - f * hop, span, lane);
         wave_lds_fence();
         fir_accum(A, sig, gy + b * gy_stride + (size_t)f * hop, hop, lane);
     }
@@ -553,6 +569,73 @@ static inline int zp_pad(int n_mag) { return (int)align_up((size_t)n_mag, ZG_COL
 
 using namespace golf;
 
+// pad = total zero padding of the excitation: 2P (zero-phase, P each side) or N-1 (causal, all in front)
+static int fir_geometry(const char* who, int B, int T, int F, int N, int hop, int KS, int frame0, int* nfr_out,
+                        bool causal = false) {
+    if (B < 1 || T < 1 || F < 1 || N < 2 || hop < 1 || KS < ((N + 3) & ~3) || frame0 < 0 || frame0 >= F)
+        return fail(GOLF_EINVAL, "%s: bad sizes B=%d T=%d F=%d N=%d hop=%d row_stride=%d frame0=%d", who, B, T, F, N, hop,
+                    KS, frame0);
+    const int pad = causal ? N - 1 : 2 * ((N - 1) / 2), span = N + hop - 1;
+    if (T + pad < span)
+        return fail(GOLF_EINVAL, "%s: excitation (T=%d) shorter than one frame span (%d)", who, T, span - pad);
+    int nfr = (T + pad - span) / hop + 1;
+    if (nfr > F - frame0) nfr = F - frame0;
+    *nfr_out = nfr;
+    return GOLF_OK;
+}
+
+template <bool CAUSAL>
+static int fir_frames_fwd(const char* who, const float* ex, int64_t ex_stride, const float* kern, int kern_row_stride,
+                          float* y, int64_t y_stride, int B, int T, int F, int N, int hop, int frame0, void* stream) {
+    if (!ex || !kern || !y) return fail(GOLF_EINVAL, "%s: null pointer", who);
+    int nfr = 0;
+    if (int rc = fir_geometry(who, B, T, F, N, hop, kern_row_stride, frame0, &nfr, CAUSAL)) return rc;
+    const int npass = (hop + FIR_TILE - 1) / FIR_TILE;
+    const int RS = fir_region(256 + ((N + 3) & ~3) + 4);
+    const long long units = (long long)B * nfr * npass;
+    hipLaunchKernelGGL(fir_frames_fwd_kernel<CAUSAL>, dim3((unsigned)((units + FIR_WAVES - 1) / FIR_WAVES)),
+                       dim3(64 * FIR_WAVES), FIR_WAVES * RS * sizeof(float), (hipStream_t)stream, ex, ex_stride, kern,
+                       kern_row_stride, y, y_stride, B, T, nfr, F, N, hop, npass, RS, frame0);
+    GOLF_LAUNCH_CHECK();
+    return GOLF_OK;
+}
+
+template <bool CAUSAL>
+static int fir_frames_bwd(const char* who, const float* gy, int64_t gy_stride, const float* ex, int64_t ex_stride,
+                          const float* kern, int kern_row_stride, float* g_ex, int64_t g_ex_stride, float* g_kern, int B,
+                          int T, int F, int N, int hop, int frame0, void* stream) {
+    if (!gy || !ex || !kern) return fail(GOLF_EINVAL, "%s: null pointer", who);
+    int nfr = 0;
+    if (int rc = fir_geometry(who, B, T, F, N, hop, kern_row_stride, frame0, &nfr, CAUSAL)) return rc;
+    if (hop % 4 != 0)
+        return fail(GOLF_EUNSUPPORTED, "%s: hop=%d must be a multiple of 4 (the frame's gradient "
+                    "samples are the packed taps of the backward kernels)", who, hop);
+    const int RS = fir_region(256 + hop + 4);
+    hipStream_t st = (hipStream_t)stream;
+    if (g_kern) {
+        // passes over the whole ROW (kern_row_stride >= N): the padding taps [N, KS) are part of the contract ("zeroed") and a
+        // pass count taken from N left [npass * 252, KS) unwritten whenever N sat just under a multiple of 252 (ADVICE r4)
+        const int npass = (kern_row_stride + FIR_TILE - 1) / FIR_TILE;
+        const long long units = (long long)B * F * npass;
+        hipLaunchKernelGGL(fir_frames_bwd_kern_kernel<CAUSAL>, dim3((unsigned)((units + FIR_WAVES - 1) / FIR_WAVES)),
+                           dim3(64 * FIR_WAVES), FIR_WAVES * RS * sizeof(float), st, gy, gy_stride, ex, ex_stride,
+                           g_kern, kern_row_stride, B, T, nfr, F, N, hop, npass, RS, frame0);
+        GOLF_LAUNCH_CHECK();
+    }
+    if (g_ex) {
+        const int P = CAUSAL ? N - 1 : (N - 1) / 2;
+        const int TILE = hop <= FIR_TILE ? hop : FIR_TILE;
+        const int tile_lo = P / TILE, tile_hi = (P + T - 1) / TILE;
+        const int ntile = tile_hi - tile_lo + 1;
+        const long long units = (long long)B * ntile;
+        hipLaunchKernelGGL(fir_frames_bwd_ex_kernel<CAUSAL>, dim3((unsigned)((units + FIR_WAVES - 1) / FIR_WAVES)),
+                           dim3(64 * FIR_WAVES), FIR_WAVES * RS * sizeof(float), st, gy, gy_stride, kern,
+                           kern_row_stride, g_ex, g_ex_stride, B, T, nfr, F, N, hop, TILE, tile_lo, ntile, RS, frame0);
+        GOLF_LAUNCH_CHECK();
+    }
+    return GOLF_OK;
+}
+
 extern "C" {
 
 int golf_zero_phase_fir_row_stride(int n_mag) {
@@ -603,19 +686,6 @@ int golf_zero_phase_fir_kernels_bwd_f32(const float* g_kern, const float* log_ma
     return GOLF_OK;
 }
 
-static int fir_geometry(const char* who, int B, int T, int F, int N, int hop, int KS, int frame0, int* nfr_out) {
-    if (B < 1 || T < 1 || F < 1 || N < 2 || hop < 1 || KS < ((N + 3) & ~3) || frame0 < 0 || frame0 >= F)
-        return fail(GOLF_EINVAL, "%s: bad sizes B=%d T=%d F=%d N=%d hop=%d row_stride=%d frame0=%d", who, B, T, F, N, hop,
-                    KS, frame0);
-    const int P = (N - 1) / 2, span = N + hop - 1;
-    if (T + 2 * P < span)
-        return fail(GOLF_EINVAL, "%s: excitation (T=%d) shorter than one frame span (%d)", who, T, span - 2 * P);
-    int nfr = (T + 2 * P - span) / hop + 1;
-    if (nfr > F - frame0) nfr = F - frame0;
-    *nfr_out = nfr;
-    return GOLF_OK;
-}
-
 int golf_ltv_fir_frames_length(int T, int F, int N, int hop) {
     int nfr = 0;
     if (fir_geometry("ltv_fir_frames_length", 1, T, F, N, hop, (N + 3) & ~3, 0, &nfr)) return -1;
@@ -624,52 +694,35 @@ int golf_ltv_fir_frames_length(int T, int F, int N, int hop) {
 
 int golf_ltv_fir_frames_fwd_f32(const float* ex, int64_t ex_stride, const float* kern, int kern_row_stride, float* y,
                                 int64_t y_stride, int B, int T, int F, int N, int hop, int frame0, void* stream) {
-    if (!ex || !kern || !y) return fail(GOLF_EINVAL, "ltv_fir_frames_fwd: null pointer");
-    int nfr = 0;
-    if (int rc = fir_geometry("ltv_fir_frames_fwd", B, T, F, N, hop, kern_row_stride, frame0, &nfr)) return rc;
-    const int npass = (hop + FIR_TILE - 1) / FIR_TILE;
-    const int RS = fir_region(256 + ((N + 3) & ~3) + 4);
-    const long long units = (long long)B * nfr * npass;
-    hipLaunchKernelGGL(fir_frames_fwd_kernel, dim3((unsigned)((units + FIR_WAVES - 1) / FIR_WAVES)),
-                       dim3(64 * FIR_WAVES), FIR_WAVES * RS * sizeof(float), (hipStream_t)stream, ex, ex_stride, kern,
-                       kern_row_stride, y, y_stride, B, T, nfr, F, N, hop, npass, RS, frame0);
-    GOLF_LAUNCH_CHECK();
-    return GOLF_OK;
+    return fir_frames_fwd<false>("ltv_fir_frames_fwd", ex, ex_stride, kern, kern_row_stride, y, y_stride, B, T, F, N, hop,
+                                 frame0, stream);
 }
 
 int golf_ltv_fir_frames_bwd_f32(const float* gy, int64_t gy_stride, const float* ex, int64_t ex_stride,
                                 const float* kern, int kern_row_stride, float* g_ex, int64_t g_ex_stride,
                                 float* g_kern, int B, int T, int F, int N, int hop, int frame0, void* stream) {
-    if (!gy || !ex || !kern) return fail(GOLF_EINVAL, "ltv_fir_frames_bwd: null pointer");
+    return fir_frames_bwd<false>("ltv_fir_frames_bwd", gy, gy_stride, ex, ex_stride, kern, kern_row_stride, g_ex,
+                                 g_ex_stride, g_kern, B, T, F, N, hop, frame0, stream);
+}
+
+int golf_ltv_fir_frames_causal_length(int T, int F, int N, int hop) {
     int nfr = 0;
-    if (int rc = fir_geometry("ltv_fir_frames_bwd", B, T, F, N, hop, kern_row_stride, frame0, &nfr)) return rc;
-    if (hop % 4 != 0)
-        return fail(GOLF_EUNSUPPORTED, "ltv_fir_frames_bwd: hop=%d must be a multiple of 4 (the frame's gradient "
-                    "samples are the packed taps of the backward kernels)", hop);
-    const int RS = fir_region(256 + hop + 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (g_kern) {
-        // passes over the whole ROW (kern_row_stride >= N): the padding taps [N, KS) are part of the contract ("zeroed") and a
-        // pass count taken from N left [npass * 252, KS) unwritten whenever N sat just under a multiple of 252 (ADVICE r4)
-        const int npass = (kern_row_stride + FIR_TILE - 1) / FIR_TILE;
-        const long long units = (long long)B * F * npass;
-        hipLaunchKernelGGL(fir_frames_bwd_kern_kernel, dim3((unsigned)((units + FIR_WAVES - 1) / FIR_WAVES)),
-                           dim3(64 * FIR_WAVES), FIR_WAVES * RS * sizeof(float), st, gy, gy_stride, ex, ex_stride,
-                           g_kern, kern_row_stride, B, T, nfr, F, N, hop, npass, RS, frame0);
-        GOLF_LAUNCH_CHECK();
-    }
-    if (g_ex) {
-        const int P = (N - 1) / 2;
-        const int TILE = hop <= FIR_TILE ? hop : FIR_TILE;
-        const int tile_lo = P / TILE, tile_hi = (P + T - 1) / TILE;
-        const int ntile = tile_hi - tile_lo + 1;
-        const long long units = (long long)B * ntile;
-        hipLaunchKernelGGL(fir_frames_bwd_ex_kernel, dim3((unsigned)((units + FIR_WAVES - 1) / FIR_WAVES)),
-                           dim3(64 * FIR_WAVES), FIR_WAVES * RS * sizeof(float), st, gy, gy_stride, kern,
-                           kern_row_stride, g_ex, g_ex_stride, B, T, nfr, F, N, hop, TILE, tile_lo, ntile, RS, frame0);
-        GOLF_LAUNCH_CHECK();
-    }
-    return GOLF_OK;
+    if (fir_geometry("ltv_fir_frames_causal_length", 1, T, F, N, hop, (N + 3) & ~3, 0, &nfr, true)) return -1;
+    return nfr * hop;
+}
+
+int golf_ltv_fir_frames_causal_fwd_f32(const float* ex, int64_t ex_stride, const float* kern, int kern_row_stride,
+                                       float* y, int64_t y_stride, int B, int T, int F, int N, int hop, int frame0,
+                                       void* stream) {
+    return fir_frames_fwd<true>("ltv_fir_frames_causal_fwd", ex, ex_stride, kern, kern_row_stride, y, y_stride, B, T, F,
+                                N, hop, frame0, stream);
+}
+
+int golf_ltv_fir_frames_causal_bwd_f32(const float* gy, int64_t gy_stride, const float* ex, int64_t ex_stride,
+                                       const float* kern, int kern_row_stride, float* g_ex, int64_t g_ex_stride,
+                                       float* g_kern, int B, int T, int F, int N, int hop, int frame0, void* stream) {
+    return fir_frames_bwd<true>("ltv_fir_frames_causal_bwd", gy, gy_stride, ex, ex_stride, kern, kern_row_stride, g_ex,
+                                g_ex_stride, g_kern, B, T, F, N, hop, frame0, stream);
 }
 
 static int lti_check(const char* who, int B, int T, int ntaps, int lead) {

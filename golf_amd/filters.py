@@ -15,11 +15,12 @@ from torch import Tensor
 from . import functional as GF
 from .audiotensor import AudioTensor
 from .ctrl import Controllable, wrap_ctrl_fn
-from .utils import biquads2lpc, get_logits2biquads, get_window_fn, lsp2lpc, rc2lpc
+from .utils import biquads2lpc, get_logits2biquads, get_radiation_time_filter, get_window_fn, lsp2lpc, rc2lpc
 
 __all__ = ["LTVCepFilter", "DiffWorldSPFilter", "melscale_fbanks", "FilterInterface", "LTVFilterInterface", "LTVMinimumPhaseFilterPrecise", "LTVMinimumPhaseFilter",
            "LTVZeroPhaseFIRFilter", "LTVZeroPhaseFIRFilterPrecise", "LTVAPZeroPhaseFIRFilter", "LTIAcousticFilter",
-           "convert2samplewise"]
+           "LTVMinimumPhaseFIRFilterPrecise", "LTVMinimumPhaseFIRFilter", "LTIRadiationFilter",
+           "SampleBasedLTVMinimumPhaseFilter", "convert2samplewise"]
 
 
 class FilterInterface(Controllable):
@@ -293,6 +294,105 @@ class LTIAcousticFilter(FilterInterface):
         return torch.cat([self.kernel, torch.ones(1, device=self.kernel.device)]).flip(0)
 
 
+class LTVMinimumPhaseFIRFilterPrecise(LTVFilterInterface):
+    """Sample-wise minimum-phase FIR filter (reference models/filters.py:198-241): per-frame minimum-phase impulse
+    responses designed from log magnitudes (same magnitude response as the zero-phase filter, response from tap 0, no
+    lookahead), linearly interpolated to sample rate, y[t] = sum_j h_t[j] ex[t-j].  ``forward`` runs
+    golf_min_phase_fir_kernels_f32 (two contractions on the matrix cores) + golf_ltv_fir_frames_causal_* twice (rows f and
+    f+1, blended per sample); differentiable w.r.t. ``ex`` and ``log_mag``.
+
+    ``n_mag`` (not in the reference's signature; the zero-phase twin has it too) installs the ``.ctrl`` split that lets
+    the class sit in a decoder."""
+
+    def __init__(self, window: str, n_mag: int = None):
+        super().__init__()
+        self.window_fn = get_window_fn(window)
+        self._windows = {}
+        if n_mag is not None:
+            self.ctrl = wrap_ctrl_fn(split_size=(n_mag,), trsfm_fn=lambda x: (x,))
+
+    def _window(self, n: int, device) -> Tensor:
+        key = (n, str(device))
+        w = self._windows.get(key)
+        if w is None:
+            w = self._windows[key] = GF.min_phase_window(self.window_fn, n, device)
+        return w
+
+    @staticmethod
+    def get_minimum_phase_fir(log_mag: Tensor) -> Tensor:
+        """(…,F,n_mag) -> (…,F,N) minimum-phase impulse responses, *not* windowed (filters.py:203-214)."""
+        lm = log_mag.reshape(-1, log_mag.shape[-2], log_mag.shape[-1]) if log_mag.dim() != 3 else log_mag
+        n = 2 * (lm.shape[-1] - 1)
+        k = GF.min_phase_fir_kernels(lm, torch.ones(n, device=lm.device))
+        return k.reshape(*log_mag.shape[:-1], n)
+
+    def windowing(self, kernel: Tensor) -> Tensor:
+        return kernel * self._window(kernel.shape[-1], kernel.device)
+
+    def _inputs(self, ex: AudioTensor, log_mag: AudioTensor):
+        assert ex.ndim == 2, ex.shape
+        assert log_mag.ndim == 3, log_mag.shape
+        assert ex.hop_length == 1, f"excitation must be at hop 1 (got {ex.hop_length})"
+        x = ex.as_tensor()
+        return x, log_mag.as_tensor(), self._window(2 * (log_mag.shape[-1] - 1), x.device), int(log_mag.hop_length)
+
+    def forward(self, ex: AudioTensor, log_mag: AudioTensor) -> AudioTensor:
+        return AudioTensor(GF.min_phase_fir_filter_precise(*self._inputs(ex, log_mag)))
+
+
+class LTVMinimumPhaseFIRFilter(LTVMinimumPhaseFIRFilterPrecise):
+    """Frame-wise minimum-phase FIR filter (reference models/filters.py:244-283): frame f's kernel filters its hop
+    samples, y[f*hop+n] = sum_j h_f[j] ex[f*hop+n-j], T // hop frames (more than there are kernels is an error, as in the
+    reference).  golf_min_phase_fir_kernels_f32 + golf_ltv_fir_frames_causal_{fwd,bwd}_f32.
+
+    ``conv_method`` ("direct" | "fft") is accepted and validated for config compatibility, as in the zero-phase twin."""
+
+    def __init__(self, window: str, conv_method: str = "direct", n_mag: int = None):
+        super().__init__(window=window, n_mag=n_mag)
+        if conv_method not in ("direct", "fft"):
+            raise ValueError(f"Unknown conv_method: {conv_method}")
+
+    def forward(self, ex: AudioTensor, log_mag: AudioTensor) -> AudioTensor:
+        return AudioTensor(GF.min_phase_fir_filter(*self._inputs(ex, log_mag)))
+
+
+class LTIRadiationFilter(FilterInterface):
+    """Lip-radiation filter (reference models/filters.py:400-423): a fixed FIR of 2*num_zeros + 1 taps, same-length
+    output, y[t] = sum_i r[i] ex[t + num_zeros - i] with r = get_radiation_time_filter(num_zeros, window).  ``_kernel``
+    is the reference's non-persistent (1, 1, 2*num_zeros+1) buffer (r flipped: a correlation kernel).  Runs
+    golf_lti_fir_f32; the gradient goes to ``ex`` only."""
+
+    def __init__(self, num_zeros: int, window: str = "hanning"):
+        super().__init__()
+        k = get_radiation_time_filter(num_zeros, get_window_fn(window)).flip(0).float()
+        self.register_buffer("_kernel", k.unsqueeze(0).unsqueeze(0), persistent=False)
+        self._padding = k.shape[0] // 2
+        # the kernel of golf_lti_fir_f32 holds a multiple of 4 taps: zeros behind the last one
+        self.register_buffer("_taps", torch.cat([k, torch.zeros((-k.shape[0]) % 4)]), persistent=False)
+
+    def forward(self, ex: Tensor) -> Tensor:
+        assert ex.ndim == 2
+        if isinstance(ex, AudioTensor):
+            return AudioTensor(GF.lti_fir(ex.as_tensor(), self._taps, self._padding), hop_length=ex.hop_length)
+        return GF.lti_fir(ex, self._taps, self._padding)
+
+
+class SampleBasedLTVMinimumPhaseFilter(LTVMinimumPhaseFilter):
+    """Deprecated alias of the sample-wise all-pole filter (reference models/filters.py:763-790): the reference upsamples
+    the coefficients and calls sample_wise_lpc, which is what ``LTVMinimumPhaseFilterPrecise.forward`` runs on the
+    frame-rate tracks."""
+
+    def __init__(self, lpc_order: int = None, lpc_parameterisation: str = "rc2lpc", max_abs_value: float = 1, **kwargs):
+        import warnings
+
+        warnings.warn("SampleBasedLTVMinimumPhaseFilter is deprecated. Use LTVMinimumPhaseFilterPrecise instead.")
+        super().__init__("hanning", 1, lpc_order=lpc_order, lpc_parameterisation=lpc_parameterisation,
+                         max_abs_value=max_abs_value)
+
+    prefetch = LTVMinimumPhaseFilterPrecise.prefetch
+    forward = LTVMinimumPhaseFilterPrecise.forward
+
+
 class LTVCepFilter(LTVFilterInterface):
     """Cepstral harmonic filter of the NHV baseline (reference models/filters.py:559-623; cfg/ae/decoder/nhv.yaml):
     ``filter_order + 1`` cepstral coefficients per frame -> log-magnitude response (even extension + FFT) -> zero- or
@@ -395,6 +495,10 @@ def convert2samplewise(config: dict) -> dict:
                 config["class_path"] = value.rsplit(".", 1)[0] + ".LTVMinimumPhaseFilterPrecise"
                 for k in ("window", "window_length", "centred"):
                     config.get("init_args", {}).pop(k, None)
+                return config
+            if ".LTVMinimumPhaseFIRFilter" in value and not value.endswith("Precise"):
+                config["class_path"] = value.rsplit(".", 1)[0] + ".LTVMinimumPhaseFIRFilterPrecise"
+                config.get("init_args", {}).pop("conv_method", None)
                 return config
             if ".LTVZeroPhaseFIRFilter" in value and not value.endswith("Precise"):
                 config["class_path"] = value.rsplit(".", 1)[0] + ".LTVZeroPhaseFIRFilterPrecise"

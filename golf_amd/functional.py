@@ -14,7 +14,8 @@ from . import _lib
 __all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lti_frames_ola", "glottal_osc",
            "ss_output_length", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
-           "zero_phase_fir_filter_precise",
+           "zero_phase_fir_filter_precise", "min_phase_fir_basis", "min_phase_window", "min_phase_fir_kernels",
+           "min_phase_fir_filter", "min_phase_fir_filter_precise", "ltv_fir_frames_causal",
            "fir_frames_length", "lti_fir", "harmonic_osc", "biquad_frames_ola"]
 
 HAVE_TRANSITIONS = 1
@@ -1359,6 +1360,205 @@ def ltv_fir_frames(ex: torch.Tensor, kernels: torch.Tensor, hop: int) -> torch.T
     KS = (N + 15) // 16 * 16
     kern = torch.nn.functional.pad(kernels.reshape(B * F, N), (0, KS - N))
     return _FIRFrames.apply(ex, kern, F, N, hop, 0)
+
+
+# ------------------------------------------------------------------------------------------------
+# minimum-phase FIR filter (reference models/filters.py:198-283): the causal twin of the zero-phase filter
+# ------------------------------------------------------------------------------------------------
+_mp_basis_cache = {}
+
+
+def min_phase_fir_basis(n_mag: int, device) -> torch.Tensor:
+    """The constant matrices of the minimum-phase design for ``n_mag`` bins (Hilbert transform on the half spectrum,
+    cosine and sine synthesis, both orientations), built once per device."""
+    dev = torch.device(device)
+    key = (n_mag, dev.index if dev.index is not None else torch.cuda.current_device())
+    b = _mp_basis_cache.get(key)
+    if b is None:
+        lib = _lib.load()
+        nbytes = lib.golf_min_phase_fir_basis_bytes(n_mag)
+        b = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        _lib.check(lib.golf_min_phase_fir_basis_f32(n_mag, b.data_ptr(), nbytes, _lib.stream_ptr()),
+                   "golf_min_phase_fir_basis_f32")
+        _mp_basis_cache[key] = b
+    return b
+
+
+def min_phase_window(window_fn, n: int, device=None) -> torch.Tensor:
+    """The reference's ``windowing`` (models/filters.py:216-221) as a vector: window_fn(n) with its first n // 2 entries
+    set to 1 (the minimum-phase response starts at tap 0: only its tail is tapered)."""
+    w = window_fn(n).to(dtype=torch.float32).clone()
+    w[: n // 2] = 1
+    return w.to(device=device).contiguous()
+
+
+def fir_frames_causal_length(T: int, F: int, N: int, hop: int) -> int:
+    lib = _lib.load()
+    n = lib.golf_ltv_fir_frames_causal_length(T, F, N, hop)
+    if n < 0:
+        raise _lib.GolfError(lib.golf_last_error().decode(errors="replace"))
+    return n
+
+
+def _mp_check_window(log_mag, window):
+    n_mag = log_mag.shape[2]
+    if window.numel() != 2 * (n_mag - 1):
+        raise _lib.GolfError(f"min_phase_fir: window has {window.numel()} taps, expected {2 * (n_mag - 1)}")
+
+
+def _mp_kernels_raw(lib, log_mag, window, basis):
+    B, F, n_mag = log_mag.shape
+    KS = lib.golf_zero_phase_fir_row_stride(n_mag)
+    kern = torch.empty(B * F, KS, dtype=torch.float32, device=log_mag.device)
+    _lib.check(lib.golf_min_phase_fir_kernels_f32(log_mag.data_ptr(), window.data_ptr(), basis.data_ptr(),
+                                                  kern.data_ptr(), B * F, n_mag, _lib.stream_ptr()),
+               "golf_min_phase_fir_kernels_f32")
+    return kern
+
+
+def min_phase_fir_kernels(log_mag: torch.Tensor, window: torch.Tensor) -> torch.Tensor:
+    """(B,F,n_mag) log magnitudes -> (B,F,N) minimum-phase FIR kernels times ``window`` (N taps), N = 2*(n_mag-1)
+    (no autograd)."""
+    _lib.require_device(log_mag, window)
+    lib = _lib.load()
+    log_mag = log_mag.detach().contiguous()
+    window = window.contiguous()
+    _mp_check_window(log_mag, window)
+    B, F, n_mag = log_mag.shape
+    N = 2 * (n_mag - 1)
+    kern = _mp_kernels_raw(lib, log_mag, window, min_phase_fir_basis(n_mag, log_mag.device))
+    return kern.view(B, F, -1)[..., :N]
+
+
+class _MPKernels(torch.autograd.Function):
+    """(B,F,n_mag) log magnitudes -> (B*F, row_stride) windowed minimum-phase FIR rows (two contractions on the MFMAs)."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, log_mag, window):
+        _lib.require_device(log_mag, window)
+        lib = _lib.load()
+        log_mag = log_mag.contiguous()
+        window = window.contiguous()
+        _mp_check_window(log_mag, window)
+        basis = min_phase_fir_basis(log_mag.shape[2], log_mag.device)
+        kern = _mp_kernels_raw(lib, log_mag, window, basis)
+        ctx.save_for_backward(log_mag, window, basis)
+        return kern
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g_kern):
+        log_mag, window, basis = ctx.saved_tensors
+        lib = _lib.load()
+        g_kern = g_kern.contiguous()
+        B, F, n_mag = log_mag.shape
+        g_lm = torch.empty_like(log_mag)
+        _lib.check(lib.golf_min_phase_fir_kernels_bwd_f32(g_kern.data_ptr(), log_mag.data_ptr(), window.data_ptr(),
+                                                          basis.data_ptr(), g_lm.data_ptr(), B * F, n_mag,
+                                                          _lib.stream_ptr()),
+                   "golf_min_phase_fir_kernels_bwd_f32")
+        return g_lm, None
+
+
+class _FIRFramesCausal(torch.autograd.Function):
+    """Causal per-frame FIR with kernel rows kern (B*F, row_stride): y[b,f*hop+n] = sum_j kern[f+frame0][j] ex[b,f*hop+n-j]."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, ex, kern, F, N, hop, frame0):
+        _lib.require_device(ex, kern)
+        lib = _lib.load()
+        ex = _rows(ex)
+        kern = kern.contiguous()
+        B, T = ex.shape
+        if kern.shape[0] != B * F:
+            raise _lib.GolfError(f"fir_frames_causal: {kern.shape[0]} kernel rows for B={B}, F={F}")
+        Ty = fir_frames_causal_length(T, F - frame0, N, hop)
+        y = torch.empty(B, Ty, dtype=torch.float32, device=ex.device)
+        _lib.check(lib.golf_ltv_fir_frames_causal_fwd_f32(ex.data_ptr(), ex.stride(0), kern.data_ptr(), kern.shape[1],
+                                                          y.data_ptr(), y.stride(0), B, T, F, N, hop, frame0,
+                                                          _lib.stream_ptr()),
+                   "golf_ltv_fir_frames_causal_fwd_f32")
+        ctx.save_for_backward(ex, kern)
+        ctx.geom = (F, N, hop, frame0)
+        return y
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, gy):
+        ex, kern = ctx.saved_tensors
+        F, N, hop, frame0 = ctx.geom
+        lib = _lib.load()
+        gy = _rows(gy)
+        B, T = ex.shape
+        need_ex, need_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g_ex = torch.empty_like(ex) if need_ex else None
+        g_kern = torch.empty_like(kern) if need_k else None
+        _lib.check(lib.golf_ltv_fir_frames_causal_bwd_f32(gy.data_ptr(), gy.stride(0), ex.data_ptr(), ex.stride(0),
+                                                          kern.data_ptr(), kern.shape[1],
+                                                          g_ex.data_ptr() if need_ex else None,
+                                                          g_ex.stride(0) if need_ex else 0,
+                                                          g_kern.data_ptr() if need_k else None,
+                                                          B, T, F, N, hop, frame0, _lib.stream_ptr()),
+                   "golf_ltv_fir_frames_causal_bwd_f32")
+        return g_ex, g_kern, None, None, None, None
+
+
+def _mp_check_frames(who: str, ex, F: int, hop: int) -> None:
+    T = ex.shape[-1]
+    if T < hop:
+        raise _lib.GolfError(f"{who}: excitation (T={T}) shorter than one hop ({hop})")
+    if T // hop > F:   # the reference asserts this (models/filters.py:273-275)
+        raise _lib.GolfError(f"{who}: {T // hop} frames of excitation (T={T}, hop={hop}) but only {F} kernels")
+
+
+def min_phase_fir_filter(ex: torch.Tensor, log_mag: torch.Tensor, window: torch.Tensor, hop: int) -> torch.Tensor:
+    """LTVMinimumPhaseFIRFilter.forward on plain tensors: ex (B,T), log_mag (B,F,n_mag) at ``hop``, window (N) ->
+    (B, (T // hop) * hop), y[b,f*hop+n] = sum_j kernel[b,f,j] ex[b,f*hop+n-j]; differentiable w.r.t. ex and log_mag."""
+    if log_mag.dim() != 3 or ex.dim() != 2 or log_mag.shape[0] != ex.shape[0]:
+        raise _lib.GolfError(f"min_phase_fir_filter: ex {tuple(ex.shape)} vs log_mag {tuple(log_mag.shape)}")
+    F, n_mag = log_mag.shape[1], log_mag.shape[2]
+    _mp_check_frames("min_phase_fir_filter", ex, F, hop)
+    kern = _MPKernels.apply(log_mag, window)
+    return _FIRFramesCausal.apply(ex, kern, F, 2 * (n_mag - 1), hop, 0)
+
+
+def min_phase_fir_filter_precise(ex: torch.Tensor, log_mag: torch.Tensor, window: torch.Tensor, hop: int) -> torch.Tensor:
+    """LTVMinimumPhaseFIRFilterPrecise.forward (reference models/filters.py:223-241): the kernels are linearly
+    interpolated to sample rate, y[t] = sum_j ((1-w_t) K_f[j] + w_t K_{f+1}[j]) ex[t-j], f = t // hop, w_t = (t % hop)/hop,
+    output length min(T, (F-1)*hop+1).  Evaluated as two causal frame FIRs (kernel rows f and f+1 over the same signal)
+    blended per sample; the single sample t = (F-1)*hop is a dot product with the last kernel."""
+    if log_mag.dim() != 3 or ex.dim() != 2 or log_mag.shape[0] != ex.shape[0]:
+        raise _lib.GolfError(f"min_phase_fir_filter_precise: ex {tuple(ex.shape)} vs log_mag {tuple(log_mag.shape)}")
+    B, T = ex.shape
+    F, n_mag = log_mag.shape[1], log_mag.shape[2]
+    if F < 2:
+        raise _lib.GolfError("min_phase_fir_filter_precise: need at least 2 frames")
+    N = 2 * (n_mag - 1)
+    Tfull = (F - 1) * hop + 1
+    Tout = min(T, Tfull)
+    kern = _MPKernels.apply(log_mag, window)
+    x = ex[:, :Tfull]          # a causal filter: the outputs t < Tfull read nothing later (zeros past T)
+    if x.shape[1] < Tfull:
+        x = torch.nn.functional.pad(x, (0, Tfull - x.shape[1]))
+    ya = _FIRFramesCausal.apply(x, kern, F, N, hop, 0)[:, : (F - 1) * hop]
+    yb = _FIRFramesCausal.apply(x, kern, F, N, hop, 1)[:, : (F - 1) * hop]
+    w = (torch.arange((F - 1) * hop, device=ex.device) % hop).to(torch.float32) / hop
+    main = ya + w * (yb - ya)
+    tail = torch.nn.functional.pad(x, (N - 1, 0))[:, Tfull - 1: Tfull - 1 + N]  # ex[Tfull-1 - (N-1) + i], i < N
+    last = (tail.flip(-1) * kern.view(B, F, -1)[:, F - 1, :N]).sum(-1, keepdim=True)
+    return torch.cat([main, last], dim=1)[:, :Tout]
+
+
+def ltv_fir_frames_causal(ex: torch.Tensor, kernels: torch.Tensor, hop: int) -> torch.Tensor:
+    """Causal frame-wise FIR with arbitrary per-frame kernels (B,F,N): y[b,f*hop+n] = sum_j kernels[b,f,j] *
+    ex[b,f*hop+n-j], (T // hop) * hop samples; differentiable w.r.t. both."""
+    B, F, N = kernels.shape
+    _mp_check_frames("ltv_fir_frames_causal", ex, F, hop)
+    KS = (N + 15) // 16 * 16
+    kern = torch.nn.functional.pad(kernels.reshape(B * F, N), (0, KS - N))
+    return _FIRFramesCausal.apply(ex, kern, F, N, hop, 0)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ import torch
 from torch import Tensor
 
 __all__ = ["lsp2lpc", 
-    "rc2lpc", "get_logits2biquads", "biquads2lpc", "coeff_product", "get_window_fn",
+    "rc2lpc", "get_logits2biquads", "biquads2lpc", "coeff_product", "get_window_fn", "get_radiation_time_filter",
     "get_transformed_lf", "get_transformed_lf_v2", "linear_upsample", "TimeContext",
 ]
 
@@ -89,6 +89,19 @@ def get_window_fn(window: str = "hann"):
 
     get_window(window, 8)  # raise early on unknown names
     return lambda n: torch.tensor(get_window(window, n))
+
+
+def get_radiation_time_filter(num_zeros: int = 16, window_fn: Callable[[int], Tensor] = None) -> Tensor:
+    """Lip-radiation FIR of 2*num_zeros + 1 taps (reference models/utils.py:403-414): the derivative of a sinc sampled at
+    the integers t = -num_zeros..num_zeros, (cos(pi t) - sinc(pi t)) / t with torch.sinc's normalised sinc, 0 at t = 0,
+    times ``window_fn(2*num_zeros + 1)`` if given."""
+    t = torch.arange(-num_zeros, num_zeros + 1)
+    pi_t = t * torch.pi
+    out = (torch.cos(pi_t) - torch.sinc(pi_t)) / t
+    out[num_zeros] = 0
+    if window_fn is not None:
+        out = out * window_fn(out.shape[0])
+    return out
 
 
 class TimeContext:

@@ -544,6 +544,43 @@ int golf_ltv_fir_frames_bwd_f32(const float* gy, int64_t gy_stride, const float*
                                 float* g_kern, int B, int T, int F, int N, int hop, int frame0, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Minimum-phase FIR filter: the causal twin of f-1 (same magnitude response, impulse response from tap 0, no lookahead).
+ * Replaces LTVMinimumPhaseFIRFilterPrecise.get_minimum_phase_fir + windowing, models/filters.py:203-221 (with
+ * hilbert, models/utils.py:557-574):
+ *     L_sym = [log_mag, flip(log_mag)[1:-1]];  theta = -Im hilbert(L_sym);  kernel = Re ifft(exp(L_sym + j theta)) * window
+ * as two dense real contractions on the matrix cores in exact fp32 (N = 2*(n_mag-1), w = 1 at bins 0 and N/2, else 2):
+ *     theta = log_mag @ S^T,   kernel = (e^L cos theta) @ C - (e^L sin theta) @ Sn,
+ *     C[k][m] = w_k cos(2 pi k m / N) / N,  Sn[k][m] = w_k sin(2 pi k m / N) / N,  S = the Hilbert transform on the half spectrum.
+ * `basis` holds S, C and Sn in both orientations, built once per n_mag into a caller-owned buffer of
+ * golf_min_phase_fir_basis_bytes().  `window` is a vector of N taps (the reference's windowing(), filters.py:216-221, is
+ * window_fn(N) with its first N/2 entries set to 1: the caller builds it).  Rows go to the (G, row_stride) layout of
+ * golf_zero_phase_fir_row_stride(n_mag), taps [N, row_stride) written as zeros.  One workgroup keeps its rows in LDS from
+ * the log magnitudes to the finished taps: GOLF_EUNSUPPORTED where they do not fit (forward n_mag > 640, backward > 512).
+ * Nothing is allocated, nothing synchronises.
+ * ------------------------------------------------------------------------------------------- */
+size_t golf_min_phase_fir_basis_bytes(int n_mag);
+int golf_min_phase_fir_basis_f32(int n_mag, void* basis, size_t basis_bytes, void* stream);
+/* log_mag (G, n_mag), window (N) -> kern (G, row_stride);  G = B*F */
+int golf_min_phase_fir_kernels_f32(const float* log_mag, const float* window, const void* basis, float* kern, int G,
+                                   int n_mag, void* stream);
+/* g_kern (G, row_stride) -> g_log_mag (G, n_mag); theta is recomputed from log_mag */
+int golf_min_phase_fir_kernels_bwd_f32(const float* g_kern, const float* log_mag, const float* window, const void* basis,
+                                       float* g_log_mag, int G, int n_mag, void* stream);
+
+/* Causal frame FIR, replaces LTVMinimumPhaseFIRFilter.forward, models/filters.py:270-283 (left pad by N-1, unfold
+ * N+hop-1 samples every hop, correlate each frame with its flipped kernel):
+ *     y[b, f*hop+n] = sum_{j<N} kernel[b,f,j] * ex[b, f*hop+n-j],   nfr = min(T / hop, F - frame0) frames,
+ * output length nfr*hop (golf_ltv_fir_frames_causal_length; -1 if T < hop).  Arguments, kernel-row layout, frame0 and
+ * the backward's hop % 4 == 0 are those of golf_ltv_fir_frames_{fwd,bwd}_f32. */
+int golf_ltv_fir_frames_causal_length(int T, int F, int N, int hop);
+int golf_ltv_fir_frames_causal_fwd_f32(const float* ex, int64_t ex_stride, const float* kern, int kern_row_stride,
+                                       float* y, int64_t y_stride, int B, int T, int F, int N, int hop, int frame0,
+                                       void* stream);
+int golf_ltv_fir_frames_causal_bwd_f32(const float* gy, int64_t gy_stride, const float* ex, int64_t ex_stride,
+                                       const float* kern, int kern_row_stride, float* g_ex, int64_t g_ex_stride,
+                                       float* g_kern, int B, int T, int F, int N, int hop, int frame0, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f-2: LTI FIR shared by the whole batch — the room filter after the end filter.
  * Replaces LTIAcousticFilter.forward, models/filters.py:426-449 (pad + F.conv1d with one learnable kernel):
  *     y[b,t] = sum_{n<ntaps} taps[n] * ex[b, t - lead + n],   ex = 0 outside [0,T)
