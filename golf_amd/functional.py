@@ -11,7 +11,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lti_frames_ola", "glottal_osc",
+__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "lti_frames_ola",
+           "glottal_osc",
            "ss_output_length", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
            "zero_phase_fir_filter_precise", "min_phase_fir_basis", "min_phase_window", "min_phase_fir_kernels",
@@ -489,6 +490,89 @@ class _LTVInverse(torch.autograd.Function):
 def ltv_inverse(y: torch.Tensor, a: torch.Tensor, hop: int) -> torch.Tensor:
     """e[t] = y[t] + sum_i up(a)[t,i] y[t-1-i] (analysis filter); differentiable w.r.t. y and a."""
     return _LTVInverse.apply(y, a, hop)
+
+
+# ------------------------------------------------------------------------------------------------
+# LPC analysis: audio -> (gain, a, rc) per frame (include/golf_amd.h, csrc/lpc_analysis.hip)
+# ------------------------------------------------------------------------------------------------
+def lpc_analysis_frames(T: int, W: int, hop: int, centred: bool = True) -> int:
+    """Frames of the analysis: ``T // hop + 1`` centred (the filters' frame grid and the center=True STFT count),
+    ``max(T - W, 0) // hop + 1`` for frames that start at sample 0."""
+    return T // hop + 1 if centred else max(T - W, 0) // hop + 1
+
+
+class _LPCAnalysis(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, window, hop, M, origin, F, eps_rel, eps_abs, want_rc):
+        _lib.require_device(x, window)
+        lib = _lib.load()
+        x = _rows(x)
+        window = window.contiguous()
+        B, T = x.shape
+        W = window.numel()
+        gain = torch.empty(B, F, dtype=torch.float32, device=x.device)
+        a = torch.empty(B, F, M, dtype=torch.float32, device=x.device)
+        rc = torch.empty(B, F, M, dtype=torch.float32, device=x.device) if want_rc else None   # not asked for: not written
+        ws = _workspace(lib.golf_lpc_analysis_workspace_bytes(B, F, M), x.device)
+        rcode = lib.golf_lpc_analysis_fwd_f32(x.data_ptr(), x.stride(0), window.data_ptr(), gain.data_ptr(), a.data_ptr(),
+                                              _lib.ptr(rc), ws.data_ptr(), ws.numel(), B, T, F, M, hop, W, origin,
+                                              eps_rel, eps_abs, _lib.stream_ptr())
+        _lib.check(rcode, "golf_lpc_analysis_fwd_f32")
+        ctx.save_for_backward(x, window, ws)   # ws holds the regularised lags in fp64: the backward starts from them
+        ctx.geom = (hop, M, origin, F, eps_rel)
+        ctx.set_materialize_grads(False)   # the gradient of an unused output arrives as None, not as a tensor of zeros
+        return (gain, a, rc) if want_rc else (gain, a)
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g_gain, g_a, g_rc=None):
+        x, window, lags = ctx.saved_tensors
+        hop, M, origin, F, eps_rel = ctx.geom
+        if not ctx.needs_input_grad[0] or (g_gain is None and g_a is None and g_rc is None):
+            return (None,) * 9
+        lib = _lib.load()
+        B, T = x.shape
+        # an output nobody differentiated arrives as None and goes to the kernel as a null pointer: it is never read
+        gs = [None if g is None else g.float().contiguous() for g in (g_gain, g_a, g_rc)]
+        g_x = torch.empty(B, T, dtype=torch.float32, device=x.device)   # written in full by the gather
+        ws = _workspace(lib.golf_lpc_analysis_workspace_bytes(B, F, M), x.device)
+        rcode = lib.golf_lpc_analysis_bwd_f32(_lib.ptr(gs[0]), _lib.ptr(gs[1]), _lib.ptr(gs[2]), x.data_ptr(), x.stride(0),
+                                              window.data_ptr(), lags.data_ptr(), g_x.data_ptr(), g_x.stride(0),
+                                              ws.data_ptr(), ws.numel(), B, T, F, M, hop, window.numel(), origin, eps_rel,
+                                              _lib.stream_ptr())
+        _lib.check(rcode, "golf_lpc_analysis_bwd_f32")
+        return (g_x,) + (None,) * 8
+
+
+def lpc_analysis(x: torch.Tensor, window: torch.Tensor, hop: int, order: int, centred: bool = True, n_frames: int = None,
+                 eps_rel: float = 1e-9, eps_abs: float = 1e-12, return_rc: bool = False):
+    """Frame-wise LPC analysis by the autocorrelation method: x (B, T), window (W,) -> ``(gain (B, F), a (B, F, order))`` or,
+    with ``return_rc``, ``(gain, a, rc)``.  Frame f reads ``x[f*hop - W//2 + k] * window[k]`` (``centred``, F = T // hop + 1:
+    the frame grid of the filters) or ``x[f*hop + k] * window[k]`` (F = max(T - W, 0) // hop + 1); x is zero outside [0, T)
+    and ``n_frames`` overrides F.  ``a`` are the coefficients of A(z) = 1 + sum_i a_i z^-i that ``ltv_allpole_ss``,
+    ``lti_frames_ola`` and ``ltv_inverse`` take, ``rc`` the reflection coefficients with ``rc2lpc(rc) == a``,
+    ``gain = sqrt(prediction error / sum(window**2))``.  The zero lag is regularised as ``r0 * (1 + eps_rel) + eps_abs``.
+    Lags and recursion run in fp64 on the device; differentiable w.r.t. x through any subset of the outputs (the window is
+    a constant).  1 <= order <= 64, order < W <= 4096, hop >= 1."""
+    if x.dim() != 2 or window.dim() != 1:
+        raise _lib.GolfError(f"lpc_analysis: x must be (B, T) and window (W,) (got {tuple(x.shape)}, {tuple(window.shape)})")
+    hop, M, W = int(hop), int(order), window.numel()
+    if hop < 1:
+        raise _lib.GolfError(f"lpc_analysis: hop={hop} must be >= 1")
+    F = lpc_analysis_frames(x.shape[1], W, hop, centred) if n_frames is None else int(n_frames)
+    if F < 1:
+        raise _lib.GolfError(f"lpc_analysis: n_frames={F} must be >= 1")
+    if x.shape[0] * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
+        raise _lib.GolfError(f"lpc_analysis: B*F = {x.shape[0] * F} frames, must be < 2^31")
+    if x.shape[0] == 0:
+        # an empty batch: empty results of the right widths that stay in the graph, like the filters'
+        _lib.require_device(x.float(), window)
+        z = x.float().sum(1)
+        out = (z[:, None].expand(0, F), z[:, None, None].expand(0, F, M), z[:, None, None].expand(0, F, M))
+        return out if return_rc else out[:2]
+    return _LPCAnalysis.apply(x, window, hop, M, -(W // 2) if centred else 0, F, float(eps_rel), float(eps_abs),
+                              bool(return_rc))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -13,9 +13,55 @@ import torch
 from torch import Tensor, nn
 
 from . import functional as GF
+from .audiotensor import AudioTensor
 from .utils import get_window_fn
 
-__all__ = ["BatchSecondOrderLPCSynth"]
+__all__ = ["BatchSecondOrderLPCSynth", "LPCAnalysis"]
+
+
+class LPCAnalysis(nn.Module):
+    """Frame-wise LPC analysis by the autocorrelation method: a waveform -> ``(gain, a)`` at hop ``hop_length``, on the
+    device and differentiable w.r.t. the waveform (golf_lpc_analysis_{fwd,bwd}_f32, fp64 lags and recursion).  The
+    reference has no such module; its output is the ``end_filter_params`` tuple that ``LTVMinimumPhaseFilterPrecise`` and
+    ``LTVMinimumPhaseFilter`` take in ``forward`` and in ``reverse``: analysis / resynthesis, residual extraction, targets
+    for the encoder head (``logits``), LPC-domain losses on synthesised audio.
+
+    ``centred=True`` puts frame f around sample ``f * hop_length`` (the filters' frame grid, ``T // hop_length + 1``
+    frames); ``centred=False`` starts it there.  ``gain = sqrt(prediction error / sum(window**2))``: a unit-variance
+    excitation through ``a`` reproduces the frame's level."""
+
+    def __init__(self, lpc_order: int, hop_length: int, window_length: int = None, window: str = "hann",
+                 centred: bool = True):
+        super().__init__()
+        self.lpc_order = lpc_order
+        self.hop_length = hop_length
+        self.window_length = hop_length * 4 if window_length is None else window_length
+        self.centred = centred
+        self.register_buffer("_window", get_window_fn(window)(self.window_length).float(), persistent=False)
+
+    def analyse(self, x, return_rc: bool = False):
+        """Plain tensors: ``(gain (B, F), a (B, F, M))`` or ``(gain, a, rc)``."""
+        if isinstance(x, AudioTensor):
+            assert x.hop_length == 1, f"the waveform must be at hop 1 (got {x.hop_length})"
+            x = x.as_tensor()
+        assert x.ndim == 2, x.shape
+        return GF.lpc_analysis(x, self._window, self.hop_length, self.lpc_order, centred=self.centred, return_rc=return_rc)
+
+    def forward(self, x):
+        gain, a = self.analyse(x)
+        return AudioTensor(gain, self.hop_length), AudioTensor(a, self.hop_length)
+
+    @staticmethod
+    def to_logits(gain: Tensor, rc: Tensor, max_abs_value: float = 1.0):
+        """``(log_gain (B, F, 1), lpc_logits (B, F, M))``: the inverse of the ``rc2lpc`` control transform
+        ``(exp(log_gain), rc2lpc(tanh(lpc_logits) * max_abs_value))``."""
+        lim = 1.0 - 1e-6
+        return torch.log(gain).unsqueeze(-1), torch.atanh(torch.clamp(rc / max_abs_value, -lim, lim))
+
+    def logits(self, x, max_abs_value: float = 1.0):
+        """Targets for an encoder head that drives ``LTVMinimumPhaseFilterPrecise(lpc_parameterisation="rc2lpc")``."""
+        gain, _, rc = self.analyse(x, return_rc=True)
+        return self.to_logits(gain, rc, max_abs_value)
 
 
 class BatchSecondOrderLPCSynth(nn.Module):

@@ -234,6 +234,35 @@ int golf_ltv_inverse_bwd_f32(const float* g_e, int64_t g_e_stride, const float* 
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * LPC analysis (additive in ABI 6): audio -> (gain, a, rc) per frame by the autocorrelation method -- the estimate of
+ * the time-varying predictor that a-1, a-4 and a-5 take as an input.  The reference has no such module; the definition is
+ * the textbook one (oracle/make_lpc_tracks.py), with frame f of row b starting at sample origin + f*hop (origin =
+ * -floor(W/2): the filters' centred frames; origin = 0: frames from sample 0) and x = 0 outside [0, T):
+ *     s[k] = x[origin + f*hop + k] * window[k],   r[j] = sum_{n < W-j} s[n] s[n+j]  (j = 0..M),
+ *     r[0] <- r[0] * (1 + eps_rel) + eps_abs     (silent frames stay well posed: a = 0),
+ *     Levinson-Durbin from E_0 = r[0]:  k_i = -(r[i] + sum_{j<i} a_j r[i-j]) / E_{i-1},  a_j <- a_j + k_i a_{i-j},  a_i = k_i,
+ *                                       E_i = E_{i-1} (1 - k_i^2),
+ *     a (B, F, M) of A(z) = 1 + sum_i a_i z^-i (the sign of a-1, a-4, a-5),  rc (B, F, M) = k_1..k_M (golf_rc2lpc of it is a),
+ *     gain (B, F) = sqrt(max(E_M, 0) / sum_k window[k]^2).
+ * The frame is staged in fp32; lags, recursion and the whole backward are fp64 (reflection coefficients of speech reach
+ * 0.998: fp32 lags or an fp32 recursion are 1e-3 .. 1e-1 off in a).  The forward keeps the regularised lags (B, F, M+1) as
+ * doubles in `ws` (golf_lpc_analysis_workspace_bytes); the backward reads them from there (`lags`) and needs a second
+ * buffer of the same size as its own `ws`.  g_gain, g_a, g_rc may each be NULL (an output nobody differentiates); rc may
+ * be NULL in the forward.  g_x (B, T) is written in full, by a gather in a fixed order: no atomics, bit-reproducible.  The
+ * window is a constant.  No call allocates or synchronises.
+ * Refused before any launch: null required pointers (GOLF_EINVAL); M < 1, M > 64, W <= M, W > 4096 (a frame must fit
+ * LDS), hop < 1, B*F >= 2^31 (GOLF_EUNSUPPORTED).
+ * ------------------------------------------------------------------------------------------- */
+size_t golf_lpc_analysis_workspace_bytes(int B, int F, int M);
+int golf_lpc_analysis_fwd_f32(const float* x, int64_t x_stride, const float* window, float* gain, float* a, float* rc,
+                              void* ws, size_t ws_bytes, int B, int T, int F, int M, int hop, int W, int64_t origin,
+                              double eps_rel, double eps_abs, void* stream);
+int golf_lpc_analysis_bwd_f32(const float* g_gain, const float* g_a, const float* g_rc, const float* x, int64_t x_stride,
+                              const float* window, const void* lags, float* g_x, int64_t g_x_stride, void* ws,
+                              size_t ws_bytes, int B, int T, int F, int M, int hop, int W, int64_t origin, double eps_rel,
+                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a-4: frame-wise LTI all-pole + windowed overlap-add — GOLF-ff end filter.
  * Replaces LTVMinimumPhaseFilter.forward, models/filters.py:131-184 (pad, unfold, lpc_synthesis ->
  * torchaudio.functional.lfilter models/lpc.py:11-16, diagonal conv_transpose1d OLA, normalise).
