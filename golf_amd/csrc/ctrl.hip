@@ -198,107 +198,123 @@ __global__ __launch_bounds__(RC_THREADS) void rc2lpc_bwd_reg_kernel(const float*
 //   rep 0 "coef": a1 = 2 rho tanh(l0);            a2 = ((2 - |a1|) rho tanh(l1) + |a1|) / 2
 //   rep 1 "conj": r = rho sigmoid(l0);            a1 = -2 r tanh(l1);   a2 = r^2
 //   rep 2 "real": z = rho tanh(l);                a1 = -(z0 + z1);      a2 = z0 z1
-struct Sos { float a1, a2; };
-__device__ __forceinline__ Sos sos_from_logits(float l0, float l1, float rho, int rep) {
+// All of it in double: the product of K sections cancels.  With "coef" at K = 32 single frames grow to 1e11 before they come
+// down to |a| ~ 1 (condition 6e10), and an fp32 product leaves 1e-3 of such a frame's largest coefficient -- as much as the
+// reference's own fp32 run, but in other places, so no per-frame comparison with it can hold.  In double the result is the
+// float64 product rounded once (1e-6 of every frame, gradients included); the cost is 2K tanh and 2K^2 FMAs per frame.
+constexpr int SOS_BWD_THREADS = 32;   // [6K+4] doubles per frame: 49 KiB of LDS at K = 32
+struct Sos { double a1, a2; };
+__device__ __forceinline__ Sos sos_from_logits(float l0f, float l1f, double rho, int rep) {
+    const double l0 = (double)l0f, l1 = (double)l1f;
     Sos s;
     if (rep == 0) {
-        s.a1 = 2.f * rho * tanhf(l0);
-        const float m = fabsf(s.a1);
-        s.a2 = 0.5f * ((2.f - m) * tanhf(l1) * rho + m);
+        s.a1 = 2.0 * rho * tanh(l0);
+        const double m = fabs(s.a1);
+        s.a2 = 0.5 * ((2.0 - m) * tanh(l1) * rho + m);
     } else if (rep == 1) {
-        const float r = rho / (1.f + expf(-l0));
-        s.a1 = -2.f * r * tanhf(l1);
+        const double r = rho / (1.0 + exp(-l0));
+        s.a1 = -2.0 * r * tanh(l1);
         s.a2 = r * r;
     } else {
-        const float z0 = rho * tanhf(l0), z1 = rho * tanhf(l1);
+        const double z0 = rho * tanh(l0), z1 = rho * tanh(l1);
         s.a1 = -(z0 + z1);
         s.a2 = z0 * z1;
     }
     return s;
 }
 // (g_a1, g_a2) -> (g_l0, g_l1)
-__device__ __forceinline__ void sos_backward(float l0, float l1, float rho, int rep, float g1, float g2, float& gl0,
-                                             float& gl1) {
+__device__ __forceinline__ void sos_backward(float l0f, float l1f, double rho, int rep, double g1, double g2, double& gl0,
+                                             double& gl1) {
+    const double l0 = (double)l0f, l1 = (double)l1f;
     if (rep == 0) {
-        const float t0 = tanhf(l0), t1 = tanhf(l1);
-        const float a1 = 2.f * rho * t0, m = fabsf(a1);
-        const float sgn = a1 > 0.f ? 1.f : (a1 < 0.f ? -1.f : 0.f);
-        const float da2_da1 = 0.5f * sgn * (1.f - t1 * rho);
-        gl0 = (g1 + g2 * da2_da1) * 2.f * rho * (1.f - t0 * t0);
-        gl1 = g2 * 0.5f * (2.f - m) * rho * (1.f - t1 * t1);
+        const double t0 = tanh(l0), t1 = tanh(l1);
+        const double a1 = 2.0 * rho * t0, m = fabs(a1);
+        const double sgn = a1 > 0.0 ? 1.0 : (a1 < 0.0 ? -1.0 : 0.0);
+        const double da2_da1 = 0.5 * sgn * (1.0 - t1 * rho);
+        gl0 = (g1 + g2 * da2_da1) * 2.0 * rho * (1.0 - t0 * t0);
+        gl1 = g2 * 0.5 * (2.0 - m) * rho * (1.0 - t1 * t1);
     } else if (rep == 1) {
-        const float sg = 1.f / (1.f + expf(-l0)), r = rho * sg, t1 = tanhf(l1);
-        const float dr = rho * sg * (1.f - sg);
-        gl0 = (g1 * (-2.f * t1) + g2 * 2.f * r) * dr;
-        gl1 = g1 * (-2.f * r) * (1.f - t1 * t1);
+        const double sg = 1.0 / (1.0 + exp(-l0)), r = rho * sg, t1 = tanh(l1);
+        const double dr = rho * sg * (1.0 - sg);
+        gl0 = (g1 * (-2.0 * t1) + g2 * 2.0 * r) * dr;
+        gl1 = g1 * (-2.0 * r) * (1.0 - t1 * t1);
     } else {
-        const float t0 = tanhf(l0), t1 = tanhf(l1);
-        const float z0 = rho * t0, z1 = rho * t1;
-        gl0 = (-g1 + g2 * z1) * rho * (1.f - t0 * t0);
-        gl1 = (-g1 + g2 * z0) * rho * (1.f - t1 * t1);
+        const double t0 = tanh(l0), t1 = tanh(l1);
+        const double z0 = rho * t0, z1 = rho * t1;
+        gl0 = (-g1 + g2 * z1) * rho * (1.0 - t0 * t0);
+        gl1 = (-g1 + g2 * z0) * rho * (1.0 - t1 * t1);
     }
 }
 // poly (length n+1) times (1 + a1 z^-1 + a2 z^-2), in place, length n+3
-__device__ __forceinline__ void mul_sos(float* p, int stride, int n, Sos s) {
-    p[(n + 1) * stride] = 0.f;
-    p[(n + 2) * stride] = 0.f;
+__device__ __forceinline__ void mul_sos(double* p, int stride, int n, Sos s) {
+    p[(n + 1) * stride] = 0.0;
+    p[(n + 2) * stride] = 0.0;
     for (int i = n + 2; i >= 1; --i) {
-        const float pm1 = p[(i - 1) * stride], pm2 = i >= 2 ? p[(i - 2) * stride] : 0.f;
-        p[i * stride] = fmaf(s.a2, pm2, fmaf(s.a1, pm1, p[i * stride]));
+        const double pm1 = p[(i - 1) * stride], pm2 = i >= 2 ? p[(i - 2) * stride] : 0.0;
+        p[i * stride] = fma(s.a2, pm2, fma(s.a1, pm1, p[i * stride]));
     }
 }
 
 __global__ __launch_bounds__(RC_THREADS) void sos2lpc_fwd_kernel(const float* __restrict__ logits, float* __restrict__ a,
                                                                  int64_t N, int K, float rho, int rep) {
-    extern __shared__ float smem[];   // [2K+1][RC_THREADS]
+    extern __shared__ double dsm[];   // [2K+1][RC_THREADS]
     const int lane = threadIdx.x;
     const int64_t row = (int64_t)blockIdx.x * RC_THREADS + lane;
     if (row >= N) return;
-    float* p = smem + lane;
+    double* p = dsm + lane;
     const float* lg = logits + row * 2 * K;
-    p[0] = 1.f;
-    for (int k = 0; k < K; ++k) mul_sos(p, RC_THREADS, 2 * k, sos_from_logits(lg[2 * k], lg[2 * k + 1], rho, rep));
+    p[0] = 1.0;
+    for (int k = 0; k < K; ++k)
+        mul_sos(p, RC_THREADS, 2 * k, sos_from_logits(lg[2 * k], lg[2 * k + 1], (double)rho, rep));
     float* out = a + row * 2 * K;
-    for (int i = 0; i < 2 * K; ++i) out[i] = p[(i + 1) * RC_THREADS];
+    for (int i = 0; i < 2 * K; ++i) out[i] = (float)p[(i + 1) * RC_THREADS];
 }
 
 // Sections are applied in index order, so going backwards: rebuild the product of sections 0..k-1, take the two
 // correlations for (g_a1, g_a2), pull the gradient back through section k.
-__global__ __launch_bounds__(RC_THREADS) void sos2lpc_bwd_kernel(const float* __restrict__ logits,
-                                                                 const float* __restrict__ g_a,
-                                                                 float* __restrict__ g_logits, int64_t N, int K,
-                                                                 float rho, int rep) {
-    extern __shared__ float smem[];   // poly [2K+1][T], grad [2K+3][T]
+__global__ __launch_bounds__(SOS_BWD_THREADS) void sos2lpc_bwd_kernel(const float* __restrict__ logits,
+                                                                      const float* __restrict__ g_a,
+                                                                      float* __restrict__ g_logits, int64_t N, int K,
+                                                                      float rho_f, int rep) {
+    extern __shared__ double dsm[];   // poly [2K+1][T], grad [2K+3][T], sections [2K][T]
+    constexpr int T = SOS_BWD_THREADS;
     const int lane = threadIdx.x;
-    const int64_t row = (int64_t)blockIdx.x * RC_THREADS + lane;
+    const int64_t row = (int64_t)blockIdx.x * T + lane;
     if (row >= N) return;
     const int M = 2 * K;
-    float* p = smem + lane;
-    float* g = smem + (size_t)(M + 1) * RC_THREADS + lane;
+    const double rho = (double)rho_f;
+    double* p = dsm + lane;
+    double* g = dsm + (size_t)(M + 1) * T + lane;
+    double* sec = dsm + (size_t)(2 * M + 4) * T + lane;
     const float* lg = logits + row * M;
     const float* ga = g_a + row * M;
-    g[0] = 0.f;
-    for (int i = 0; i < M; ++i) g[(i + 1) * RC_THREADS] = ga[i];
-    g[(M + 1) * RC_THREADS] = 0.f;
-    g[(M + 2) * RC_THREADS] = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const Sos s = sos_from_logits(lg[2 * k], lg[2 * k + 1], rho, rep);
+        sec[(2 * k) * T] = s.a1;
+        sec[(2 * k + 1) * T] = s.a2;
+    }
+    g[0] = 0.0;
+    for (int i = 0; i < M; ++i) g[(i + 1) * T] = (double)ga[i];
+    g[(M + 1) * T] = 0.0;
+    g[(M + 2) * T] = 0.0;
     float* gl = g_logits + row * M;
     for (int k = K - 1; k >= 0; --k) {
-        p[0] = 1.f;
-        for (int j = 0; j < k; ++j) mul_sos(p, RC_THREADS, 2 * j, sos_from_logits(lg[2 * j], lg[2 * j + 1], rho, rep));
+        p[0] = 1.0;
+        for (int j = 0; j < k; ++j) mul_sos(p, T, 2 * j, Sos{sec[(2 * j) * T], sec[(2 * j + 1) * T]});
         const int n = 2 * k;                       // degree of the product so far; new poly has degree n + 2
-        const Sos s = sos_from_logits(lg[2 * k], lg[2 * k + 1], rho, rep);
-        float g1 = 0.f, g2 = 0.f;
+        const Sos s{sec[(2 * k) * T], sec[(2 * k + 1) * T]};
+        double g1 = 0.0, g2 = 0.0;
         for (int i = 1; i <= n + 2; ++i) {
-            if (i - 1 <= n) g1 = fmaf(g[i * RC_THREADS], p[(i - 1) * RC_THREADS], g1);
-            if (i >= 2) g2 = fmaf(g[i * RC_THREADS], p[(i - 2) * RC_THREADS], g2);
+            if (i - 1 <= n) g1 = fma(g[i * T], p[(i - 1) * T], g1);
+            if (i >= 2) g2 = fma(g[i * T], p[(i - 2) * T], g2);
         }
         // g_prev[i] = g_new[i] + a1 g_new[i+1] + a2 g_new[i+2], ascending in place (reads run ahead of writes)
         for (int i = 0; i <= n; ++i)
-            g[i * RC_THREADS] = fmaf(s.a2, g[(i + 2) * RC_THREADS], fmaf(s.a1, g[(i + 1) * RC_THREADS], g[i * RC_THREADS]));
-        float gl0, gl1;
+            g[i * T] = fma(s.a2, g[(i + 2) * T], fma(s.a1, g[(i + 1) * T], g[i * T]));
+        double gl0, gl1;
         sos_backward(lg[2 * k], lg[2 * k + 1], rho, rep, g1, g2, gl0, gl1);
-        gl[2 * k] = gl0;
-        gl[2 * k + 1] = gl1;
+        gl[2 * k] = (float)gl0;
+        gl[2 * k + 1] = (float)gl1;
     }
 }
 
@@ -358,7 +374,7 @@ extern "C" int golf_sos2lpc_fwd_f32(const float* logits, float* a, int64_t N, in
     if (N < 1 || K < 1 || 2 * K > RC_MAX_ORDER || rep < 0 || rep > 2 || !(max_abs_pole > 0.f))
         return fail(GOLF_EINVAL, "sos2lpc_fwd: bad size / parameterisation (N=%lld K=%d rep=%d)", (long long)N, K, rep);
     hipLaunchKernelGGL(sos2lpc_fwd_kernel, dim3((unsigned)ceil_div(N, RC_THREADS)), dim3(RC_THREADS),
-                       sizeof(float) * (size_t)(2 * K + 1) * RC_THREADS, (hipStream_t)stream, logits, a, N, K,
+                       sizeof(double) * (size_t)(2 * K + 1) * RC_THREADS, (hipStream_t)stream, logits, a, N, K,
                        max_abs_pole, rep);
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
@@ -369,8 +385,8 @@ extern "C" int golf_sos2lpc_bwd_f32(const float* logits, const float* g_a, float
     if (!logits || !g_a || !g_logits) return fail(GOLF_EINVAL, "sos2lpc_bwd: null pointer");
     if (N < 1 || K < 1 || 2 * K > RC_MAX_ORDER || rep < 0 || rep > 2 || !(max_abs_pole > 0.f))
         return fail(GOLF_EINVAL, "sos2lpc_bwd: bad size / parameterisation (N=%lld K=%d rep=%d)", (long long)N, K, rep);
-    hipLaunchKernelGGL(sos2lpc_bwd_kernel, dim3((unsigned)ceil_div(N, RC_THREADS)), dim3(RC_THREADS),
-                       sizeof(float) * (size_t)(4 * K + 4) * RC_THREADS, (hipStream_t)stream, logits, g_a, g_logits, N, K,
+    hipLaunchKernelGGL(sos2lpc_bwd_kernel, dim3((unsigned)ceil_div(N, SOS_BWD_THREADS)), dim3(SOS_BWD_THREADS),
+                       sizeof(double) * (size_t)(6 * K + 4) * SOS_BWD_THREADS, (hipStream_t)stream, logits, g_a, g_logits, N, K,
                        max_abs_pole, rep);
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;

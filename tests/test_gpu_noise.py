@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import parity
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -109,3 +110,53 @@ def test_noise_band_random_offsets_and_statistics():
     louder = nb(ref, AudioTensor(lg + math.log(2.0), 240)).as_tensor()
     ratio = float(louder.square().mean() / a.square().mean())
     assert 3.0 < ratio < 5.5                                  # 4x the power for 2x the gains
+
+
+NB_WORST = parity.Worst("noise_band")
+
+# (B, T, F, hop, K, L, trailing gain rows with no sample under them) -> the branch of csrc/noise_band.hip it reaches
+NB_BRANCHES = [
+    (2, 300, 2, 512, 37, 64, 0),     # hop above the forward's block: one gain segment per block, nrows = 3
+    (2, 513, 3, 256, 64, 256, 0),    # hop equal to the block, the clamped tail sample at w = 1; offsets pinned to 0 and L - 1
+    (2, 700, 9, 300, 33, 128, 5),    # live = 3 of nseg = 8 segments: 5 of 9 gain rows receive nothing but the memset
+    (2, 130, 40, 240, 31, 64, 38),    # live = 1 of nseg = 39: 38 of 40 gain rows receive nothing
+    (3, 257, 2, 256, 5, 1, 0),       # Lb = 1 (mask 0)
+    (2, 100, 5, 25, 1, 8, 0),        # K = 1: a one-band pass, 31 idle slots of the backward's band chunk
+    (1, 40, 40, 1, 117, 16, 0),      # hop 1 stages 259 rows: passes of 58, 58 and an odd one-band tail pass
+    (2, 300, 1, 1, 37, 64, 0),       # F = 1: constant gain, r1 = r0, nseg = 1
+]
+
+
+@pytest.mark.parametrize("B,T,F,hop,K,L,n_dead", NB_BRANCHES)
+def test_noise_band_branches_vs_oracle(B, T, F, hop, K, L, n_dead):
+    from golf_amd import functional as GF
+    from oracle import golf_oracle as O
+
+    rng = np.random.default_rng(1000 * K + F)
+    bands = rng.normal(0, 0.3, (K, L)).astype(np.float32)
+    offs = rng.integers(0, L, (B, K))
+    if (hop, L) == (256, 256):
+        offs[:, 0], offs[:, 1], offs[1, 5], offs[0, K - 1] = 0, L - 1, L - 1, 0
+    lg = rng.normal(-2, 0.5, (B, F, K)).astype(np.float32)
+    gy = rng.normal(0, 1, (B, T)).astype(np.float32)
+    if F == 1:
+        # the oracle's upsampler returns length 1 for one frame: the same row twice at hop = T is the same constant gain
+        lg2 = np.repeat(lg, 2, axis=1)
+        ref = O.noise_band_forward(bands, offs, lg2, T, T)
+        ref_g = O.noise_band_backward(gy, bands, offs, lg2, T).sum(axis=1, keepdims=True)
+    else:
+        ref = O.noise_band_forward(bands, offs, lg, hop, T)
+        ref_g = O.noise_band_backward(gy, bands, offs, lg, hop)
+    assert ref.shape == (B, T)
+    lgt = dev(lg, True)
+    y = GF.noise_band(dev(bands), torch.from_numpy(offs).cuda(), lgt, hop, T)
+    (y * dev(gy)).sum().backward()
+    got_g = lgt.grad.cpu().numpy()
+    what = f"noise_band B{B} T{T} F{F} hop{hop} K{K} L{L}"
+    parity.check_global(NB_WORST, what + " fwd", y.detach().cpu().numpy(), ref, 1e-4)
+    parity.check_global(NB_WORST, what + " grad", got_g, ref_g, 2e-4)
+    if n_dead:
+        dead = F - n_dead                                    # first gain row with no sample under it
+        assert dead == (T - 1) // hop + 2
+        assert np.all(ref_g[:, dead:] == 0.0) and np.all(got_g[:, dead:] == 0.0)
+        assert np.all(got_g[:, dead - 1] != 0.0)

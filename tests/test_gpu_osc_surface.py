@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import parity
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -169,3 +170,54 @@ def test_decoder_trains_through_predicted_f0():
     torch.cuda.synchronize()
     for name, t in (("phase", phase.grad), ("weight", w.grad), ("table", dec.harm_oscillator.table.grad)):
         assert t is not None and torch.isfinite(t).all() and float(t.abs().max()) > 0, name
+
+
+WT_WORST = parity.Worst("wavetable_lookup")
+
+# (B, N, K, L, hop_t) -> the branch of golf_wavetable_lookup_{fwd,bwd}_f32 it reaches
+WT_CASES = [
+    (2, 700, 4, 16384, 240),     # 2*L*4 = 128 KiB: the backward without LDS, atomics straight to g_tables
+    (1, 300, 2, 8192, 100),      # exactly 64 KiB of dynamic LDS: the largest table of the LDS backward
+    (2, 50, 1, 64, 7),           # K = 1: both rows of every interval are the same table
+    (2, 1000, 3, 256, 100),      # 10 intervals over 3 tables: rows replicated past the last
+    (2, 40, 41, 32, 1),          # hop 1: rf = 0, one sample per workgroup
+    (1, 1300, 3, 128, 600),      # a segment longer than the 256-thread block: the sample loop strides
+]
+
+
+@pytest.mark.parametrize("B,N,K,L,hop_t", WT_CASES)
+def test_wavetable_lookup_branches_vs_oracle(B, N, K, L, hop_t):
+    """GF.wavetable_lookup against the float64 oracle: random tables, random phases in [0, 1) (L is a power of two, so
+    phase * L is exact in fp32 and both sides pick the same cell), each gradient requested alone and then both.  Phases 0,
+    the largest float below 1 and 1.0 itself are planted; there the forward and the table gradient are compared, the phase
+    gradient is not (the derivative jumps at a cell edge)."""
+    from golf_amd import functional as GF
+    from oracle import golf_oracle as O
+
+    rng = np.random.default_rng(L + N)
+    phase = rng.random((B, N), dtype=np.float32)
+    assert phase.max() < 1.0
+    planted = np.zeros((B, N), dtype=bool)
+    spots = rng.choice(N, 9, replace=False)
+    for i, n in enumerate(spots):
+        phase[i % B, n] = (0.0, np.nextafter(np.float32(1), np.float32(0)), 1.0)[i % 3]
+        planted[i % B, n] = True
+    tables = rng.normal(0, 1, (B, K, L)).astype(np.float32)
+    gy = rng.normal(0, 1, (B, N)).astype(np.float32)
+    ref = O.wavetable_generate(phase, tables, hop_t)
+    ref_gp, ref_gt = O.wavetable_generate_backward(gy, phase, tables, hop_t)
+    what = f"wavetable B{B} N{N} K{K} L{L} hop{hop_t}"
+    for need_p, need_t in ((True, False), (False, True), (True, True)):
+        pt, tt = dev(phase, need_p), dev(tables, need_t)
+        y = GF.wavetable_lookup(pt, tt, hop_t)
+        (y * dev(gy)).sum().backward()
+        torch.cuda.synchronize()
+        tag = f"{what} [{'p' if need_p else ''}{'t' if need_t else ''}]"
+        parity.check_global(WT_WORST, tag + " fwd", y.detach().cpu().numpy(), ref, 1e-4)
+        assert (pt.grad is None) == (not need_p) and (tt.grad is None) == (not need_t)
+        if need_t:
+            parity.check_global(WT_WORST, tag + " d/d table", tt.grad.cpu().numpy(), ref_gt, 2e-4)
+        if need_p:
+            parity.check_global(WT_WORST, tag + " d/d phase", np.where(planted, 0.0, pt.grad.cpu().numpy()),
+                                np.where(planted, 0.0, ref_gp), 5e-4)
+            assert torch.isfinite(pt.grad).all()
