@@ -196,7 +196,49 @@ class LTVMinimumPhaseFilter(LTVMinimumPhaseFilterPrecise):
         return AudioTensor(y)
 
 
-class LTVZeroPhaseFIRFilter(LTVFilterInterface):
+class _LTVFIRFilter(LTVFilterInterface):
+    """What the LTV FIR modules designed from log magnitudes share: the window vectors, the ``n_mag`` control split, the
+    input checks and the un-windowed kernels.  Every public class with a computation of its own defines its own
+    ``forward``, never a shared one that dispatches: the streams recognise the filter they can run block by block by the
+    identity of that function (``stream._branch_kind``)."""
+
+    def __init__(self, window: str, n_mag: int = None):
+        super().__init__()
+        self.window_fn = get_window_fn(window)
+        self._windows = {}
+        if n_mag is not None:
+            self.ctrl = wrap_ctrl_fn(split_size=(n_mag,), trsfm_fn=lambda x: (x,))
+
+    def _make_window(self, n: int, device) -> Tensor:
+        return self.window_fn(n).to(device=device, dtype=torch.float32).contiguous()
+
+    def _window(self, n: int, device) -> Tensor:
+        key = (n, str(device))
+        w = self._windows.get(key)
+        if w is None:
+            w = self._windows[key] = self._make_window(n, device)
+        return w
+
+    def windowing(self, kernel: Tensor) -> Tensor:
+        return kernel * self._window(kernel.shape[-1], kernel.device)
+
+    @staticmethod
+    def _get_fir(design, log_mag: Tensor) -> Tensor:
+        """(…,F,n_mag) -> (…,F,N) impulse responses of ``design``, *not* windowed."""
+        lm = log_mag.reshape(-1, log_mag.shape[-2], log_mag.shape[-1]) if log_mag.dim() != 3 else log_mag
+        n = 2 * (lm.shape[-1] - 1)
+        k = GF._fir_kernels(design, lm, torch.ones(n, device=lm.device))
+        return k.reshape(*log_mag.shape[:-1], n)
+
+    def _inputs(self, ex: AudioTensor, log_mag: AudioTensor):
+        assert ex.ndim == 2, ex.shape
+        assert log_mag.ndim == 3, log_mag.shape
+        assert ex.hop_length == 1, f"excitation must be at hop 1 (got {ex.hop_length})"
+        x = ex.as_tensor()
+        return x, log_mag.as_tensor(), self._window(2 * (log_mag.shape[-1] - 1), x.device), int(log_mag.hop_length)
+
+
+class LTVZeroPhaseFIRFilter(_LTVFIRFilter):
     """Noise filter of every GOLF decoder: per-frame zero-phase FIR designed from log magnitudes
     (reference models/filters.py:286-306,340-384).  ``forward`` runs golf_zero_phase_fir_kernels_f32 (cosine
     transform on the matrix cores) + golf_ltv_fir_frames_{fwd,bwd}_f32; differentiable w.r.t. ``ex`` and ``log_mag``.
@@ -205,39 +247,16 @@ class LTVZeroPhaseFIRFilter(LTVFilterInterface):
     reference; it is accepted and validated for config compatibility, there is one kernel here."""
 
     def __init__(self, window: str, conv_method: str = "direct", n_mag: int = None):
-        super().__init__()
+        super().__init__(window=window, n_mag=n_mag)
         if conv_method not in ("direct", "fft"):
             raise ValueError(f"Unknown conv_method: {conv_method}")
-        self.window_fn = get_window_fn(window)
-        self._windows = {}
-        if n_mag is not None:
-            self.ctrl = wrap_ctrl_fn(split_size=(n_mag,), trsfm_fn=lambda x: (x,))
-
-    def _window(self, n: int, device) -> Tensor:
-        key = (n, str(device))
-        w = self._windows.get(key)
-        if w is None:
-            w = self._windows[key] = self.window_fn(n).to(device=device, dtype=torch.float32).contiguous()
-        return w
 
     def get_zero_phase_fir(self, log_mag: Tensor) -> Tensor:
         """(…,F,n_mag) -> (…,F,N) zero-phase impulse responses, *not* windowed (filters.py:294-300)."""
-        lm = log_mag.reshape(-1, log_mag.shape[-2], log_mag.shape[-1]) if log_mag.dim() != 3 else log_mag
-        n = 2 * (lm.shape[-1] - 1)
-        k = GF.zero_phase_fir_kernels(lm, torch.ones(n, device=lm.device))
-        return k.reshape(*log_mag.shape[:-1], n)
-
-    def windowing(self, kernel: Tensor) -> Tensor:
-        return kernel * self._window(kernel.shape[-1], kernel.device)
+        return self._get_fir(GF.ZERO_PHASE_FIR, log_mag)
 
     def forward(self, ex: AudioTensor, log_mag: AudioTensor) -> AudioTensor:
-        assert ex.ndim == 2, ex.shape
-        assert log_mag.ndim == 3, log_mag.shape
-        assert ex.hop_length == 1, f"excitation must be at hop 1 (got {ex.hop_length})"
-        n = 2 * (log_mag.shape[-1] - 1)
-        y = GF.zero_phase_fir_filter(ex.as_tensor(), log_mag.as_tensor(), self._window(n, ex.as_tensor().device),
-                                     int(log_mag.hop_length))
-        return AudioTensor(y)
+        return AudioTensor(GF.zero_phase_fir_filter(*self._inputs(ex, log_mag)))
 
 
 class LTVZeroPhaseFIRFilterPrecise(LTVZeroPhaseFIRFilter):
@@ -249,13 +268,7 @@ class LTVZeroPhaseFIRFilterPrecise(LTVZeroPhaseFIRFilter):
         super().__init__(window=window, conv_method="direct", n_mag=n_mag)
 
     def forward(self, ex: AudioTensor, log_mag: AudioTensor) -> AudioTensor:
-        assert ex.ndim == 2, ex.shape
-        assert log_mag.ndim == 3, log_mag.shape
-        assert ex.hop_length == 1, f"excitation must be at hop 1 (got {ex.hop_length})"
-        n = 2 * (log_mag.shape[-1] - 1)
-        y = GF.zero_phase_fir_filter_precise(ex.as_tensor(), log_mag.as_tensor(),
-                                             self._window(n, ex.as_tensor().device), int(log_mag.hop_length))
-        return AudioTensor(y)
+        return AudioTensor(GF.zero_phase_fir_filter_precise(*self._inputs(ex, log_mag)))
 
 
 class LTVAPZeroPhaseFIRFilter(LTVZeroPhaseFIRFilter):
@@ -294,7 +307,7 @@ class LTIAcousticFilter(FilterInterface):
         return torch.cat([self.kernel, torch.ones(1, device=self.kernel.device)]).flip(0)
 
 
-class LTVMinimumPhaseFIRFilterPrecise(LTVFilterInterface):
+class LTVMinimumPhaseFIRFilterPrecise(_LTVFIRFilter):
     """Sample-wise minimum-phase FIR filter (reference models/filters.py:198-241): per-frame minimum-phase impulse
     responses designed from log magnitudes (same magnitude response as the zero-phase filter, response from tap 0, no
     lookahead), linearly interpolated to sample rate, y[t] = sum_j h_t[j] ex[t-j].  ``forward`` runs
@@ -304,37 +317,13 @@ class LTVMinimumPhaseFIRFilterPrecise(LTVFilterInterface):
     ``n_mag`` (not in the reference's signature; the zero-phase twin has it too) installs the ``.ctrl`` split that lets
     the class sit in a decoder."""
 
-    def __init__(self, window: str, n_mag: int = None):
-        super().__init__()
-        self.window_fn = get_window_fn(window)
-        self._windows = {}
-        if n_mag is not None:
-            self.ctrl = wrap_ctrl_fn(split_size=(n_mag,), trsfm_fn=lambda x: (x,))
-
-    def _window(self, n: int, device) -> Tensor:
-        key = (n, str(device))
-        w = self._windows.get(key)
-        if w is None:
-            w = self._windows[key] = GF.min_phase_window(self.window_fn, n, device)
-        return w
+    def _make_window(self, n: int, device) -> Tensor:
+        return GF.min_phase_window(self.window_fn, n, device)
 
     @staticmethod
     def get_minimum_phase_fir(log_mag: Tensor) -> Tensor:
         """(…,F,n_mag) -> (…,F,N) minimum-phase impulse responses, *not* windowed (filters.py:203-214)."""
-        lm = log_mag.reshape(-1, log_mag.shape[-2], log_mag.shape[-1]) if log_mag.dim() != 3 else log_mag
-        n = 2 * (lm.shape[-1] - 1)
-        k = GF.min_phase_fir_kernels(lm, torch.ones(n, device=lm.device))
-        return k.reshape(*log_mag.shape[:-1], n)
-
-    def windowing(self, kernel: Tensor) -> Tensor:
-        return kernel * self._window(kernel.shape[-1], kernel.device)
-
-    def _inputs(self, ex: AudioTensor, log_mag: AudioTensor):
-        assert ex.ndim == 2, ex.shape
-        assert log_mag.ndim == 3, log_mag.shape
-        assert ex.hop_length == 1, f"excitation must be at hop 1 (got {ex.hop_length})"
-        x = ex.as_tensor()
-        return x, log_mag.as_tensor(), self._window(2 * (log_mag.shape[-1] - 1), x.device), int(log_mag.hop_length)
+        return _LTVFIRFilter._get_fir(GF.MIN_PHASE_FIR, log_mag)
 
     def forward(self, ex: AudioTensor, log_mag: AudioTensor) -> AudioTensor:
         return AudioTensor(GF.min_phase_fir_filter_precise(*self._inputs(ex, log_mag)))

@@ -5,6 +5,7 @@ Every function raises if the tensors are not fp32 ROCm-device tensors — no CPU
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 
 import torch
@@ -1270,202 +1271,51 @@ def noise_band(bands: torch.Tensor, offsets: torch.Tensor, log_gain: torch.Tenso
 
 
 # ------------------------------------------------------------------------------------------------
-# zero-phase FIR noise filter (reference models/filters.py:286-384)
+# LTV FIR filters designed from log magnitudes: zero-phase (the noise filter, reference models/filters.py:286-384) and
+# minimum-phase (its causal twin, reference models/filters.py:198-283).  One code path; what differs is in _FIRDesign.
 # ------------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class _FIRDesign:
+    """What tells the two designs apart: the name used in messages and cache keys, whether the frame filter that applies
+    the kernels is causal, and the C entry points of the design (include/golf_amd.h)."""
+    kind: str
+    causal: bool
+    basis_bytes: str
+    basis: str
+    kernels: str
+    kernels_bwd: str
+
+
+ZERO_PHASE_FIR = _FIRDesign("zero_phase", False, "golf_zero_phase_fir_basis_bytes", "golf_zero_phase_fir_basis_f32",
+                            "golf_zero_phase_fir_kernels_f32", "golf_zero_phase_fir_kernels_bwd_f32")
+MIN_PHASE_FIR = _FIRDesign("min_phase", True, "golf_min_phase_fir_basis_bytes", "golf_min_phase_fir_basis_f32",
+                           "golf_min_phase_fir_kernels_f32", "golf_min_phase_fir_kernels_bwd_f32")
+
 _basis_cache = {}
 
 
-def zero_phase_fir_basis(n_mag: int, device) -> torch.Tensor:
-    """The constant cosine-transform matrix for ``n_mag`` bins (both orientations), built once per device."""
+def _fir_basis(design: _FIRDesign, n_mag: int, device) -> torch.Tensor:
     dev = torch.device(device)
-    key = (n_mag, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = (design.kind, n_mag, dev.index if dev.index is not None else torch.cuda.current_device())
     b = _basis_cache.get(key)
     if b is None:
         lib = _lib.load()
-        nbytes = lib.golf_zero_phase_fir_basis_bytes(n_mag)
+        nbytes = getattr(lib, design.basis_bytes)(n_mag)
         b = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        _lib.check(lib.golf_zero_phase_fir_basis_f32(n_mag, b.data_ptr(), nbytes, _lib.stream_ptr()),
-                   "golf_zero_phase_fir_basis_f32")
+        _lib.check(getattr(lib, design.basis)(n_mag, b.data_ptr(), nbytes, _lib.stream_ptr()), design.basis)
         _basis_cache[key] = b
     return b
 
 
-def fir_frames_length(T: int, F: int, N: int, hop: int) -> int:
-    lib = _lib.load()
-    n = lib.golf_ltv_fir_frames_length(T, F, N, hop)
-    if n < 0:
-        raise _lib.GolfError(lib.golf_last_error().decode(errors="replace"))
-    return n
-
-
-def _zp_kernels_raw(lib, log_mag, window, basis):
-    B, F, n_mag = log_mag.shape
-    KS = lib.golf_zero_phase_fir_row_stride(n_mag)
-    kern = torch.empty(B * F, KS, dtype=torch.float32, device=log_mag.device)
-    _lib.check(lib.golf_zero_phase_fir_kernels_f32(log_mag.data_ptr(), window.data_ptr(), basis.data_ptr(),
-                                                   kern.data_ptr(), B * F, n_mag, _lib.stream_ptr()),
-               "golf_zero_phase_fir_kernels_f32")
-    return kern
-
-
-def zero_phase_fir_kernels(log_mag: torch.Tensor, window: torch.Tensor) -> torch.Tensor:
-    """(B,F,n_mag) log magnitudes -> (B,F,N) windowed zero-phase FIR kernels, N = 2*(n_mag-1) (no autograd)."""
-    _lib.require_device(log_mag, window)
-    lib = _lib.load()
-    log_mag = log_mag.detach().contiguous()
-    B, F, n_mag = log_mag.shape
-    N = 2 * (n_mag - 1)
-    kern = _zp_kernels_raw(lib, log_mag, window.contiguous(), zero_phase_fir_basis(n_mag, log_mag.device))
-    return kern.view(B, F, -1)[..., :N]
-
-
-class _ZPKernels(torch.autograd.Function):
-    """(B,F,n_mag) log magnitudes -> (B*F, row_stride) windowed zero-phase FIR rows (cosine transform on the MFMAs)."""
-
-    @staticmethod
-    @_amp_fwd
-    def forward(ctx, log_mag, window):
-        _lib.require_device(log_mag, window)
-        lib = _lib.load()
-        log_mag = log_mag.contiguous()
-        window = window.contiguous()
-        n_mag = log_mag.shape[2]
-        if window.numel() != 2 * (n_mag - 1):
-            raise _lib.GolfError(f"zero_phase_fir: window has {window.numel()} taps, expected {2 * (n_mag - 1)}")
-        basis = zero_phase_fir_basis(n_mag, log_mag.device)
-        kern = _zp_kernels_raw(lib, log_mag, window, basis)
-        ctx.save_for_backward(log_mag, window, basis)
-        return kern
-
-    @staticmethod
-    @_amp_bwd
-    def backward(ctx, g_kern):
-        log_mag, window, basis = ctx.saved_tensors
-        lib = _lib.load()
-        g_kern = g_kern.contiguous()
-        B, F, n_mag = log_mag.shape
-        g_lm = torch.empty_like(log_mag)
-        _lib.check(lib.golf_zero_phase_fir_kernels_bwd_f32(g_kern.data_ptr(), log_mag.data_ptr(), window.data_ptr(),
-                                                           basis.data_ptr(), g_lm.data_ptr(), B * F, n_mag,
-                                                           _lib.stream_ptr()),
-                   "golf_zero_phase_fir_kernels_bwd_f32")
-        return g_lm, None
-
-
-class _FIRFrames(torch.autograd.Function):
-    """Per-frame FIR with kernel rows kern (B*F, row_stride): output frame f uses row f + frame0."""
-
-    @staticmethod
-    @_amp_fwd
-    def forward(ctx, ex, kern, F, N, hop, frame0):
-        _lib.require_device(ex, kern)
-        lib = _lib.load()
-        ex = _rows(ex)
-        kern = kern.contiguous()
-        B, T = ex.shape
-        if kern.shape[0] != B * F:
-            raise _lib.GolfError(f"fir_frames: {kern.shape[0]} kernel rows for B={B}, F={F}")
-        Ty = fir_frames_length(T, F - frame0, N, hop)
-        y = torch.empty(B, Ty, dtype=torch.float32, device=ex.device)
-        _lib.check(lib.golf_ltv_fir_frames_fwd_f32(ex.data_ptr(), ex.stride(0), kern.data_ptr(), kern.shape[1],
-                                                   y.data_ptr(), y.stride(0), B, T, F, N, hop, frame0,
-                                                   _lib.stream_ptr()),
-                   "golf_ltv_fir_frames_fwd_f32")
-        ctx.save_for_backward(ex, kern)
-        ctx.geom = (F, N, hop, frame0)
-        return y
-
-    @staticmethod
-    @_amp_bwd
-    def backward(ctx, gy):
-        ex, kern = ctx.saved_tensors
-        F, N, hop, frame0 = ctx.geom
-        lib = _lib.load()
-        gy = _rows(gy)
-        B, T = ex.shape
-        need_ex, need_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        g_ex = torch.empty_like(ex) if need_ex else None
-        g_kern = torch.empty_like(kern) if need_k else None
-        _lib.check(lib.golf_ltv_fir_frames_bwd_f32(gy.data_ptr(), gy.stride(0), ex.data_ptr(), ex.stride(0),
-                                                   kern.data_ptr(), kern.shape[1],
-                                                   g_ex.data_ptr() if need_ex else None,
-                                                   g_ex.stride(0) if need_ex else 0,
-                                                   g_kern.data_ptr() if need_k else None,
-                                                   B, T, F, N, hop, frame0, _lib.stream_ptr()),
-                   "golf_ltv_fir_frames_bwd_f32")
-        # (the padding taps [N, row stride) carry no gradient: the kernel writes their zeros itself)
-        return g_ex, g_kern, None, None, None, None
-
-
-def zero_phase_fir_filter(ex: torch.Tensor, log_mag: torch.Tensor, window: torch.Tensor, hop: int) -> torch.Tensor:
-    """LTVZeroPhaseFIRFilter.forward on plain tensors: ex (B,T), log_mag (B,F,n_mag) at ``hop`` -> (B, nfr*hop);
-    differentiable w.r.t. ex and log_mag."""
-    if log_mag.dim() != 3 or log_mag.shape[0] != ex.shape[0]:
-        raise _lib.GolfError(f"zero_phase_fir_filter: ex {tuple(ex.shape)} vs log_mag {tuple(log_mag.shape)}")
-    F, n_mag = log_mag.shape[1], log_mag.shape[2]
-    kern = _ZPKernels.apply(log_mag, window)
-    return _FIRFrames.apply(ex, kern, F, 2 * (n_mag - 1), hop, 0)
-
-
-def zero_phase_fir_filter_precise(ex: torch.Tensor, log_mag: torch.Tensor, window: torch.Tensor, hop: int) -> torch.Tensor:
-    """LTVZeroPhaseFIRFilterPrecise.forward (reference models/filters.py:308-337): the kernels are linearly
-    interpolated to sample rate, y[t] = sum_k pad(ex)[t+k] * ((1-w_t) K_f[k] + w_t K_{f+1}[k]), f = t // hop,
-    w_t = (t % hop)/hop, output length min(T, (F-1)*hop+1).  Evaluated as two frame FIRs (kernel rows f and f+1 over
-    the same signal) blended per sample; the single sample t = (F-1)*hop is a dot product with the last kernel."""
-    if log_mag.dim() != 3 or log_mag.shape[0] != ex.shape[0]:
-        raise _lib.GolfError(f"zero_phase_fir_filter_precise: ex {tuple(ex.shape)} vs log_mag {tuple(log_mag.shape)}")
-    B, T = ex.shape
-    F, n_mag = log_mag.shape[1], log_mag.shape[2]
-    if F < 2:
-        raise _lib.GolfError("zero_phase_fir_filter_precise: need at least 2 frames")
-    N = 2 * (n_mag - 1)
-    P = (N - 1) // 2
-    Tfull = (F - 1) * hop + 1
-    Tout = min(T, Tfull)
-    kern = _ZPKernels.apply(log_mag, window)
-    # the samples the outputs t < Tfull can reach: ex[t + k - P], k < N  ->  indices < Tfull + N-1-P (zeros past T)
-    Tin = Tfull + N - 1 - P
-    x = ex[:, :Tin]
-    if x.shape[1] < Tin:
-        x = torch.nn.functional.pad(x, (0, Tin - x.shape[1]))
-    ya = _FIRFrames.apply(x, kern, F, N, hop, 0)[:, : (F - 1) * hop]
-    yb = _FIRFrames.apply(x, kern, F, N, hop, 1)[:, : (F - 1) * hop]
-    w = (torch.arange((F - 1) * hop, device=ex.device) % hop).to(torch.float32) / hop
-    main = ya + w * (yb - ya)
-    tail = torch.nn.functional.pad(x, (P, 0))[:, Tfull - 1: Tfull - 1 + N]  # pad(ex)[Tfull-1 + k], k < N
-    last = (tail * kern.view(B, F, -1)[:, F - 1, :N]).sum(-1, keepdim=True)
-    return torch.cat([main, last], dim=1)[:, :Tout]
-
-
-def ltv_fir_frames(ex: torch.Tensor, kernels: torch.Tensor, hop: int) -> torch.Tensor:
-    """Frame-wise FIR with arbitrary per-frame kernels (B,F,N): y[b,f*hop+n] = sum_k pad(ex)[b,f*hop+n+k] *
-    kernels[b,f,k]; differentiable w.r.t. both."""
-    B, F, N = kernels.shape
-    KS = (N + 15) // 16 * 16
-    kern = torch.nn.functional.pad(kernels.reshape(B * F, N), (0, KS - N))
-    return _FIRFrames.apply(ex, kern, F, N, hop, 0)
-
-
-# ------------------------------------------------------------------------------------------------
-# minimum-phase FIR filter (reference models/filters.py:198-283): the causal twin of the zero-phase filter
-# ------------------------------------------------------------------------------------------------
-_mp_basis_cache = {}
+def zero_phase_fir_basis(n_mag: int, device) -> torch.Tensor:
+    """The constant cosine-transform matrix for ``n_mag`` bins (both orientations), built once per device."""
+    return _fir_basis(ZERO_PHASE_FIR, n_mag, device)
 
 
 def min_phase_fir_basis(n_mag: int, device) -> torch.Tensor:
     """The constant matrices of the minimum-phase design for ``n_mag`` bins (Hilbert transform on the half spectrum,
     cosine and sine synthesis, both orientations), built once per device."""
-    dev = torch.device(device)
-    key = (n_mag, dev.index if dev.index is not None else torch.cuda.current_device())
-    b = _mp_basis_cache.get(key)
-    if b is None:
-        lib = _lib.load()
-        nbytes = lib.golf_min_phase_fir_basis_bytes(n_mag)
-        b = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        _lib.check(lib.golf_min_phase_fir_basis_f32(n_mag, b.data_ptr(), nbytes, _lib.stream_ptr()),
-                   "golf_min_phase_fir_basis_f32")
-        _mp_basis_cache[key] = b
-    return b
+    return _fir_basis(MIN_PHASE_FIR, n_mag, device)
 
 
 def min_phase_window(window_fn, n: int, device=None) -> torch.Tensor:
@@ -1476,120 +1326,138 @@ def min_phase_window(window_fn, n: int, device=None) -> torch.Tensor:
     return w.to(device=device).contiguous()
 
 
-def fir_frames_causal_length(T: int, F: int, N: int, hop: int) -> int:
-    lib = _lib.load()
-    n = lib.golf_ltv_fir_frames_causal_length(T, F, N, hop)
-    if n < 0:
-        raise _lib.GolfError(lib.golf_last_error().decode(errors="replace"))
-    return n
-
-
-def _mp_check_window(log_mag, window):
-    n_mag = log_mag.shape[2]
-    if window.numel() != 2 * (n_mag - 1):
-        raise _lib.GolfError(f"min_phase_fir: window has {window.numel()} taps, expected {2 * (n_mag - 1)}")
-
-
-def _mp_kernels_raw(lib, log_mag, window, basis):
+def _fir_kernels_raw(design: _FIRDesign, log_mag, window, basis):
+    """Contiguous device tensors log_mag (B,F,n_mag), window (N), basis -> (B*F, row_stride) windowed kernel rows.  Every
+    call that takes a window ends here, so this is where its length is checked: the kernel reads N taps of it."""
     B, F, n_mag = log_mag.shape
+    if window.numel() != 2 * (n_mag - 1):
+        raise _lib.GolfError(f"{design.kind}_fir: window has {window.numel()} taps, expected {2 * (n_mag - 1)}")
+    lib = _lib.load()
     KS = lib.golf_zero_phase_fir_row_stride(n_mag)
     kern = torch.empty(B * F, KS, dtype=torch.float32, device=log_mag.device)
-    _lib.check(lib.golf_min_phase_fir_kernels_f32(log_mag.data_ptr(), window.data_ptr(), basis.data_ptr(),
-                                                  kern.data_ptr(), B * F, n_mag, _lib.stream_ptr()),
-               "golf_min_phase_fir_kernels_f32")
+    _lib.check(getattr(lib, design.kernels)(log_mag.data_ptr(), window.data_ptr(), basis.data_ptr(), kern.data_ptr(),
+                                            B * F, n_mag, _lib.stream_ptr()),
+               design.kernels)
     return kern
+
+
+def _fir_kernels(design: _FIRDesign, log_mag: torch.Tensor, window: torch.Tensor) -> torch.Tensor:
+    _lib.require_device(log_mag, window)
+    log_mag = log_mag.detach().contiguous()
+    B, F, n_mag = log_mag.shape
+    kern = _fir_kernels_raw(design, log_mag, window.contiguous(), _fir_basis(design, n_mag, log_mag.device))
+    return kern.view(B, F, -1)[..., :2 * (n_mag - 1)]
+
+
+def zero_phase_fir_kernels(log_mag: torch.Tensor, window: torch.Tensor) -> torch.Tensor:
+    """(B,F,n_mag) log magnitudes -> (B,F,N) windowed zero-phase FIR kernels, N = 2*(n_mag-1) (no autograd)."""
+    return _fir_kernels(ZERO_PHASE_FIR, log_mag, window)
 
 
 def min_phase_fir_kernels(log_mag: torch.Tensor, window: torch.Tensor) -> torch.Tensor:
     """(B,F,n_mag) log magnitudes -> (B,F,N) minimum-phase FIR kernels times ``window`` (N taps), N = 2*(n_mag-1)
     (no autograd)."""
-    _lib.require_device(log_mag, window)
-    lib = _lib.load()
-    log_mag = log_mag.detach().contiguous()
-    window = window.contiguous()
-    _mp_check_window(log_mag, window)
-    B, F, n_mag = log_mag.shape
-    N = 2 * (n_mag - 1)
-    kern = _mp_kernels_raw(lib, log_mag, window, min_phase_fir_basis(n_mag, log_mag.device))
-    return kern.view(B, F, -1)[..., :N]
+    return _fir_kernels(MIN_PHASE_FIR, log_mag, window)
 
 
-class _MPKernels(torch.autograd.Function):
-    """(B,F,n_mag) log magnitudes -> (B*F, row_stride) windowed minimum-phase FIR rows (two contractions on the MFMAs)."""
+class _FIRKernels(torch.autograd.Function):
+    """(B,F,n_mag) log magnitudes -> (B*F, row_stride) windowed FIR rows of ``design``, on the MFMAs (zero-phase: a cosine
+    transform; minimum-phase: two contractions)."""
 
     @staticmethod
     @_amp_fwd
-    def forward(ctx, log_mag, window):
+    def forward(ctx, log_mag, window, design):
         _lib.require_device(log_mag, window)
-        lib = _lib.load()
         log_mag = log_mag.contiguous()
         window = window.contiguous()
-        _mp_check_window(log_mag, window)
-        basis = min_phase_fir_basis(log_mag.shape[2], log_mag.device)
-        kern = _mp_kernels_raw(lib, log_mag, window, basis)
+        basis = _fir_basis(design, log_mag.shape[2], log_mag.device)
+        kern = _fir_kernels_raw(design, log_mag, window, basis)
         ctx.save_for_backward(log_mag, window, basis)
+        ctx.design = design
         return kern
 
     @staticmethod
     @_amp_bwd
     def backward(ctx, g_kern):
         log_mag, window, basis = ctx.saved_tensors
-        lib = _lib.load()
+        name = ctx.design.kernels_bwd
         g_kern = g_kern.contiguous()
         B, F, n_mag = log_mag.shape
         g_lm = torch.empty_like(log_mag)
-        _lib.check(lib.golf_min_phase_fir_kernels_bwd_f32(g_kern.data_ptr(), log_mag.data_ptr(), window.data_ptr(),
-                                                          basis.data_ptr(), g_lm.data_ptr(), B * F, n_mag,
-                                                          _lib.stream_ptr()),
-                   "golf_min_phase_fir_kernels_bwd_f32")
-        return g_lm, None
+        _lib.check(getattr(_lib.load(), name)(g_kern.data_ptr(), log_mag.data_ptr(), window.data_ptr(), basis.data_ptr(),
+                                              g_lm.data_ptr(), B * F, n_mag, _lib.stream_ptr()),
+                   name)
+        return g_lm, None, None
 
 
-class _FIRFramesCausal(torch.autograd.Function):
-    """Causal per-frame FIR with kernel rows kern (B*F, row_stride): y[b,f*hop+n] = sum_j kern[f+frame0][j] ex[b,f*hop+n-j]."""
+def _fir_frames_name(causal: bool) -> str:
+    return "fir_frames_causal" if causal else "fir_frames"
+
+
+def _fir_frames_length(causal: bool, T: int, F: int, N: int, hop: int) -> int:
+    lib = _lib.load()
+    n = getattr(lib, f"golf_ltv_{_fir_frames_name(causal)}_length")(T, F, N, hop)
+    if n < 0:
+        raise _lib.GolfError(lib.golf_last_error().decode(errors="replace"))
+    return n
+
+
+def fir_frames_length(T: int, F: int, N: int, hop: int) -> int:
+    return _fir_frames_length(False, T, F, N, hop)
+
+
+def fir_frames_causal_length(T: int, F: int, N: int, hop: int) -> int:
+    return _fir_frames_length(True, T, F, N, hop)
+
+
+class _FIRFrames(torch.autograd.Function):
+    """Per-frame FIR with kernel rows kern (B*F, row_stride); output frame f uses row f + frame0.  Zero-phase alignment:
+    y[b,f*hop+n] = sum_k kern[f+frame0][k] pad(ex)[b,f*hop+n+k]; ``causal``: sum_j kern[f+frame0][j] ex[b,f*hop+n-j]."""
 
     @staticmethod
     @_amp_fwd
-    def forward(ctx, ex, kern, F, N, hop, frame0):
+    def forward(ctx, ex, kern, F, N, hop, frame0, causal):
         _lib.require_device(ex, kern)
         lib = _lib.load()
+        who = _fir_frames_name(causal)
         ex = _rows(ex)
         kern = kern.contiguous()
         B, T = ex.shape
         if kern.shape[0] != B * F:
-            raise _lib.GolfError(f"fir_frames_causal: {kern.shape[0]} kernel rows for B={B}, F={F}")
-        Ty = fir_frames_causal_length(T, F - frame0, N, hop)
+            raise _lib.GolfError(f"{who}: {kern.shape[0]} kernel rows for B={B}, F={F}")
+        Ty = _fir_frames_length(causal, T, F - frame0, N, hop)
         y = torch.empty(B, Ty, dtype=torch.float32, device=ex.device)
-        _lib.check(lib.golf_ltv_fir_frames_causal_fwd_f32(ex.data_ptr(), ex.stride(0), kern.data_ptr(), kern.shape[1],
-                                                          y.data_ptr(), y.stride(0), B, T, F, N, hop, frame0,
-                                                          _lib.stream_ptr()),
-                   "golf_ltv_fir_frames_causal_fwd_f32")
+        name = f"golf_ltv_{who}_fwd_f32"
+        _lib.check(getattr(lib, name)(ex.data_ptr(), ex.stride(0), kern.data_ptr(), kern.shape[1], y.data_ptr(),
+                                      y.stride(0), B, T, F, N, hop, frame0, _lib.stream_ptr()),
+                   name)
         ctx.save_for_backward(ex, kern)
-        ctx.geom = (F, N, hop, frame0)
+        ctx.geom = (F, N, hop, frame0, causal)
         return y
 
     @staticmethod
     @_amp_bwd
     def backward(ctx, gy):
         ex, kern = ctx.saved_tensors
-        F, N, hop, frame0 = ctx.geom
-        lib = _lib.load()
+        F, N, hop, frame0, causal = ctx.geom
         gy = _rows(gy)
         B, T = ex.shape
         need_ex, need_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g_ex = torch.empty_like(ex) if need_ex else None
         g_kern = torch.empty_like(kern) if need_k else None
-        _lib.check(lib.golf_ltv_fir_frames_causal_bwd_f32(gy.data_ptr(), gy.stride(0), ex.data_ptr(), ex.stride(0),
-                                                          kern.data_ptr(), kern.shape[1],
-                                                          g_ex.data_ptr() if need_ex else None,
-                                                          g_ex.stride(0) if need_ex else 0,
-                                                          g_kern.data_ptr() if need_k else None,
-                                                          B, T, F, N, hop, frame0, _lib.stream_ptr()),
-                   "golf_ltv_fir_frames_causal_bwd_f32")
-        return g_ex, g_kern, None, None, None, None
+        name = f"golf_ltv_{_fir_frames_name(causal)}_bwd_f32"
+        _lib.check(getattr(_lib.load(), name)(gy.data_ptr(), gy.stride(0), ex.data_ptr(), ex.stride(0),
+                                              kern.data_ptr(), kern.shape[1],
+                                              g_ex.data_ptr() if need_ex else None,
+                                              g_ex.stride(0) if need_ex else 0,
+                                              g_kern.data_ptr() if need_k else None,
+                                              B, T, F, N, hop, frame0, _lib.stream_ptr()),
+                   name)
+        # (the padding taps [N, row stride) carry no gradient: the kernel writes their zeros itself)
+        return g_ex, g_kern, None, None, None, None, None
 
 
-def _mp_check_frames(who: str, ex, F: int, hop: int) -> None:
+def _check_causal_frames(who: str, ex, F: int, hop: int) -> None:
     T = ex.shape[-1]
     if T < hop:
         raise _lib.GolfError(f"{who}: excitation (T={T}) shorter than one hop ({hop})")
@@ -1597,15 +1465,71 @@ def _mp_check_frames(who: str, ex, F: int, hop: int) -> None:
         raise _lib.GolfError(f"{who}: {T // hop} frames of excitation (T={T}, hop={hop}) but only {F} kernels")
 
 
+def _check_fir_inputs(who: str, ex, log_mag) -> None:
+    if log_mag.dim() != 3 or ex.dim() != 2 or log_mag.shape[0] != ex.shape[0]:
+        raise _lib.GolfError(f"{who}: ex {tuple(ex.shape)} vs log_mag {tuple(log_mag.shape)}")
+
+
+def _fir_filter(design: _FIRDesign, ex, log_mag, window, hop: int) -> torch.Tensor:
+    who = f"{design.kind}_fir_filter"
+    _check_fir_inputs(who, ex, log_mag)
+    F, n_mag = log_mag.shape[1], log_mag.shape[2]
+    if design.causal:
+        _check_causal_frames(who, ex, F, hop)
+    kern = _FIRKernels.apply(log_mag, window, design)
+    return _FIRFrames.apply(ex, kern, F, 2 * (n_mag - 1), hop, 0, design.causal)
+
+
+def zero_phase_fir_filter(ex: torch.Tensor, log_mag: torch.Tensor, window: torch.Tensor, hop: int) -> torch.Tensor:
+    """LTVZeroPhaseFIRFilter.forward on plain tensors: ex (B,T), log_mag (B,F,n_mag) at ``hop`` -> (B, nfr*hop);
+    differentiable w.r.t. ex and log_mag."""
+    return _fir_filter(ZERO_PHASE_FIR, ex, log_mag, window, hop)
+
+
 def min_phase_fir_filter(ex: torch.Tensor, log_mag: torch.Tensor, window: torch.Tensor, hop: int) -> torch.Tensor:
     """LTVMinimumPhaseFIRFilter.forward on plain tensors: ex (B,T), log_mag (B,F,n_mag) at ``hop``, window (N) ->
     (B, (T // hop) * hop), y[b,f*hop+n] = sum_j kernel[b,f,j] ex[b,f*hop+n-j]; differentiable w.r.t. ex and log_mag."""
-    if log_mag.dim() != 3 or ex.dim() != 2 or log_mag.shape[0] != ex.shape[0]:
-        raise _lib.GolfError(f"min_phase_fir_filter: ex {tuple(ex.shape)} vs log_mag {tuple(log_mag.shape)}")
+    return _fir_filter(MIN_PHASE_FIR, ex, log_mag, window, hop)
+
+
+def _fir_filter_precise(design: _FIRDesign, ex, log_mag, window, hop: int) -> torch.Tensor:
+    """The kernels linearly interpolated to sample rate, as two frame FIRs (kernel rows f and f+1 over the same signal)
+    blended per sample; the single sample t = (F-1)*hop is a dot product with the last kernel.  The designs differ in
+    the lead L, the samples of left context an output reads: y[t] = sum_k K_t[k] ex[t + k - L] (zero-phase) or
+    sum_j K_t[j] ex[t - j] (causal, L = N-1, the window of ex reversed)."""
+    who = f"{design.kind}_fir_filter_precise"
+    _check_fir_inputs(who, ex, log_mag)
+    B, T = ex.shape
     F, n_mag = log_mag.shape[1], log_mag.shape[2]
-    _mp_check_frames("min_phase_fir_filter", ex, F, hop)
-    kern = _MPKernels.apply(log_mag, window)
-    return _FIRFramesCausal.apply(ex, kern, F, 2 * (n_mag - 1), hop, 0)
+    if F < 2:
+        raise _lib.GolfError(f"{who}: need at least 2 frames")
+    N = 2 * (n_mag - 1)
+    L = N - 1 if design.causal else (N - 1) // 2
+    Tfull = (F - 1) * hop + 1
+    Tout = min(T, Tfull)
+    kern = _FIRKernels.apply(log_mag, window, design)
+    # the samples the outputs t < Tfull can reach: indices < Tfull + N-1-L (zeros past T); causal: nothing later than t
+    Tin = Tfull + N - 1 - L
+    x = ex[:, :Tin]
+    if x.shape[1] < Tin:
+        x = torch.nn.functional.pad(x, (0, Tin - x.shape[1]))
+    ya = _FIRFrames.apply(x, kern, F, N, hop, 0, design.causal)[:, : (F - 1) * hop]
+    yb = _FIRFrames.apply(x, kern, F, N, hop, 1, design.causal)[:, : (F - 1) * hop]
+    w = (torch.arange((F - 1) * hop, device=ex.device) % hop).to(torch.float32) / hop
+    main = ya + w * (yb - ya)
+    tail = torch.nn.functional.pad(x, (L, 0))[:, Tfull - 1: Tfull - 1 + N]  # ex[Tfull-1 - L + i], i < N
+    if design.causal:
+        tail = tail.flip(-1)   # the signal, not the kernel: the order of the products in the sum stays the kernel's
+    last = (tail * kern.view(B, F, -1)[:, F - 1, :N]).sum(-1, keepdim=True)
+    return torch.cat([main, last], dim=1)[:, :Tout]
+
+
+def zero_phase_fir_filter_precise(ex: torch.Tensor, log_mag: torch.Tensor, window: torch.Tensor, hop: int) -> torch.Tensor:
+    """LTVZeroPhaseFIRFilterPrecise.forward (reference models/filters.py:308-337): the kernels are linearly
+    interpolated to sample rate, y[t] = sum_k pad(ex)[t+k] * ((1-w_t) K_f[k] + w_t K_{f+1}[k]), f = t // hop,
+    w_t = (t % hop)/hop, output length min(T, (F-1)*hop+1).  Evaluated as two frame FIRs (kernel rows f and f+1 over
+    the same signal) blended per sample; the single sample t = (F-1)*hop is a dot product with the last kernel."""
+    return _fir_filter_precise(ZERO_PHASE_FIR, ex, log_mag, window, hop)
 
 
 def min_phase_fir_filter_precise(ex: torch.Tensor, log_mag: torch.Tensor, window: torch.Tensor, hop: int) -> torch.Tensor:
@@ -1613,36 +1537,28 @@ def min_phase_fir_filter_precise(ex: torch.Tensor, log_mag: torch.Tensor, window
     interpolated to sample rate, y[t] = sum_j ((1-w_t) K_f[j] + w_t K_{f+1}[j]) ex[t-j], f = t // hop, w_t = (t % hop)/hop,
     output length min(T, (F-1)*hop+1).  Evaluated as two causal frame FIRs (kernel rows f and f+1 over the same signal)
     blended per sample; the single sample t = (F-1)*hop is a dot product with the last kernel."""
-    if log_mag.dim() != 3 or ex.dim() != 2 or log_mag.shape[0] != ex.shape[0]:
-        raise _lib.GolfError(f"min_phase_fir_filter_precise: ex {tuple(ex.shape)} vs log_mag {tuple(log_mag.shape)}")
-    B, T = ex.shape
-    F, n_mag = log_mag.shape[1], log_mag.shape[2]
-    if F < 2:
-        raise _lib.GolfError("min_phase_fir_filter_precise: need at least 2 frames")
-    N = 2 * (n_mag - 1)
-    Tfull = (F - 1) * hop + 1
-    Tout = min(T, Tfull)
-    kern = _MPKernels.apply(log_mag, window)
-    x = ex[:, :Tfull]          # a causal filter: the outputs t < Tfull read nothing later (zeros past T)
-    if x.shape[1] < Tfull:
-        x = torch.nn.functional.pad(x, (0, Tfull - x.shape[1]))
-    ya = _FIRFramesCausal.apply(x, kern, F, N, hop, 0)[:, : (F - 1) * hop]
-    yb = _FIRFramesCausal.apply(x, kern, F, N, hop, 1)[:, : (F - 1) * hop]
-    w = (torch.arange((F - 1) * hop, device=ex.device) % hop).to(torch.float32) / hop
-    main = ya + w * (yb - ya)
-    tail = torch.nn.functional.pad(x, (N - 1, 0))[:, Tfull - 1: Tfull - 1 + N]  # ex[Tfull-1 - (N-1) + i], i < N
-    last = (tail.flip(-1) * kern.view(B, F, -1)[:, F - 1, :N]).sum(-1, keepdim=True)
-    return torch.cat([main, last], dim=1)[:, :Tout]
+    return _fir_filter_precise(MIN_PHASE_FIR, ex, log_mag, window, hop)
+
+
+def _ltv_fir_frames(causal: bool, ex, kernels, hop: int) -> torch.Tensor:
+    B, F, N = kernels.shape
+    if causal:
+        _check_causal_frames("ltv_fir_frames_causal", ex, F, hop)
+    KS = (N + 15) // 16 * 16
+    kern = torch.nn.functional.pad(kernels.reshape(B * F, N), (0, KS - N))
+    return _FIRFrames.apply(ex, kern, F, N, hop, 0, causal)
+
+
+def ltv_fir_frames(ex: torch.Tensor, kernels: torch.Tensor, hop: int) -> torch.Tensor:
+    """Frame-wise FIR with arbitrary per-frame kernels (B,F,N): y[b,f*hop+n] = sum_k pad(ex)[b,f*hop+n+k] *
+    kernels[b,f,k]; differentiable w.r.t. both."""
+    return _ltv_fir_frames(False, ex, kernels, hop)
 
 
 def ltv_fir_frames_causal(ex: torch.Tensor, kernels: torch.Tensor, hop: int) -> torch.Tensor:
     """Causal frame-wise FIR with arbitrary per-frame kernels (B,F,N): y[b,f*hop+n] = sum_j kernels[b,f,j] *
     ex[b,f*hop+n-j], (T // hop) * hop samples; differentiable w.r.t. both."""
-    B, F, N = kernels.shape
-    _mp_check_frames("ltv_fir_frames_causal", ex, F, hop)
-    KS = (N + 15) // 16 * 16
-    kern = torch.nn.functional.pad(kernels.reshape(B * F, N), (0, KS - N))
-    return _FIRFramesCausal.apply(ex, kern, F, N, hop, 0)
+    return _ltv_fir_frames(True, ex, kernels, hop)
 
 
 # ------------------------------------------------------------------------------------------------

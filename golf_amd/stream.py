@@ -773,7 +773,7 @@ class _BranchStage:
             lm = params[0]
             if lm.shape[1]:
                 x = _f32(lm, self._dev).contiguous()
-                kern = GF._zp_kernels_raw(_lib.load(), x, self._window, self._basis)
+                kern = GF._fir_kernels_raw(GF.ZERO_PHASE_FIR, x, self._window, self._basis)
                 self._kern.append(kern.view(self.B, x.shape[1], -1))
             self.n_ctrl += lm.shape[1]
         elif self.b.kind == "frames":
@@ -828,7 +828,7 @@ class _BranchStage:
         x = self.src.get(fs * b.hop, e)
         kern = self._kern.data
         Fk = kern.shape[1]
-        y = GF._FIRFrames.apply(x, kern.reshape(self.B * Fk, -1), Fk, b.taps, b.hop, fs - self._kern.start)
+        y = GF._FIRFrames.apply(x, kern.reshape(self.B * Fk, -1), Fk, b.taps, b.hop, fs - self._kern.start, False)
         self.out.append(y[:, (f_lo - fs) * b.hop: (f_hi - fs) * b.hop], fresh=True)
         self._frames = f_hi
         nxt = max(0, f_hi - q)

@@ -133,6 +133,8 @@ def test_errors():
         GF.zero_phase_fir_filter(ex, lm, torch.hann_window(256).cuda(), 240)
     with pytest.raises(_lib.GolfError):  # window / n_mag mismatch
         GF.zero_phase_fir_filter(torch.zeros(2, 1000, device="cuda"), lm, torch.hann_window(100).cuda(), 240)
+    with pytest.raises(_lib.GolfError):  # the same on the direct design call (checked on the host, before any launch)
+        GF.zero_phase_fir_kernels(lm, torch.hann_window(100).cuda())
     with pytest.raises(_lib.GolfError):  # CPU tensors: there is no CPU path
         GF.zero_phase_fir_filter(torch.zeros(2, 1000), lm.cpu(), torch.hann_window(256), 240)
 

@@ -76,10 +76,11 @@ def test_refusals():
     import torch
 
     from golf_amd.audiotensor import AudioTensor
-    from golf_amd.filters import LTVZeroPhaseFIRFilterPrecise
+    from golf_amd.filters import (LTVAPZeroPhaseFIRFilter, LTVMinimumPhaseFIRFilter, LTVMinimumPhaseFIRFilterPrecise,
+                                  LTVZeroPhaseFIRFilter, LTVZeroPhaseFIRFilterPrecise)
     from golf_amd.noise import UniformNoise
     from golf_amd.sf import HarmonicPlusNoiseSynth
-    from golf_amd.stream import DecoderStream
+    from golf_amd.stream import DecoderStream, _branch_kind
     from golf_amd.synth import WrappedPhaseDownsampledIndexedGlottalFlowTable
     from golf_amd.synthetic import make_ddsp_decoder, make_decoder
 
@@ -105,6 +106,11 @@ def test_refusals():
     d.noise_filter = LTVZeroPhaseFIRFilterPrecise(window="hanning", n_mag=256)
     with pytest.raises(NotImplementedError, match="LTVZeroPhaseFIRFilterPrecise"):
         DecoderStream(d, 2)
+    # a filter streams as the frame-wise zero-phase FIR only if it runs that class's own forward
+    for cls in (LTVZeroPhaseFIRFilter, LTVAPZeroPhaseFIRFilter):
+        assert _branch_kind(cls(window="hanning", n_mag=256)) == "fir"
+    for cls in (LTVZeroPhaseFIRFilterPrecise, LTVMinimumPhaseFIRFilter, LTVMinimumPhaseFIRFilterPrecise):
+        assert _branch_kind(cls(window="hanning", n_mag=256)) is None
     st = DecoderStream(make_decoder(), 2)
     z = lambda *s: AudioTensor(torch.zeros(*s))
     args = dict(phase=z(2, 1), harm_oscillator_params=(AudioTensor(torch.zeros(2, 1), 2400),),

@@ -67,8 +67,8 @@ def main():
         "mp design bwd": lambda: chk(lib.golf_min_phase_fir_kernels_bwd_f32(p(g_kern), p(lm), p(mwin), p(mb), p(g_lm), G, N_MAG, st), "mpb"),
     }
     # frame FIRs on finished kernel rows
-    zk = GF._zp_kernels_raw(lib, lm, zwin, zb)
-    mk = GF._mp_kernels_raw(lib, lm, mwin, mb)
+    zk = GF._fir_kernels_raw(GF.ZERO_PHASE_FIR, lm, zwin, zb)
+    mk = GF._fir_kernels_raw(GF.MIN_PHASE_FIR, lm, mwin, mb)
     Tz, Tm = GF.fir_frames_length(T, F, N, HOP), GF.fir_frames_causal_length(T, F, N, HOP)
     yz, ym = torch.empty(B, Tz, device="cuda"), torch.empty(B, Tm, device="cuda")
     gz, gm = torch.randn(B, Tz, generator=g).cuda(), torch.randn(B, Tm, generator=g).cuda()
