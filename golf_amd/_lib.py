@@ -64,6 +64,9 @@ SIGNATURES = {
     "golf_stft_filter_frames_stream_f32": (_int, [_c_f32p, _i64, _i64, _int, _i64, _c_f32p, _i64, _int, _int, _i64, _c_f32p,
                                                   _i64, _int, _c_f32p, _i64, _i64, _int, _int, _int, _int, _c_f32p, _vp, _sz,
                                                   _vp]),
+    "golf_stft_filter_frames_bwd_workspace_bytes": (_sz, [_int] * 5),
+    "golf_stft_filter_frames_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _int, _c_f32p, _c_f32p, _i64, _c_f32p]
+                                        + [_int] * 5 + [_vp, _sz, _vp]),
     "golf_lti_frames_bwd_workspace_bytes": (_sz, [_int] * 6),
     "golf_lti_frames_ola_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64, _int,
                                            _c_f32p, _c_f32p] + [_int] * 7 + [_vp, _vp, _sz, _vp]),

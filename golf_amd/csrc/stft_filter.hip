@@ -242,6 +242,191 @@ __global__ __launch_bounds__(256) void stft_ola_kernel(const float* __restrict__
     y[(size_t)b * y_stride + i] = acc / norm;
 }
 
+// ---- backward of the whole utterance (x_end = T, frames_end = frames, a zero carry) -------------------------------------------
+// With q = gy / norm:  gu_f[k] = w[k] q[f*hop - n/2 + k]  (0 outside [0, Ty)),  GU_f = FFT(gu_f),  V_f = FFT(v_f) recomputed;
+//   g_h_f[kk] = c[kk] conj(V_f[kk]) GU_f[kk] / n  on bins 0 .. n/2  (c = 1 at 0 and n/2, else 2: a bin and its mirror);
+//   gv_f      = Re IFFT(conj(Hext_f) GU_f);   G[p] = sum_f w[k] gv_f[k]  on the padded positions p = f*hop - n/2 + k;
+//   g_x[r]    = G[r] + G[-r] (1 <= r <= n/2) + G[2(T-1) - r] (where that position is >= T): the transpose of the reflect pad.
+// Two launches again: the frames (gv_f -> ws, g_h rows in place), then a gather of g_x from ws alone in a fixed order.
+// v_f and gu_f are transformed one after the other, not packed as v + i gu into one complex transform: the split of a packed
+// spectrum rounds GU_f relative to |V_f| + |GU_f|, and a loss gradient is routinely orders of magnitude smaller than the
+// signal.  V_f's bins wait in registers meanwhile -- a lane needs exactly the bins it owns -- so the LDS is the forward's.
+struct StftBwdArgs {
+    const float* gy;     // (B, Ty)
+    int64_t gy_stride;
+    const float* x;      // (B, T)
+    int64_t x_stride;
+    const float* h;      // (B, F, n/2+1) real or (B, F, n/2+1, 2)
+    int h_kind;
+    const float* window;
+    float* g_h;          // as h, or null: V_f and the response gradient are skipped
+    float* ws;           // (B, frames, n): gv_f; null: no g_x wanted, the inverse transform is skipped
+    int T, Ty, F, frames, hop, n, lg, fpb;
+};
+
+// grid (ceil(frames / fpb) + (g_h ? F - frames : 0), B): the extra blocks zero the response rows no frame uses.
+__global__ __launch_bounds__(512) void stft_bwd_frames_kernel(StftBwdArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int n = p.n, q = n >> 2, lg = p.lg, half = n >> 1;
+    const int b = blockIdx.y;
+    const int nb = half + 1, hw = p.h_kind ? 2 : 1;
+    const int nblk = (p.frames + p.fpb - 1) / p.fpb;
+    if ((int)blockIdx.x >= nblk) {
+        float* dst = p.g_h + ((size_t)b * p.F + p.frames + (blockIdx.x - nblk)) * nb * hw;
+        for (int k = threadIdx.x; k < nb * hw; k += blockDim.x) dst[k] = 0.f;
+        return;
+    }
+    const int P = n + (n >> 3);
+    float* twc = lds;
+    float* tws = lds + n;
+    const int g = threadIdx.x >> (lg - 2), j = threadIdx.x & (q - 1);
+    float* re = lds + 2 * n + (size_t)g * 2 * P;
+    float* im = re + P;
+    const int f = blockIdx.x * p.fpb + g;
+    const bool mine = f < p.frames;
+    const int fc = mine ? f : p.frames - 1;    // (a group past the last frame repeats it and writes nothing)
+    {
+        const float step = -2.0f / (float)n;
+        for (int t = threadIdx.x; t < n; t += blockDim.x) {
+            float s, c;
+            sincospif((float)t * step, &s, &c);
+            twc[t] = c;
+            tws[t] = s;
+        }
+    }
+    const int sb = fc * p.hop - half;
+    float vr[3] = {0.f, 0.f, 0.f}, vi[3] = {0.f, 0.f, 0.f};   // V_f at bins j, j + n/4, j + n/2 (the last is used by j = 0 only)
+    if (p.g_h) {
+        const float* xrow = p.x + (size_t)b * p.x_stride;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = j + u * q;
+            int r = sb + k;
+            if (r < 0) r = -r;
+            if (r >= p.T) r = 2 * (p.T - 1) - r;
+            re[stft_pad(k)] = xrow[r] * p.window[k];
+            im[stft_pad(k)] = 0.f;
+        }
+        __syncthreads();
+        stft_fft<false>(re, im, twc, tws, j, q, lg);
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            vr[u] = re[stft_pad(j + u * q)];
+            vi[u] = im[stft_pad(j + u * q)];
+        }
+    }
+    {
+        // the elements this lane has just read are the ones it overwrites: no barrier in between
+        const float* gyrow = p.gy + (size_t)b * p.gy_stride;
+        const int fmax = p.frames - 1;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = j + u * q;
+            const int m = sb + k;          // output sample; m + n/2 is its position relative to frame 0's start
+            float v = 0.f;
+            if (m >= 0 && m < p.Ty) {
+                const int mp = m + half;
+                int fhi = mp / p.hop;
+                if (fhi > fmax) fhi = fmax;
+                const int flo = mp - n + 1 <= 0 ? 0 : (mp - n + p.hop) / p.hop;
+                float norm = 0.f;          // the forward's normaliser, in the forward's order
+                for (int ff = flo; ff <= fhi; ++ff) {
+                    const float wk = p.window[mp - ff * p.hop];
+                    norm = fmaf(wk, wk, norm);
+                }
+                v = p.window[k] * (gyrow[m] / norm);
+            }
+            re[stft_pad(k)] = v;
+            im[stft_pad(k)] = 0.f;
+        }
+    }
+    __syncthreads();
+    stft_fft<false>(re, im, twc, tws, j, q, lg);
+    const float inv_n = 1.0f / (float)n;
+    if (p.g_h && mine) {
+        float* grow = p.g_h + ((size_t)b * p.F + f) * nb * hw;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int k = j + u * q;
+            if (k > half) continue;
+            const float gr = re[stft_pad(k)], gi = im[stft_pad(k)];
+            const float c = (k == 0 || k == half) ? inv_n : 2.0f * inv_n;
+            const float hr = fmaf(vr[u], gr, vi[u] * gi) * c;    // conj(V) GU
+            if (p.h_kind)
+                *reinterpret_cast<float2*>(grow + 2 * k) = make_float2(hr, fmaf(vr[u], gi, -vi[u] * gr) * c);
+            else
+                grow[k] = hr;
+        }
+    }
+    if (!p.ws) return;   // (uniform over the block)
+    {
+        // bins j + u*n/4 are the ones this lane reads in the inverse's first stage: no barrier in between
+        const float* hrow = p.h + ((size_t)b * p.F + fc) * nb * hw;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = j + u * q;
+            const int kk = k <= half ? k : n - k;
+            float hre, him = 0.f;              // conj(Hext[k])
+            if (p.h_kind) {
+                const float2 hv = *reinterpret_cast<const float2*>(hrow + 2 * kk);
+                hre = hv.x;
+                him = k <= half ? -hv.y : hv.y;
+            } else {
+                hre = hrow[kk];
+            }
+            const int i = stft_pad(k);
+            const float a = re[i], c = im[i];
+            re[i] = fmaf(a, hre, -c * him);
+            im[i] = fmaf(a, him, c * hre);
+        }
+    }
+    stft_fft<true>(re, im, twc, tws, j, q, lg);
+    if (mine) {
+        float* orow = p.ws + ((size_t)b * p.frames + f) * n;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = j + u * q;
+            orow[k] = re[stft_pad(k)] * inv_n;
+        }
+    }
+}
+
+// G at padded position p (mp = p + n/2 >= 0): the frames that cover it, in ascending f with fmaf; 0 where none does.
+__device__ __forceinline__ float stft_bwd_G(const float* __restrict__ wf, const float* __restrict__ window, int mp, int frames,
+                                            int hop, int n) {
+    int fhi = mp / hop;
+    if (fhi > frames - 1) fhi = frames - 1;
+    const int flo = mp - n + 1 <= 0 ? 0 : (mp - n + hop) / hop;
+    float acc = 0.f;
+    for (int f = flo; f <= fhi; ++f) {
+        const int k = mp - f * hop;
+        acc = fmaf(window[k], wf[(size_t)f * n + k], acc);
+    }
+    return acc;
+}
+
+// g_x (B, T) from the frames in ws: the position itself, its mirror about sample 0, its mirror about sample T-1.
+__global__ __launch_bounds__(256) void stft_bwd_gather_kernel(const float* __restrict__ ws, const float* __restrict__ window,
+                                                              float* __restrict__ g_x, int64_t g_x_stride, int T, int frames,
+                                                              int hop, int n) {
+    const int b = blockIdx.y;
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= T) return;
+    const int half = n >> 1;
+    const float* wf = ws + (size_t)b * frames * n;
+    float acc = stft_bwd_G(wf, window, r + half, frames, hop, n);
+    if (r >= 1 && r <= half) acc += stft_bwd_G(wf, window, half - r, frames, hop, n);
+    const int p2 = 2 * (T - 1) - r;
+    if (p2 >= T) acc += stft_bwd_G(wf, window, p2 + half, frames, hop, n);
+    g_x[(size_t)b * g_x_stride + r] = acc;
+}
+
+// rows (gridDim.y) of `cols` zeros
+__global__ __launch_bounds__(256) void stft_bwd_zero_kernel(float* __restrict__ dst, int64_t stride, int64_t cols) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < cols) dst[(size_t)blockIdx.y * stride + i] = 0.f;
+}
+
 static int stft_log2(int n) {   // log2 n for a power of two in [64, 2048], else 0
     for (int lg = 6; lg <= 11; ++lg)
         if (n == (1 << lg)) return lg;
@@ -249,6 +434,19 @@ static int stft_log2(int n) {   // log2 n for a power of two in [64, 2048], else
 }
 
 static int stft_S(int n, int hop) { return (n + hop - 1) / hop - 1; }
+
+// The one-shot geometry the backward takes (what the forward takes with the end markers set), else an error code.
+static int stft_bwd_geometry(int B, int T, int F, int n_fft, int hop, bool report) {
+    auto no = [&](int code, const char* msg) { return report ? fail(code, "stft_filter_frames_bwd: %s", msg) : code; };
+    if (B < 1 || T < 1 || F < 1 || hop < 1 || n_fft < 1) return no(GOLF_EINVAL, "bad size");
+    if (!stft_log2(n_fft)) return no(GOLF_EUNSUPPORTED, "n_fft is not a power of two in [64, 2048]");
+    if (n_fft < 2 * hop) return no(GOLF_EINVAL, "n_fft < 2*hop");
+    if (T <= n_fft / 2) return no(GOLF_EINVAL, "T samples cannot be reflect-padded by n_fft/2");
+    const int64_t frames = std::min<int64_t>(1 + T / hop, F);
+    if (frames * n_fft >= (1ll << 29) || T >= (1 << 29) || (int64_t)F * (n_fft / 2 + 1) >= (1ll << 29))
+        return no(GOLF_EUNSUPPORTED, "call too large");
+    return GOLF_OK;
+}
 
 }  // namespace golf
 
@@ -368,6 +566,71 @@ extern "C" int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stri
         hipLaunchKernelGGL(stft_ola_kernel, dim3((unsigned)(ceil_div(ny, 256) + ncout), B), dim3(256), 0, st,
                            (const float*)ws, window, y, y_stride, carry, ny, mb, fmin, fmax, S + nf, hop, n_fft, S, ncout,
                            ncout ? (int)((fdone - ncout) % S) : 0);
+        GOLF_LAUNCH_CHECK();
+    }
+    return GOLF_OK;
+}
+
+extern "C" size_t golf_stft_filter_frames_bwd_workspace_bytes(int B, int T, int F, int n_fft, int hop) {
+    if (stft_bwd_geometry(B, T, F, n_fft, hop, false) != GOLF_OK) return 0;
+    return align_up(sizeof(float) * (size_t)B * std::min(1 + T / hop, F) * n_fft, 256);
+}
+
+extern "C" int golf_stft_filter_frames_bwd_f32(const float* gy, int64_t gy_stride, const float* x, int64_t x_stride,
+                                               const float* h, int h_kind, const float* window, float* g_x,
+                                               int64_t g_x_stride, float* g_h, int B, int T, int F, int n_fft, int hop,
+                                               void* ws, size_t ws_bytes, void* stream) {
+    if (h_kind != 0 && h_kind != 1) return fail(GOLF_EINVAL, "stft_filter_frames_bwd: bad kind %d", h_kind);
+    const int rc = stft_bwd_geometry(B, T, F, n_fft, hop, true);
+    if (rc != GOLF_OK) return rc;
+    const int frames = std::min(1 + T / hop, F), Ty = hop * (frames - 1);
+    if (!x || !h || !window || (Ty > 0 && !gy) || (!g_x && !g_h))
+        return fail(GOLF_EINVAL, "stft_filter_frames_bwd: null pointer (one of g_x, g_h may be null)");
+    if (x_stride < T || gy_stride < Ty || (g_x && g_x_stride < T))
+        return fail(GOLF_EINVAL, "stft_filter_frames_bwd: row stride too small");
+    const size_t need = golf_stft_filter_frames_bwd_workspace_bytes(B, T, F, n_fft, hop);
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255))
+        return fail(GOLF_EWORKSPACE, "stft_filter_frames_bwd: workspace needs %zu bytes, 256-aligned (got %zu)", need, ws_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t hcols = (int64_t)F * (n_fft / 2 + 1) * (h_kind ? 2 : 1);
+    if (Ty == 0) {   // a single frame reaches no output sample
+        if (g_x) {
+            hipLaunchKernelGGL(stft_bwd_zero_kernel, dim3((unsigned)ceil_div(T, 256), B), dim3(256), 0, st, g_x, g_x_stride,
+                               (int64_t)T);
+            GOLF_LAUNCH_CHECK();
+        }
+        if (g_h) {
+            hipLaunchKernelGGL(stft_bwd_zero_kernel, dim3((unsigned)ceil_div(hcols, 256), B), dim3(256), 0, st, g_h, hcols, hcols);
+            GOLF_LAUNCH_CHECK();
+        }
+        return GOLF_OK;
+    }
+    StftBwdArgs p;
+    p.gy = gy;
+    p.gy_stride = gy_stride;
+    p.x = x;
+    p.x_stride = x_stride;
+    p.h = h;
+    p.h_kind = h_kind;
+    p.window = window;
+    p.g_h = g_h;
+    p.ws = g_x ? (float*)ws : nullptr;
+    p.T = T;
+    p.Ty = Ty;
+    p.F = F;
+    p.frames = frames;
+    p.hop = hop;
+    p.n = n_fft;
+    p.lg = stft_log2(n_fft);
+    p.fpb = n_fft >= 256 ? 1 : 256 / n_fft;
+    const int threads = p.fpb * (n_fft / 4);
+    const size_t ldsb = sizeof(float) * (2 * (size_t)n_fft + (size_t)p.fpb * 2 * (n_fft + n_fft / 8));
+    hipLaunchKernelGGL(stft_bwd_frames_kernel, dim3((unsigned)(ceil_div(frames, p.fpb) + (g_h ? F - frames : 0)), B),
+                       dim3(threads), ldsb, st, p);
+    GOLF_LAUNCH_CHECK();
+    if (g_x) {
+        hipLaunchKernelGGL(stft_bwd_gather_kernel, dim3((unsigned)ceil_div(T, 256), B), dim3(256), 0, st, (const float*)ws,
+                           window, g_x, g_x_stride, T, frames, hop, n_fft);
         GOLF_LAUNCH_CHECK();
     }
     return GOLF_OK;

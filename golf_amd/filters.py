@@ -382,15 +382,43 @@ class SampleBasedLTVMinimumPhaseFilter(LTVMinimumPhaseFilter):
     forward = LTVMinimumPhaseFilterPrecise.forward
 
 
+def _on_hip_frames(module, x: Tensor, ctrl: Tensor) -> bool:
+    """Whether an STFT-domain filter module runs ``GF.stft_filter_frames`` on these inputs: not switched off
+    (``hip_frames``), ROCm device tensors in fp32 (or fp16 / bf16 under autocast), and a geometry the kernel takes -- centred,
+    n_fft a power of two in [64, 2048], n_fft >= 2*hop, more than n_fft/2 samples, at least two frames.  Everything else
+    (CPU tensors, float64, center=False, n_fft = 1000 ...) runs torch.stft / torch.istft."""
+    if not (module.hip_frames and x.is_cuda and ctrl.is_cuda and getattr(module, "center", True)):
+        return False
+    dtypes = (torch.float32, torch.float16, torch.bfloat16) if torch.is_autocast_enabled() else (torch.float32,)
+    if x.dtype not in dtypes or ctrl.dtype not in dtypes:
+        return False
+    n, hop = int(module.n_fft), int(module.hop_length)
+    frames = min(1 + x.shape[-1] // hop, ctrl.shape[1])
+    return n & (n - 1) == 0 and 64 <= n <= 2048 and n >= 2 * hop and x.shape[-1] > n // 2 and frames >= 2
+
+
+def _hip_frames(module, x: Tensor, ctrl: Tensor) -> AudioTensor:
+    """The module's response rows on bins 0 .. n_fft/2 (torch, fp32, differentiable) through ``GF.stft_filter_frames``."""
+    with torch.autocast("cuda", enabled=False):
+        H = module.response_rows(ctrl.float())
+        return AudioTensor(GF.stft_filter_frames(x.float(), H, module._window, module.hop_length))
+
+
 class LTVCepFilter(LTVFilterInterface):
     """Cepstral harmonic filter of the NHV baseline (reference models/filters.py:559-623; cfg/ae/decoder/nhv.yaml):
     ``filter_order + 1`` cepstral coefficients per frame -> log-magnitude response (even extension + FFT) -> zero- or
     minimum-phase frequency response (the minimum phase is minus the Hilbert transform of the log magnitude) -> applied
     in the STFT domain (two-sided STFT with ``window``, multiply, inverse STFT).
 
-    Stock PyTorch on rocFFT: a frequency-domain baseline filter, not part of the GOLF path; here so that the shipped NHV
-    decoder builds and runs on this package.  The reference takes the transforms from torchaudio (third party); the same
-    torch.stft / torch.istft calls are made directly."""
+    On a ROCm device the STFT-domain part runs and trains on the frame-filter kernel (``GF.stft_filter_frames``: the
+    arithmetic of the streamed decoder, custom backward) for fp32 inputs -- fp16 / bf16 under autocast -- when n_fft is a
+    power of two in [64, 2048], n_fft >= 2*hop, the input is longer than n_fft/2 and there are at least two frames; the
+    response rows (cepstra -> bins 0 .. n_fft/2, complex for "min", real for "zero") stay torch autograd.  CPU tensors,
+    float64 and every other geometry run stock PyTorch on rocFFT, as does an instance with ``hip_frames = False``; both paths
+    return hop*(frames-1) samples.  The reference takes the transforms from torchaudio (third party); the stock path makes
+    the same torch.stft / torch.istft calls directly.  No fused design kernel (cepstrum -> response) exists."""
+
+    hip_frames = True   # False: torch.stft / torch.istft on the device too
 
     def __init__(self, filter_order: int, n_fft: int, window: str, hop_length: int, phase: str = "zero", **kwargs):
         super().__init__()
@@ -420,9 +448,15 @@ class LTVCepFilter(LTVFilterInterface):
         analytic = torch.fft.ifft(torch.fft.fft(log_mag, dim=-1) * weights, dim=-1)
         return torch.exp(torch.complex(log_mag, -analytic.imag)).transpose(-1, -2)
 
+    def response_rows(self, ceps: Tensor) -> Tensor:
+        """(B, F, order + 1) cepstra -> (B, F, n_fft/2 + 1) response rows on bins 0 .. n_fft/2, as the stream forms them."""
+        return self.frequency_response(ceps)[:, : self.n_fft // 2 + 1].transpose(1, 2).contiguous()
+
     def forward(self, ex: AudioTensor, ceps: AudioTensor, **kwargs) -> AudioTensor:
         assert ceps.hop_length == self.hop_length
         x = ex.as_tensor()
+        if _on_hip_frames(self, x, ceps.as_tensor()):
+            return _hip_frames(self, x, ceps.as_tensor())
         H = self.frequency_response(ceps.as_tensor())
         X = torch.stft(x, self.n_fft, self.hop_length, self.n_fft, self._window, center=True, pad_mode="reflect",
                        normalized=False, onesided=False, return_complex=True)
@@ -453,7 +487,12 @@ def melscale_fbanks(n_freqs: int, f_min: float, f_max: float, n_mels: int, sampl
 class DiffWorldSPFilter(LTVFilterInterface):
     """Spectral-envelope filter of the WORLD baseline (reference models/filters.py:717-760; cfg/ae/decoder/world.yaml): a
     mel spectral envelope per frame -> linear magnitudes through the rectified pseudo-inverse of a mel filterbank ->
-    sqrt -> applied as a zero-phase gain in the STFT domain.  Stock PyTorch (rocFFT), like the reference."""
+    sqrt -> applied as a zero-phase gain in the STFT domain.  On a ROCm device the STFT-domain part runs and trains on the
+    frame-filter kernel (``GF.stft_filter_frames``) under the conditions given for ``LTVCepFilter`` plus ``center=True``,
+    the gain rows staying torch autograd; otherwise, and with ``hip_frames = False``, stock PyTorch (rocFFT) like the
+    reference."""
+
+    hip_frames = True   # False: torch.stft / torch.istft on the device too
 
     def __init__(self, n_mels: int, n_fft: int, hop_length: int, f_min: float, f_max: float, center: bool = True,
                  window: str = "hanning", **kwargs):
@@ -464,8 +503,14 @@ class DiffWorldSPFilter(LTVFilterInterface):
         self.n_fft, self.hop_length, self.center = n_fft, hop_length, center
         self.ctrl = wrap_ctrl_fn(split_size=(n_mels,), trsfm_fn=lambda x: (torch.exp(x),))
 
+    def response_rows(self, mel_sp: Tensor) -> Tensor:
+        """(B, F, n_mels) mel envelope -> (B, F, n_fft/2 + 1) real gain rows, as the stream forms them."""
+        return torch.sqrt(mel_sp @ self.fb)
+
     def forward(self, ex: AudioTensor, mel_sp: AudioTensor) -> AudioTensor:
         assert mel_sp.hop_length == self.hop_length
+        if _on_hip_frames(self, ex.as_tensor(), mel_sp.as_tensor()):
+            return _hip_frames(self, ex.as_tensor(), mel_sp.as_tensor())
         gain = torch.sqrt(mel_sp.as_tensor() @ self.fb).transpose(1, 2)                  # (B, bins, F)
         X = torch.stft(ex.as_tensor(), self.n_fft, self.hop_length, self.n_fft, self._window, center=self.center,
                        pad_mode="reflect", normalized=False, onesided=True, return_complex=True)

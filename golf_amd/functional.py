@@ -746,16 +746,55 @@ def stft_filter_stream(x, H, window, hop: int, carry=None, *, x0: int, h0: int, 
     return y, carry
 
 
+class _STFTFilterFrames(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, H, window, hop):
+        ctx.dtypes = (x.dtype, H.dtype)
+        x, window = _rows(x.float()), window.float().contiguous()
+        cplx = H.is_complex()
+        H = H.to(torch.complex64).contiguous() if cplx else H.float().contiguous()
+        T = x.shape[1]
+        frames = min(1 + T // hop, H.shape[1])
+        # the streaming entry in a single call: end markers set, a fresh zero carry
+        y = stft_filter_stream(x, H, window, hop, None, x0=0, h0=0, f0=0, nf=frames, n0=0, ny=hop * (frames - 1), x_end=T,
+                               frames_end=frames)[0]
+        ctx.save_for_backward(x, torch.view_as_real(H) if cplx else H, window)
+        ctx.hop = hop
+        return y
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, gy):
+        x, Hf, window = ctx.saved_tensors
+        need_x, need_h = ctx.needs_input_grad[:2]
+        lib = _lib.load()
+        gy = _rows(gy)
+        B, T = x.shape
+        F, n = Hf.shape[1], window.numel()
+        g_x = torch.empty(B, T, dtype=torch.float32, device=x.device) if need_x else None   # written in full
+        g_h = torch.empty_like(Hf) if need_h else None                                     # (zeros for the rows no frame uses)
+        ws = _workspace(lib.golf_stft_filter_frames_bwd_workspace_bytes(B, T, F, n, ctx.hop), x.device)
+        rc = lib.golf_stft_filter_frames_bwd_f32(gy.data_ptr(), gy.stride(0), x.data_ptr(), x.stride(0), Hf.data_ptr(),
+                                                 int(Hf.ndim == 4), window.data_ptr(), _lib.ptr(g_x),
+                                                 T if g_x is None else g_x.stride(0), _lib.ptr(g_h), B, T, F, n, ctx.hop,
+                                                 ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "golf_stft_filter_frames_bwd_f32")
+        if need_h:
+            g_h = (torch.view_as_complex(g_h) if Hf.ndim == 4 else g_h).to(ctx.dtypes[1])
+        return g_x.to(ctx.dtypes[0]) if need_x else None, g_h, None, None
+
+
 def stft_filter_frames(x, H, window, hop: int) -> torch.Tensor:
-    """The whole utterance through ``stft_filter_stream`` in a single call with the end markers set: ``x`` (B, T), ``H``
-    (B, F, n_fft/2+1) -> (B, hop*(frames-1)), frames = min(1 + T//hop, F).  What LTVCepFilter / DiffWorldSPFilter compute with
-    torch.stft / torch.istft; the tests compare the kernel against them through this."""
-    T, F, n = x.shape[1], H.shape[1], window.numel()
+    """The STFT-domain frame filter over a whole utterance: ``x`` (B, T), ``H`` (B, F, n_fft/2+1) real or complex -> (B,
+    hop*(frames-1)), frames = min(1 + T//hop, F).  What LTVCepFilter / DiffWorldSPFilter compute with torch.stft / torch.istft,
+    and what they run on the device.  The forward is ``stft_filter_stream`` in a single call with the end markers set;
+    differentiable w.r.t. ``x`` and ``H`` (golf_stft_filter_frames_bwd_f32), the gradient of a complex ``H`` in torch's
+    convention (d/d re + i d/d im)."""
+    T, n = x.shape[1], window.numel()
     if T <= n // 2:
         raise _lib.GolfError(f"stft_filter_frames: {T} samples cannot be reflect-padded by n_fft/2 = {n // 2}")
-    frames = min(1 + T // int(hop), F)
-    return stft_filter_stream(x, H, window, hop, None, x0=0, h0=0, f0=0, nf=frames, n0=0, ny=int(hop) * (frames - 1),
-                              x_end=T, frames_end=frames)[0]
+    return _STFTFilterFrames.apply(x, H, window, int(hop))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -754,12 +754,7 @@ class _BranchStage:
 
     def _response(self, ctrl: torch.Tensor) -> torch.Tensor:
         """(B, rows, n_fft/2 + 1) response rows from control rows, by the module's own code: the rows of the one-shot's H."""
-        from .filters import LTVCepFilter
-
-        m = self._module
-        if isinstance(m, LTVCepFilter):
-            return m.frequency_response(ctrl)[:, : m.n_fft // 2 + 1].transpose(1, 2).contiguous()
-        return torch.sqrt(ctrl @ m.fb)
+        return self._module.response_rows(ctrl)
 
     def append(self, params) -> None:
         if self.b.kind == "stft":

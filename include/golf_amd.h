@@ -340,6 +340,29 @@ int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stride, int64_t
                                        int nf, float* y, int64_t y_stride, int64_t n0, int ny, int B, int n_fft, int hop,
                                        float* carry, void* ws, size_t ws_bytes, void* stream);
 
+/* Backward of the STFT-domain frame filter over a whole utterance (additive in ABI 6): the forward above called once with
+ * x0 = h0 = f0 = n0 = 0, x_end = T, frames_end = frames = min(1 + T/hop, F), ny = Ty = hop*(frames-1) and a zero carry --
+ * what autograd computes in the reference through torch.stft, the product and torch.istft (closed form restated in float64 in
+ * tests/stft_filter_ref.py).  With q = gy / norm, pad = n/2, v_f the windowed frame of the forward and V_f = FFT(v_f), recomputed:
+ *   gu_f[k] = w[k]*q[f*hop - pad + k] (0 outside [0, Ty));   GU_f = FFT(gu_f);
+ *   g_h[b,f,kk] = c[kk]*conj(V_f[kk])*GU_f[kk]/n on bins 0 .. n/2, c = 1 at bins 0 and n/2 and 2 elsewhere: (re, im) for
+ *           h_kind 1, the real part for h_kind 0; rows frames <= f < F are zeros;
+ *   gv_f = Re IFFT(conj(Hext_f)*GU_f);   G[p] = sum_f w[k]*gv_f[k], k = p + pad - f*hop, frames in ascending f with fmaf;
+ *   g_x[r] = G[r] + G[-r] (1 <= r <= pad) + G[2(T-1) - r] (where that position is >= T): a gather, no atomics.
+ *   gy (B, Ty), x (B, T), g_x (B, T) with row strides; h and g_h contiguous as in the forward, F rows each.
+ *   g_x or g_h may be NULL (not both): the inverse transforms and the gather, or V_f and the response gradient, are skipped,
+ *   and the gradient that is computed has the bits of the joint call.  Both are written in full.
+ *   ws      scratch of golf_stft_filter_frames_bwd_workspace_bytes() bytes (0 for a refused geometry), 256-aligned: the gv_f.
+ * Refused before any launch: n not a power of two in [64, 2048] or a call too large (GOLF_EUNSUPPORTED); n < 2*hop, T <= n/2,
+ * null pointers, row strides below the row length (GOLF_EINVAL); a missing, short or misaligned workspace (GOLF_EWORKSPACE).
+ * Two launches (frames, then the gather; Ty = 0 writes zeros and transforms nothing), no allocation, no host<->device
+ * synchronisation, capturable in a hipGraph.  v_f and gu_f are transformed separately (a packed v + i*gu transform would
+ * round GU_f relative to the signal's magnitude); every sum runs in a fixed order: the gradients are bit-reproducible. */
+size_t golf_stft_filter_frames_bwd_workspace_bytes(int B, int T, int F, int n_fft, int hop);
+int golf_stft_filter_frames_bwd_f32(const float* gy, int64_t gy_stride, const float* x, int64_t x_stride, const float* h,
+                                    int h_kind, const float* window, float* g_x, int64_t g_x_stride, float* g_h, int B, int T,
+                                    int F, int n_fft, int hop, void* ws, size_t ws_bytes, void* stream);
+
 /* Custom backward of the above (what autograd computes in the reference through conv_transpose1d, lfilter, unfold,
  * the zero pad and the gain product; closed form in oracle/golf_oracle.py::lti_frames_ola_backward, pinned by
  * tests/golden/g15):  g_q = gy/norm;  u_f = the frame's all-pole recursion run backwards in time on window*g_q;
