@@ -7,6 +7,7 @@ infrastructure and is never imported from here.)
 from __future__ import annotations
 
 import ctypes
+import glob
 import os
 import subprocess
 import threading
@@ -169,8 +170,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     import hashlib
 
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_common.h"), os.path.join(CSRC, "lpc_p1f.h"),
-                   os.path.join(INCLUDE, "golf_amd.h")]
+    deps = srcs + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "golf_amd.h")]
     extra = os.environ.get("GOLF_HIPCC_FLAGS", "").split()
     lib_path = os.path.join(LIB_DIR, "libgolf_hip.flags.so") if extra else LIB_PATH
     os.makedirs(LIB_DIR, exist_ok=True)

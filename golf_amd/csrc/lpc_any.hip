@@ -1,5 +1,5 @@
 // Sample-wise LTV all-pole filter (include/golf_amd.h, a-1) for the shapes WITHOUT a ring plan: any 1 <= M <= 64, any hop >= 1,
-// any F >= 1 (lpc_ss.hip make_ss_plan returns false: no ring width in {8,16,24,32,40} divides the hop, M > 38, or F == 1).
+// any F >= 1 (lpc_ss_plan.h make_ss_plan returns false: no ring width in {8,16,24,32,40} divides the hop, M > 38, or F == 1).
 // fp32, 64-bit row addressing.  Forward (one-shot and carried-state), adjoint and gradients; gfx950 only.
 //
 // The recursion is serial in time, so the cost of a sample is the dependent chain behind it.  One WAVE per utterance, one LANE

@@ -40,117 +40,9 @@
 #include "device_common.h"
 #include "lpc_p1f.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace golf {
-
-// ------------------------------------------------------------------------------------------
-// plan
-// ------------------------------------------------------------------------------------------
-// (W, NT) kernel instantiations: NT taps computed (zero padded above M), ring width W >= NT+1
-// (the adjoint ring needs one free slot), W | hop.  Keep in sync with GOLF_SS_DISPATCH below.
-struct WNT { int W, NT; };
-static const WNT kTable[] = {{8, 2},   {8, 4},   {8, 6},   {16, 8},  {16, 12}, {16, 14}, {24, 8},  {24, 12},
-                             {24, 16}, {24, 20}, {24, 22}, {32, 16}, {32, 22}, {32, 26}, {32, 30}, {40, 22},
-                             {40, 26}, {40, 32}, {40, 38}};
-
-// Batch size from which the batch-parallel serial kernels replace the chunked scan (build parameter).
-// Chunking buys parallelism in time at the price of (M+2)-fold arithmetic; once the batch alone fills the chip's wave
-// slots that price stops paying.  Measured crossover on MI355X (M=22, T=47761): DESIGN.md §4.1.
-#ifndef GOLF_SS_SERIAL_MIN_BATCH
-#define GOLF_SS_SERIAL_MIN_BATCH 2048
-#endif
-
-bool make_ss_plan(int B, int T, int F, int M, int hop, SsPlan* p, int mode) {
-    p->W = 0;
-    p->NT = 0;
-    // mode: 0 = by batch size, GOLF_SS_SERIAL / GOLF_SS_CHUNKED force one; rows of 16 utterances must fit a 2 GB
-    // buffer descriptor
-    p->serial = mode == GOLF_SS_SERIAL || (mode != GOLF_SS_CHUNKED && B >= GOLF_SS_SERIAL_MIN_BATCH);
-    if (F >= 2) {
-        for (const WNT& e : kTable) {
-            if (e.NT < M || hop % e.W != 0) continue;
-            if (p->W == 0 || e.NT < p->NT || (e.NT == p->NT && e.W < p->W)) { p->W = e.W; p->NT = e.NT; }
-        }
-    }
-    if (p->W == 0) { p->total = 256; return false; }
-    const int W = p->W;
-    int L;
-    const int target = 240;
-    if (hop >= target) {
-        L = W;
-        for (int cand = W; cand <= 256 && cand <= hop; cand += W)
-            if (hop % cand == 0) L = cand;
-    } else {
-        L = hop * (target / hop);
-    }
-    // (Shorter chunks were tried in round 4 with an env override here: L = 120 at hop 240 halves the chunk recursion -- flat-scan
-    //  chunk passes 13 / 10 us instead of ~20 -- but the two-level passes stay at 26 / 21 us because their prologues grow with the
-    //  group count (25 groups: 24 fold steps), the pre-pass goes 16 -> 30 us and the maps double: one batch alone 143 vs 129 us,
-    //  four in flight 87.9 vs 69.3.)
-    p->L = L;
-    p->NC = (int)ceil_div(T, L);
-    p->NP = p->NC - 1;
-    p->seg = L < hop ? L : hop;
-    p->NSEG = (int)ceil_div(T, p->seg);
-    size_t o = 0;
-    if (p->serial) {   // batch-parallel serial path: no transition matrices, no boundary states
-        p->off_phi = p->off_phiT = p->off_z = p->off_E = p->off_z2 = p->off_S = p->off_zadj = p->off_lam = 0;
-        p->NG = p->GS = 0;
-        p->off_mt = p->off_gv = p->off_pmax = 0;
-        p->off_tier = p->off_S1 = p->off_status = p->off_phi64 = p->off_fixcnt = 0;
-        p->off_m64 = p->off_v64 = p->off_g64 = 0;
-        p->off_mtT = p->off_L1 = p->off_wadj = p->off_dadj = 0;
-        p->off_gflag = 0;
-        p->off_g = o;    o = align_up(o + sizeof(float) * (size_t)B * T, 256);
-        p->off_pa = o;   o = align_up(o + sizeof(float) * (size_t)B * p->NSEG * 2 * W, 256);
-        p->off_pg = o;   o = align_up(o + sizeof(float) * (size_t)B * p->NSEG * 2, 256);
-        p->total = o;
-        return true;
-    }
-    p->off_phi = o;  o = align_up(o + sizeof(float) * (size_t)B * (p->NP > 0 ? p->NP : 1) * p->NT * W, 256);
-    p->off_phiT = o; o = align_up(o + sizeof(float) * (size_t)B * (p->NP > 0 ? p->NP : 1) * p->NT * W, 256);
-    p->off_z = o;    o = align_up(o + sizeof(float) * (size_t)B * (p->NP > 0 ? p->NP : 1) * W, 256);
-    p->off_E = o;    o = align_up(o + sizeof(float) * (size_t)B * (p->NP > 0 ? p->NP : 1) * W, 256);
-    p->off_z2 = o;   o = align_up(o + sizeof(float) * (size_t)B * (p->NP > 0 ? p->NP : 1) * W, 256);
-    p->off_S = o;    o = align_up(o + sizeof(float) * (size_t)B * p->NC * 64, 256);
-    p->off_zadj = o; o = align_up(o + sizeof(float) * (size_t)B * p->NC * W, 256);
-    p->off_lam = o;  o = align_up(o + sizeof(float) * (size_t)B * p->NC * 64, 256);
-    p->off_g = o;    o = align_up(o + sizeof(float) * (size_t)B * T, 256);
-    p->off_pa = o;   o = align_up(o + sizeof(float) * (size_t)B * p->NSEG * 2 * W, 256);
-    p->off_pg = o;   o = align_up(o + sizeof(float) * (size_t)B * p->NSEG * 2, 256);
-    p->off_pmax = o; o = align_up(o + sizeof(float) * (size_t)B * (p->NP > 0 ? p->NP : 1), 256);   // max |Phi_c| per chunk
-    p->off_tier = o; o = align_up(o + sizeof(unsigned) * ((size_t)B * 2 + 2), 256);   // conditioning tier + hot-chunk count per utterance; [2B] scan kind of the forward, [2B+1] backward mismatch
-    p->off_status = o; o = align_up(o + sizeof(unsigned) * 8, 256);              // status words (non-finite output flag)
-    p->off_fixcnt = o; o = align_up(o + sizeof(unsigned) * ((size_t)B * 5 + 1), 256);   // fix-up units completed / claimed per utterance; [2B]: a wait for the fix-up ran out; [2B+1 .. 3B]: groups of a tier-3 utterance that have their fp64 composite; [3B+1 .. 4B]: largest partial product of those composites; [4B+1 .. 5B]: 1 = that utterance's fp64 states come from the flat scan
-    // two-level boundary scan (lpc_group_prepass_kernel + lpc_fwdq2_kernel): worth it from ~48 chunk maps on, and the
-    // chunk kernels' prologue keeps rows of up to 24 state components in its prefetch rings
-    p->NG = 0;
-    p->GS = 0;
-    p->off_mt = p->off_gv = o;
-    if (p->NP >= 48 && p->NT <= 24) {
-        p->GS = 16;                                  // = the 16 chunks a wave of the chunk kernels owns
-        p->NG = (int)ceil_div(p->NP, p->GS);
-        p->off_mt = o;   o = align_up(o + sizeof(float) * (size_t)B * p->NG * p->NT * W, 256);
-        p->off_gv = o; o = align_up(o + sizeof(float) * (size_t)B * p->NG * 32 * 2, 256);   // group responses (z, defects)
-    }
-    p->off_S1 = o;   o = align_up(o + sizeof(float) * (size_t)B * p->NC * 32, 256);   // first-pass chunk start states (two-level)
-    // backward, two-level adjoint scan: transposed composites, first-pass adjoint states L1 (rows -1 .. NP), group responses
-    // (zadj, defects), defects
-    p->off_mtT = o;  o = align_up(o + sizeof(float) * (size_t)B * (p->NG > 0 ? p->NG : 1) * p->NT * W, 256);
-    p->off_L1 = o;   o = align_up(o + sizeof(float) * (size_t)B * (p->NC + 1) * 32, 256);
-    p->off_wadj = o; o = align_up(o + sizeof(float) * (size_t)B * (p->NG > 0 ? p->NG : 1) * 32 * 2, 256);
-    p->off_dadj = o; o = align_up(o + sizeof(float) * (size_t)B * p->NC * W, 256);
-    // transition matrices as doubles, [b][c][j][i] (trajectory-major), written and read only for tier-3 utterances: the
-    // allocation is never touched otherwise (27 MB at B = 32 x 2 s)
-    p->off_phi64 = o; o = align_up(o + sizeof(double) * (size_t)B * (p->NP > 0 ? p->NP : 1) * p->NT * W, 256);
-    // ... and, on the two-level path, their group composites / group responses / group start states as doubles
-    p->off_m64 = o;  o = align_up(o + sizeof(double) * (size_t)B * (p->NG > 0 ? p->NG : 1) * p->NT * W, 256);
-    p->off_v64 = o;  o = align_up(o + sizeof(double) * (size_t)B * (p->NG > 0 ? p->NG : 1) * 32, 256);
-    p->off_g64 = o;  o = align_up(o + sizeof(double) * (size_t)B * (p->NG + 1) * 32, 256);
-    p->off_gflag = o; o = align_up(o + sizeof(unsigned) * (size_t)B * (p->NG + 1), 256);   // zeroed by every forward's pre-pass launch
-    p->total = o;
-    return true;
-}
 
 // Conditioning tiers of the time-chunked algorithm (numerics: tools/numlab/lab2.py).
 // The delta-form refinement sweep makes every error of the coarse propagator second order, PROVIDED the sweep contracts:
@@ -1490,7 +1382,6 @@ __device__ __forceinline__ void precise_adj_scan(const double* __restrict__ P64,
 //       and keep their 16 maps in LDS between the three stages that need them.
 // ------------------------------------------------------------------------------------------
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kGroup = 16;   // chunk maps per group = chunks per wave of the chunk kernels
 template <int W> constexpr int kMapRow = W + 4;   // row stride of a group's maps kept in LDS (lpc_fwdq2m_kernel), in words
 // prefetch depths of the two-level prologues (maps fetched ahead of the matvec that uses them): chunk maps / composites
 // (measured round 4: 8 + 8 and 6 + 8 deep were slower -- the prologue's matvec steps are issue-bound, not fetch-bound)
@@ -2406,7 +2297,6 @@ __global__ __launch_bounds__(64, GOLF_FWDQ2_WAVES) void lpc_fwdq2_kernel(const f
 // wave that completes an utterance sets its `ready` word, which the utterance's chunk waves wait for before phase B.
 // The flag words are zeroed by the pre-pass launch of the same forward (as is the non-finite status word: here the pass that
 // raises it and the pass that used to clear it are one launch).
-constexpr int kMergedMaxGroups = 32;   // (the waiting wave stages the earlier groups' responses in LDS: 128 bytes each)
 template <int W, int NT>
 __global__ __launch_bounds__(64, GOLF_FWDQ2_WAVES) void lpc_fwdq2m_kernel(
     const float* __restrict__ ex, int64_t ex_stride, const float* __restrict__ gain, const float* __restrict__ a,
@@ -3354,81 +3244,33 @@ static int device_cu_count() {
     return cache[dev];
 }
 
-// The two-level boundary scan buys latency with (utterance x group) waves whose prologues hold a SIMD's registers
-// (one wave per SIMD).  Measured with 4 batches in flight / one batch alone, two-level vs flat, us per step:
-//   B = 32: 71.9 vs 71.6 / 140 vs 166;  B = 48: 101 vs 94 / 192 vs 214;  B = 64: 132 vs 117 / 212 vs 229;
-//   (with the earlier fp32 composites) B = 96: 204 vs 166 / 300 vs 286;  B = 256: 537 vs 437 / 629 vs 515
-// so it is taken while B x NG stays below half the SIMD count (B <= 39 at 2 s), where it costs the pipelined rate nothing.
-// (Build parameter GOLF_SS_TWO_LEVEL_WAVES: a fixed cap on B x NG instead; 0 = 2 x the CU count.)
-#ifndef GOLF_SS_TWO_LEVEL_WAVES
-#define GOLF_SS_TWO_LEVEL_WAVES 0
-#endif
-static bool use_two_level_scan(const SsPlan& p, int B, int flags) {
-    const int64_t cap = GOLF_SS_TWO_LEVEL_WAVES > 0 ? (int64_t)GOLF_SS_TWO_LEVEL_WAVES : (int64_t)2 * device_cu_count();
-    return p.NG > 0 && !(flags & GOLF_SS_FLAT_SCAN) && (int64_t)B * p.NG <= cap;
-}
-
-// Conditioning tiers (see phi_guard): the arguments of the fix-up.  `accurate`: the maps in `ws` come from fp64
-// trajectories already (training path), only tier-3 utterances get their doubles.
-static FixArgs fix_args(const SsPlan& p, const float* a, int F, int M, int hop, char* ws, int accurate, int training = 0) {
+// Conditioning tiers (see phi_guard): the arguments of the fix-up.  Maps that come from fp64 trajectories already (not
+// `fast`: the training path) are `accurate`, only tier-3 utterances get their doubles.
+static FixArgs fix_args(const SsPlan& p, const SsChain& c, const float* a, int B, int F, int M, int hop, char* ws) {
     FixArgs fa;
     fa.a = a;
     fa.PhiT = (float*)(ws + p.off_phiT);
-    fa.Phi = (training && !accurate) ? (float*)(ws + p.off_phi) : nullptr;
+    fa.Phi = (c.training && c.fast) ? (float*)(ws + p.off_phi) : nullptr;
     fa.Phi64 = (double*)(ws + p.off_phi64);
     fa.pmax = (const float*)(ws + p.off_pmax);
     fa.tier = (unsigned*)(ws + p.off_tier);
     fa.status = (unsigned*)(ws + p.off_status);
     fa.fixcnt = (unsigned*)(ws + p.off_fixcnt);
     fa.F = F; fa.M = M; fa.hop = hop; fa.L = p.L; fa.NP = p.NP;
-    fa.B = 0;   // set by the caller
+    fa.B = B;
     fa.g1 = phi_guard(); fa.g2 = phi_guard2(); fa.g3 = phi_guard3(); fa.glog = group_log2_guard();
     fa.hot16 = hot_all_16ths();
     fa.hotn = hot_count();
-    fa.accurate = accurate;
+    fa.accurate = c.fast ? 0 : 1;
     return fa;
-}
-// fix-up workgroups (4 waves of 16 units) per utterance: KF1 lead the grid (the guarantee), KF2 trail it (the speed);
-// together at most one pass over all units of an utterance.  Build parameters GOLF_SS_FIXUP_KF1 (> 0) / GOLF_SS_FIXUP_KF2 (>= 0)
-// fix either count; the defaults take the rules below.
-#ifndef GOLF_SS_FIXUP_KF1
-#define GOLF_SS_FIXUP_KF1 0
-#endif
-#ifndef GOLF_SS_FIXUP_KF2
-#define GOLF_SS_FIXUP_KF2 -1
-#endif
-static void fixup_kf(const SsPlan& p, int NT, int* kf1, int* kf2, bool lone_batch = false) {
-    const int64_t all = ceil_div((int64_t)p.NP * NT, 64);   // workgroups that cover every unit in one pass
-    // Round 6 (G2 = 8: a hot utterance of the recipe now has 50 - 150 hot chunks, not 5 - 20): a caller WITHOUT batches in flight
-    // (no GOLF_SS_THROUGHPUT, two-level path) gets (10, 38) -- trailing workgroups cost a lone batch nothing, leading ones cost its
-    // cold utterances.  One batch alone over 32 recipe seeds, mean / cold / hot / tier 3, us: (6, 10) 140.4 / 123.2 / 147.6 / 170.3;
-    // (10, 22) 137.3 / 122.4 / 142.9 / 164.1; (10, 38) 136.2 / 121.8 / 142.2 / 161.1; (8, 48) 136.8; (10, 59) 137.3; (6, 63) 137.8;
-    // (16, 32) 139.0 / 128.8 / ..; (32, 0) 140.1 / 131.1.  With four batches in flight the same settings LOSE (headline 68.7 ->
-    // 70.2 - 72.6 us/step): there every idle workgroup is dispatch cost, and (6, 10) stays.
-    int k1 = GOLF_SS_FIXUP_KF1 > 0 ? GOLF_SS_FIXUP_KF1 : (lone_batch ? 10 : 6);
-    if (k1 > all) k1 = (int)(all < 1 ? 1 : all);
-    // Every fix-up workgroup that finds nothing to do is dispatch cost, and with several batches in flight that is what
-    // counts.  Measured, (KF1, KF2) -> us/step pipelined: B = 256, launch of its own (18 hot utterances + one tier 3 in the
-    // four slots; kernel alone in brackets): (6, 10) 452 [77], (6, 26) 461 [52], (6, 42) 470 [61], (6, 90) 483 [67];
-    // B = 32, merged into the pre-pass (headline / driver's 20 steps / recipe_stream): (6, 10) 74.3 / 82.9 / 77.9,
-    // (6, 26) 74.9 / 83.5 / 78.4, (6, 42) 75.8 / 86.4 / 80.9.  16 workgroups = 1024 units per pass: one pass for up to 46 hot
-    // chunks of an utterance (typical: 5 - 20); a tier-3 utterance (all 199) takes five.
-    int64_t k2 = GOLF_SS_FIXUP_KF2 >= 0 ? GOLF_SS_FIXUP_KF2 : (lone_batch ? 38 : 10);
-    if (k1 + k2 > all) k2 = all - k1 > 0 ? all - k1 : 0;
-    *kf1 = k1;
-    *kf2 = (int)k2;
 }
 
 // ... as a launch of its own (flat-scan path)
 template <int W, int NT>
-static int launch_fixup(const SsPlan& p, const float* a, int B, int F, int M, int hop, char* ws, int accurate,
-                        int training, hipStream_t st) {
-    if (p.NP <= 0) return GOLF_OK;
-    int k1, k2;
-    fixup_kf(p, NT, &k1, &k2);
-    FixArgs fa = fix_args(p, a, F, M, hop, ws, accurate, training);
-    fa.B = B;
-    hipLaunchKernelGGL((lpc_fixup_kernel<W, NT>), dim3((unsigned)(k1 + k2), B), dim3(256), 0, st, fa);
+static int launch_fixup(const SsPlan& p, const SsChain& c, const float* a, int B, int F, int M, int hop, char* ws,
+                        hipStream_t st) {
+    hipLaunchKernelGGL((lpc_fixup_kernel<W, NT>), dim3((unsigned)(c.k1 + c.k2), B), dim3(256), 0, st,
+                       fix_args(p, c, a, B, F, M, hop, ws));
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }
@@ -3436,54 +3278,46 @@ static int launch_fixup(const SsPlan& p, const float* a, int B, int F, int M, in
 // Transitions prepared ahead of the excitation: what the forward's boundary scan derives from the matrices alone -- the
 // fix-up of hot chunk maps and, with the two-level scan, the group composites (one launch).
 template <int W, int NT>
-static int launch_composites(const SsPlan& p, const float* a, int B, int F, int M, int hop, char* ws, int accurate,
-                             int flags, hipStream_t st) {
-    const int training = (accurate || (flags & GOLF_SS_TRAINING)) ? 1 : 0;   // the backward follows: keep what it needs
+static int launch_composites(const SsPlan& p, const SsChain& c, const float* a, int B, int F, int M, int hop, char* ws,
+                             hipStream_t st) {
     if constexpr (NT <= 24) {
-        if (use_two_level_scan(p, B, flags)) {
-            FixArgs fa = fix_args(p, a, F, M, hop, ws, accurate, training);
-            fa.B = B;
-            int k1, k2;
-            fixup_kf(p, NT, &k1, &k2, !(flags & GOLF_SS_THROUGHPUT));
-            const int nf = B * (k1 + k2), nu = p.NG * B;
-            hipLaunchKernelGGL((lpc_group_prepass_kernel<W, NT>), dim3((unsigned)(nf + nu)), dim3(256), 0, st,
+        if (c.two_level) {
+            hipLaunchKernelGGL((lpc_group_prepass_kernel<W, NT>), dim3((unsigned)(c.nf + c.nu)), dim3(256), 0, st,
                                (const float*)(ws + p.off_phiT), (float*)nullptr, (float*)(ws + p.off_mt),
-                               (float*)nullptr, p.NP, p.NG, B, 1, fa, k1, k2,
-                               training ? (float*)(ws + p.off_mtT) : (float*)nullptr, ZPassArgs{nullptr, 0, nullptr, 0});
+                               (float*)nullptr, p.NP, p.NG, B, 1, fix_args(p, c, a, B, F, M, hop, ws), c.k1, c.k2,
+                               c.training ? (float*)(ws + p.off_mtT) : (float*)nullptr, ZPassArgs{nullptr, 0, nullptr, 0});
             GOLF_LAUNCH_CHECK();
             return GOLF_OK;
         }
     }
-    return launch_fixup<W, NT>(p, a, B, F, M, hop, ws, accurate, training, st);
+    return launch_fixup<W, NT>(p, c, a, B, F, M, hop, ws, st);
 }
 
 // The fp32 transition matrices alone (+ their per-chunk maxima): needs only the coefficients.
 template <int W, int NT>
-static int launch_maps(const SsPlan& p, const float* a, int B, int F, int M, int hop, char* ws, int flags, hipStream_t st) {
-    if (p.NP <= 0) return GOLF_OK;
+static int launch_maps(const SsPlan& p, const float* a, int B, int F, int M, int hop, char* ws, bool training, hipStream_t st) {
     float* Phi = (float*)(ws + p.off_phi);
     float* PhiT = (float*)(ws + p.off_phiT);
     const int nq = B * p.NP;
-    float* phi_out = (flags & GOLF_SS_TRAINING) ? Phi : (float*)nullptr;
     hipLaunchKernelGGL((lpc_p1f_kernel<W, NT, 2>), dim3((unsigned)ceil_div(nq, P1fGeom<W, NT, 2>::CPW * P1F_WPB)),
                        dim3(64 * P1F_WPB), 0, st, a, PhiT, F, M, hop, p.L, p.NP, nq, (float*)(ws + p.off_pmax),
-                       (unsigned*)(ws + p.off_fixcnt), B, phi_out);
+                       (unsigned*)(ws + p.off_fixcnt), B, training ? Phi : (float*)nullptr);
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }
 
 template <int W, int NT>
-static int launch_transitions(const SsPlan& p, const float* a, int B, int T, int F, int M, int hop, char* ws,
-                              int fast, int flags, hipStream_t st) {
+static int launch_transitions(const SsPlan& p, const SsChain& c, bool composites, const float* a, int B, int F, int M,
+                              int hop, char* ws, hipStream_t st) {
     if (p.NP <= 0) return GOLF_OK;
+    if (c.fast) {  // fp32 trajectories as float2 pairs (the forward then runs one refinement sweep)
+        if (int rc = launch_maps<W, NT>(p, a, B, F, M, hop, ws, c.training, st)) return rc;
+        if (!composites) return GOLF_OK;   // the forward runs the fix-up and the composites itself
+        return launch_composites<W, NT>(p, c, a, B, F, M, hop, ws, st);
+    }
     float* Phi = (float*)(ws + p.off_phi);
     float* PhiT = (float*)(ws + p.off_phiT);
     const int nq = B * p.NP;
-    if (fast) {  // fp32 trajectories as float2 pairs (the forward then runs one refinement sweep)
-        if (int rc = launch_maps<W, NT>(p, a, B, F, M, hop, ws, flags, st)) return rc;
-        if (flags & GOLF_SS_MAPS_ONLY) return GOLF_OK;   // the forward runs the fix-up and the composites itself
-        return launch_composites<W, NT>(p, a, B, F, M, hop, ws, 0, flags, st);
-    }
     constexpr int NG = (NT + 2) / 3;
     hipLaunchKernelGGL((lpc_p1h_kernel<W, NT, 3, double>), dim3((unsigned)ceil_div(ceil_div(nq, 64) * NG, 4)),
                        dim3(256), 0, st, a, Phi, PhiT, F, M, hop, p.L, p.NP, nq);
@@ -3491,7 +3325,7 @@ static int launch_transitions(const SsPlan& p, const float* a, int B, int T, int
     hipLaunchKernelGGL((lpc_transpose_kernel<W, NT>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st,
                        (const float*)Phi, PhiT, nq, (float*)(ws + p.off_pmax), (unsigned*)(ws + p.off_fixcnt), B);
     GOLF_LAUNCH_CHECK();
-    return launch_composites<W, NT>(p, a, B, F, M, hop, ws, 1, flags, st);
+    return composites ? launch_composites<W, NT>(p, c, a, B, F, M, hop, ws, st) : GOLF_OK;
 }
 
 // Fork/join helper: `side` runs P1h (needs only `a`) while `st` runs P1z (needs the excitation).
@@ -3518,10 +3352,11 @@ struct ForkJoin {
     }
 };
 
+// ss_chain's decisions in launch order
 template <int W, int NT>
-static int launch_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const float* gain, const float* a, float* y,
-                      int64_t y_stride, int B, int T, int F, int M, int hop, char* ws, int flags, hipStream_t side,
-                      hipStream_t st) {
+static int launch_fwd(const SsPlan& p, const SsChain& c, int n_cu, const float* ex, int64_t ex_stride, const float* gain,
+                      const float* a, float* y, int64_t y_stride, int B, int T, int F, int M, int hop, char* ws,
+                      hipStream_t side, hipStream_t st) {
     float* PhiT = (float*)(ws + p.off_phiT);
     float* z = (float*)(ws + p.off_z);
     float* S = (float*)(ws + p.off_S);
@@ -3529,76 +3364,52 @@ static int launch_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const
     unsigned* nonfinite = (unsigned*)(ws + p.off_status);
     const double* Phi64 = (const double*)(ws + p.off_phi64);
     constexpr int D = 8;
-    const int fast = (flags & GOLF_SS_FAST_TRANSITIONS) ? 1 : 0;
-    const int training = (!fast || (flags & GOLF_SS_TRAINING)) ? 1 : 0;   // the backward follows: keep what it needs
     ForkJoin fork, join;
-    bool fused_p1 = false;     // the fix-up of hot maps and the group composites are still to be run by this call
-    bool z_done = false;       // the zero-state pass ran inside the transition launch (lpc_p1fz / lpc_p1hz)
-    // Round 4: the zero-state pass inside the pre-pass launch (lpc_group_prepass_kernel `parts` bit 2) -- the transition
-    // kernel then needs only the coefficients and is a launch of its own (or part of the oscillator's: MAPS_ONLY).
-    bool two_level = false;
-    if constexpr (NT <= 24) two_level = use_two_level_scan(p, B, flags);
-    const bool maps_only = (flags & GOLF_SS_HAVE_TRANSITIONS) && (flags & GOLF_SS_MAPS_ONLY);
-    const bool zin = two_level && fast && !side && !(flags & GOLF_SS_SPLIT_P1) && p.NP > 0 &&
-                     (maps_only || (flags & GOLF_SS_THROUGHPUT));
-    if (p.NP > 0) {
-        if (!(flags & GOLF_SS_HAVE_TRANSITIONS)) {
-            hipStream_t s1 = st;
-            if (side) {
-                if (fork.record_and_wait(st, side)) return fail((int)hipErrorUnknown, "ltv_allpole_fwd: stream fork failed");
-                s1 = side;
+    switch (c.maps) {
+        case SsMaps::Own:   // the matrices alone; fix-up, composites and the zero-state pass follow in the pre-pass launch
+            if (int rc = launch_maps<W, NT>(p, a, B, F, M, hop, ws, c.training, st)) return rc;
+            break;
+        case SsMaps::WithZeroState: {   // transitions + zero-state pass in one launch
+            constexpr int KT = 3;
+            const int nq = B * p.NP, ncg = (int)ceil_div(p.NP, 16);
+            const int64_t nunit = (int64_t)ncg * B;
+            const int nblk = c.fast ? (int)ceil_div(nq, P1fGeom<W, NT>::CPW * P1F_WPB) : (int)ceil_div(ceil_div(nq, 64) * ((NT + KT - 1) / KT), 4);
+            const int upw = ss_upw(nblk, nunit, n_cu), nblk_z = (int)ceil_div(nunit, 4 * upw);
+            if (c.fast) {
+                hipLaunchKernelGGL((lpc_p1fz_kernel<W, NT>), dim3((unsigned)(nblk + nblk_z)), dim3(64 * P1F_WPB),
+                                   0, st, ex, ex_stride, gain, a, z, PhiT, T, F, M, hop, p.L, p.NP, nq, nblk, ncg,
+                                   B, upw, (float*)(ws + p.off_pmax), (unsigned*)(ws + p.off_fixcnt),
+                                   c.training ? (float*)(ws + p.off_phi) : (float*)nullptr);
+                GOLF_LAUNCH_CHECK();
+            } else {
+                float* Phi = (float*)(ws + p.off_phi);
+                hipLaunchKernelGGL((lpc_p1hz_kernel<W, NT, KT>), dim3((unsigned)(nblk + nblk_z)), dim3(256), 0, st,
+                                   ex, ex_stride, gain, a, z, Phi, PhiT, T, F, M, hop, p.L, p.NP, nq, nblk, ncg, B,
+                                   upw);
+                GOLF_LAUNCH_CHECK();
+                hipLaunchKernelGGL((lpc_transpose_kernel<W, NT>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st,
+                                   (const float*)Phi, PhiT, nq, (float*)(ws + p.off_pmax),
+                                   (unsigned*)(ws + p.off_fixcnt), B);
+                GOLF_LAUNCH_CHECK();
             }
-            if (zin) {   // the matrices alone; fix-up, composites and the zero-state pass follow in the pre-pass launch
-                if (int rc = launch_maps<W, NT>(p, a, B, F, M, hop, ws, flags, st)) return rc;
-                fused_p1 = true;
-            } else if (!side && !(flags & GOLF_SS_SPLIT_P1)) {   // transitions + zero-state pass in one launch
-                const int nq = B * p.NP, ncg = (int)ceil_div(p.NP, 16);
-                const int64_t nunit = (int64_t)ncg * B;
-                const int n_cu = device_cu_count();
-                if (fast) {
-                    const int nblk_f = (int)ceil_div(nq, P1fGeom<W, NT>::CPW * P1F_WPB);
-                    int upw = 1;
-                    while (upw < 4 && nblk_f + ceil_div(nunit, 4 * upw) > n_cu) ++upw;
-                    const int nblk_z = (int)ceil_div(nunit, 4 * upw);
-                    hipLaunchKernelGGL((lpc_p1fz_kernel<W, NT>), dim3((unsigned)(nblk_f + nblk_z)), dim3(64 * P1F_WPB),
-                                       0, st, ex, ex_stride, gain, a, z, PhiT, T, F, M, hop, p.L, p.NP, nq, nblk_f, ncg,
-                                       B, upw, (float*)(ws + p.off_pmax), (unsigned*)(ws + p.off_fixcnt),
-                                       training ? (float*)(ws + p.off_phi) : (float*)nullptr);
-                    GOLF_LAUNCH_CHECK();
-                } else {
-                    constexpr int KT = 3, NG = (NT + KT - 1) / KT;
-                    float* Phi = (float*)(ws + p.off_phi);
-                    const int nblk_h = (int)ceil_div(ceil_div(nq, 64) * NG, 4);
-                    int upw = 1;
-                    while (upw < 4 && nblk_h + ceil_div(nunit, 4 * upw) > n_cu) ++upw;
-                    const int nblk_z = (int)ceil_div(nunit, 4 * upw);
-                    hipLaunchKernelGGL((lpc_p1hz_kernel<W, NT, KT>), dim3((unsigned)(nblk_h + nblk_z)), dim3(256), 0, st,
-                                       ex, ex_stride, gain, a, z, Phi, PhiT, T, F, M, hop, p.L, p.NP, nq, nblk_h, ncg, B,
-                                       upw);
-                    GOLF_LAUNCH_CHECK();
-                    hipLaunchKernelGGL((lpc_transpose_kernel<W, NT>), dim3((unsigned)ceil_div(nq, 4)), dim3(256), 0, st,
-                                       (const float*)Phi, PhiT, nq, (float*)(ws + p.off_pmax),
-                                       (unsigned*)(ws + p.off_fixcnt), B);
-                    GOLF_LAUNCH_CHECK();
-                }
-                fused_p1 = z_done = true;
-            } else if (int rc = launch_transitions<W, NT>(p, a, B, T, F, M, hop, ws, fast, flags, s1)) {
-                return rc;
-            }
-        } else if (maps_only) {
-            fused_p1 = true;   // the caller's transitions call left the matrices only
+            break;
         }
-        if (!zin && !z_done) {
-            // the zero-state pass as a launch of its own (prepared transitions, side stream, SPLIT_P1)
-            hipLaunchKernelGGL((lpc_fwdq_kernel<W, NT, 0>), dim3((unsigned)ceil_div(p.NP, 16), B), dim3(64), 0, st, ex,
-                               ex_stride, gain, a, (const float*)nullptr, z, (int64_t)0, T, F, M, hop, p.L, p.NP, p.NP,
-                               (const float*)nullptr, (const unsigned*)nullptr);
-            GOLF_LAUNCH_CHECK();
-        }
-        if (side && join.record_and_wait(side, st)) return fail((int)hipErrorUnknown, "ltv_allpole_fwd: stream join failed");
+        case SsMaps::ViaTransitions:   // with the fix-up and the composites, beside the zero-state pass
+            if (c.fork && fork.record_and_wait(st, side)) return fail((int)hipErrorUnknown, "ltv_allpole_fwd: stream fork failed");
+            if (int rc = launch_transitions<W, NT>(p, c, true, a, B, F, M, hop, ws, c.fork ? side : st)) return rc;
+            break;
+        default: break;   // None, Have
     }
+    if (c.zero_state == SsZeroState::Own) {
+        // the zero-state pass as a launch of its own (prepared transitions, side stream, SPLIT_P1)
+        hipLaunchKernelGGL((lpc_fwdq_kernel<W, NT, 0>), dim3((unsigned)ceil_div(p.NP, 16), B), dim3(64), 0, st, ex,
+                           ex_stride, gain, a, (const float*)nullptr, z, (int64_t)0, T, F, M, hop, p.L, p.NP, p.NP,
+                           (const float*)nullptr, (const unsigned*)nullptr);
+        GOLF_LAUNCH_CHECK();
+    }
+    if (c.join && join.record_and_wait(side, st)) return fail((int)hipErrorUnknown, "ltv_allpole_fwd: stream join failed");
     if constexpr (NT <= 24) {
-        if (two_level) {   // two-level boundary scan (see the kernels above)
+        if (c.two_level) {   // two-level boundary scan (see the kernels above)
             float* MT = (float*)(ws + p.off_mt);
             float* Vz = (float*)(ws + p.off_gv);                    // [b][NG][32] zero-state group responses
             float* Vd = Vz + (size_t)B * p.NG * 32;                   // ... and the groups' responses to the defects
@@ -3610,29 +3421,16 @@ static int launch_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const
             unsigned* arrived = (unsigned*)(ws + p.off_fixcnt) + 2 * (size_t)B + 1;
             const int gxf = (int)ceil_div(p.NC, kGroup);
             unsigned* gflag = (unsigned*)(ws + p.off_gflag);
-            // One batch alone (latency chain): the two chunk passes as ONE launch.  With batches in flight (GOLF_SS_THROUGHPUT) the
-            // pair of thin launches stays: measured 68.4 vs 70.5 us/step -- a wave that lives through both sweeps holds its registers
-            // for 44 us, waiting included.
-            // ... and only while its whole grid is resident at once (296 VGPRs: one wave per SIMD), which is what its waits rely on
-            // (see the kernel's comment).  use_two_level_scan's own cap (B x NG <= 2 x CUs) keeps today's shapes far below that.
-            const bool merged = !(flags & GOLF_SS_THROUGHPUT) && p.NG <= kMergedMaxGroups &&
-                                (int64_t)gxf * (B + ceil_div(B, gxf)) <= (int64_t)4 * device_cu_count();
             // transitions prepared ahead (HAVE_TRANSITIONS) or forked onto the side stream: their composites came with them
-            FixArgs fa = fix_args(p, a, F, M, hop, ws, fast ? 0 : 1, training);
-            fa.B = B;
-            int k1, k2;
-            fixup_kf(p, NT, &k1, &k2, !(flags & GOLF_SS_THROUGHPUT));
-            const int nf = B * (k1 + k2), nu = p.NG * B, nz = (int)ceil_div(nu, 4);
-            const int parts = (fused_p1 ? 3 : 2) | (zin ? 4 : 0), count = (fused_p1 ? nf + nu : 0) + nz;   // in workgroups
+            const int count = (c.owed == SsOwed::Prepass ? c.nf + c.nu : 0) + c.nz;   // in workgroups
             hipLaunchKernelGGL((lpc_group_prepass_kernel<W, NT>), dim3((unsigned)count), dim3(256), 0, st,
-                               (const float*)PhiT, z, MT, Vz, p.NP, p.NG, B, parts, fa, k1, k2,
-                               training ? (float*)(ws + p.off_mtT) : (float*)nullptr,
-                               ZPassArgs{ex, ex_stride, gain, T, merged ? gflag : (unsigned*)nullptr, B * (p.NG + 1), nonfinite});
+                               (const float*)PhiT, z, MT, Vz, p.NP, p.NG, B, c.parts, fix_args(p, c, a, B, F, M, hop, ws),
+                               c.k1, c.k2, c.training ? (float*)(ws + p.off_mtT) : (float*)nullptr,
+                               ZPassArgs{ex, ex_stride, gain, T, c.merged ? gflag : (unsigned*)nullptr, B * (p.NG + 1), nonfinite});
             GOLF_LAUNCH_CHECK();
             // refinement pass (both precisions of the maps: the sweep is what makes the states the sequential recursion's)
             const int gx3 = (int)ceil_div(p.NP, kGroup);
-            const bool thin = (flags & GOLF_SS_THROUGHPUT) != 0;
-            if (merged) {   // refinement + final pass in one launch (lpc_fwdq2m_kernel)
+            if (c.merged) {   // refinement + final pass in one launch (lpc_fwdq2m_kernel)
                 hipLaunchKernelGGL((lpc_fwdq2m_kernel<W, NT>), dim3((unsigned)gxf, B + (int)ceil_div(B, gxf)), dim3(64), 0, st, ex,
                                    ex_stride, gain, a, y, y_stride, T, F, M, hop, p.L, p.NC, (const float*)PhiT, (const float*)MT,
                                    (const float*)Vz, Vd, (const float*)z, p.NP, p.NG, S1, tier, nonfinite, B, Phi64, M64, V64, G64,
@@ -3650,14 +3448,14 @@ static int launch_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const
                                gain, a, y, y_stride, T, F, M, hop, p.L, p.NC, (const float*)PhiT, (const float*)MT,            \
                                (const float*)Vd, (float*)nullptr, (const float*)dfc, p.NP, p.NG, S1, tier, nonfinite, B,       \
                                Phi64, M64, V64, G64, arrived, (const float*)z);
-            if (thin) { GOLF_FWDQ2_LAUNCH(true) } else { GOLF_FWDQ2_LAUNCH(false) }
+            if (c.thin) { GOLF_FWDQ2_LAUNCH(true) } else { GOLF_FWDQ2_LAUNCH(false) }
 #undef GOLF_FWDQ2_LAUNCH
             GOLF_LAUNCH_CHECK();
             return GOLF_OK;
         }
     }
-    if (fused_p1)   // (otherwise launch_transitions / the caller's transitions call ran it)
-        if (int rc = launch_fixup<W, NT>(p, a, B, F, M, hop, ws, fast ? 0 : 1, training, st)) return rc;
+    if (c.owed == SsOwed::Fixup)   // (otherwise launch_transitions / the caller's transitions call ran it)
+        if (int rc = launch_fixup<W, NT>(p, c, a, B, F, M, hop, ws, st)) return rc;
     hipLaunchKernelGGL((lpc_p2_scan_kernel<W, NT, D, false>), dim3(2 * B), dim3(64), 0, st, (const float*)PhiT,
                        (const float*)z, S, p.NC, p.NP, B, tier, Phi64, nonfinite);
     GOLF_LAUNCH_CHECK();
@@ -3678,25 +3476,39 @@ static int launch_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const
     return GOLF_OK;
 }
 
+// The end of both backwards: g -> g_ex and the hat-weighted correlations per segment, then the segment -> frame reduction.
+static int launch_grad_tail(const SsPlan& p, const float* y, int64_t y_stride, const float* ex, int64_t ex_stride,
+                            const float* gain, float* g_ex, int64_t g_ex_stride, float* g_gain, float* g_a, int B, int T,
+                            int F, int M, int hop, char* ws, int tail, hipStream_t st) {
+    const float* gbuf = (const float*)(ws + p.off_g);
+    float* pa = (float*)(ws + p.off_pa);
+    float* pg = (float*)(ws + p.off_pg);
+    hipLaunchKernelGGL(lpc_grad_corr_kernel, dim3((unsigned)ceil_div(p.NSEG, 4), B), dim3(256), 0, st, gbuf, (int64_t)T, y,
+                       y_stride, ex, ex_stride, gain, g_ex, g_ex_stride, pa, pg, T, F, p.NT, p.W, hop, p.seg, p.NSEG, tail);
+    GOLF_LAUNCH_CHECK();
+    const int64_t n4 = (int64_t)B * F * (M + 1);
+    hipLaunchKernelGGL(lpc_grad_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)pa,
+                       (const float*)pg, g_a, g_gain, B, F, M, p.W, hop, p.seg, p.NSEG);
+    GOLF_LAUNCH_CHECK();
+    return GOLF_OK;
+}
+
 template <int W, int NT>
-static int launch_bwd(const SsPlan& p, const float* gy, int64_t gy_stride, const float* y, int64_t y_stride,
+static int launch_bwd(const SsPlan& p, bool two_level, const float* gy, int64_t gy_stride, const float* y, int64_t y_stride,
                       const float* ex, int64_t ex_stride, const float* gain, const float* a, float* g_ex,
                       int64_t g_ex_stride, float* g_gain, float* g_a, int B, int T, int F, int M, int hop, char* ws,
-                      int flags, int tail, hipStream_t st) {
+                      int tail, hipStream_t st) {
     const float* Phi = (const float*)(ws + p.off_phi);
     float* zadj = (float*)(ws + p.off_zadj);
     float* lam = (float*)(ws + p.off_lam);
     float* gbuf = (float*)(ws + p.off_g);
-    float* pa = (float*)(ws + p.off_pa);
-    float* pg = (float*)(ws + p.off_pg);
     float* dadj = (float*)(ws + p.off_dadj);
     const unsigned* tier = p.NP > 0 ? (const unsigned*)(ws + p.off_tier) : nullptr;   // as the forward left them
     const double* Phi64 = (const double*)(ws + p.off_phi64);
     constexpr int D = 8;
     const dim3 gq((unsigned)ceil_div(p.NC, 16), B);
-    bool done = false;
     if constexpr (NT <= 24) {
-        if (p.NP > 0 && use_two_level_scan(p, B, flags)) {   // two-level adjoint scan + refinement sweep (see lpc_adjq2_kernel)
+        if (two_level) {   // two-level adjoint scan + refinement sweep (see lpc_adjq2_kernel)
             const float* MTt = (const float*)(ws + p.off_mtT);   // written by the (training) forward's pre-pass
             float* Wz = (float*)(ws + p.off_wadj);
             float* Wd = Wz + (size_t)B * p.NG * 32;
@@ -3719,83 +3531,57 @@ static int launch_bwd(const SsPlan& p, const float* gy, int64_t gy_stride, const
                                hop, p.L, p.NC, Phi, MTt, (const float*)Wd, (float*)nullptr, (const float*)dadj, p.NP, p.NG,
                                L1, tier, B, Phi64, M64, W64, GA64, arrived, (const float*)zadj);
             GOLF_LAUNCH_CHECK();
-            done = true;
+            return launch_grad_tail(p, y, y_stride, ex, ex_stride, gain, g_ex, g_ex_stride, g_gain, g_a, B, T, F, M, hop, ws, tail, st);
         }
     }
-    if (!done) {   // flat adjoint scan, with the same refinement sweep in delta form
-        hipLaunchKernelGGL((lpc_adjq_kernel<W, NT, 0>), gq, dim3(64), 0, st, gy, gy_stride, a, (const float*)nullptr,
-                           zadj, (int64_t)0, T, F, M, hop, p.L, p.NC, tier);
+    // flat adjoint scan, with the same refinement sweep in delta form
+    hipLaunchKernelGGL((lpc_adjq_kernel<W, NT, 0>), gq, dim3(64), 0, st, gy, gy_stride, a, (const float*)nullptr,
+                       zadj, (int64_t)0, T, F, M, hop, p.L, p.NC, tier);
+    GOLF_LAUNCH_CHECK();
+    hipLaunchKernelGGL((lpc_adj_scan_kernel<W, NT, D, false>), dim3(2 * B), dim3(64), 0, st, Phi, (const float*)zadj, lam,
+                       p.NC, p.NP, B, tier, Phi64);
+    GOLF_LAUNCH_CHECK();
+    if (p.NP > 0) {
+        hipLaunchKernelGGL((lpc_adjq_kernel<W, NT, 2>), gq, dim3(64), 0, st, gy, gy_stride, a, (const float*)lam, dadj,
+                           (int64_t)0, T, F, M, hop, p.L, p.NC, tier);
         GOLF_LAUNCH_CHECK();
-        hipLaunchKernelGGL((lpc_adj_scan_kernel<W, NT, D, false>), dim3(2 * B), dim3(64), 0, st, Phi, (const float*)zadj, lam,
+        hipLaunchKernelGGL((lpc_adj_scan_kernel<W, NT, D, true>), dim3(B), dim3(64), 0, st, Phi, (const float*)dadj, lam,
                            p.NC, p.NP, B, tier, Phi64);
         GOLF_LAUNCH_CHECK();
-        if (p.NP > 0) {
-            hipLaunchKernelGGL((lpc_adjq_kernel<W, NT, 2>), gq, dim3(64), 0, st, gy, gy_stride, a, (const float*)lam, dadj,
-                               (int64_t)0, T, F, M, hop, p.L, p.NC, tier);
-            GOLF_LAUNCH_CHECK();
-            hipLaunchKernelGGL((lpc_adj_scan_kernel<W, NT, D, true>), dim3(B), dim3(64), 0, st, Phi, (const float*)dadj, lam,
-                               p.NC, p.NP, B, tier, Phi64);
-            GOLF_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL((lpc_adjq_kernel<W, NT, 1>), gq, dim3(64), 0, st, gy, gy_stride, a, (const float*)lam, gbuf,
-                           (int64_t)T, T, F, M, hop, p.L, p.NC, (const unsigned*)nullptr);
-        GOLF_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(lpc_grad_corr_kernel, dim3((unsigned)ceil_div(p.NSEG, 4), B), dim3(256), 0, st, (const float*)gbuf, (int64_t)T, y,
-                       y_stride, ex, ex_stride, gain, g_ex, g_ex_stride, pa, pg, T, F, NT, W, hop, p.seg, p.NSEG, tail);
+    hipLaunchKernelGGL((lpc_adjq_kernel<W, NT, 1>), gq, dim3(64), 0, st, gy, gy_stride, a, (const float*)lam, gbuf,
+                       (int64_t)T, T, F, M, hop, p.L, p.NC, (const unsigned*)nullptr);
     GOLF_LAUNCH_CHECK();
-    const int n4 = B * F * (M + 1);
-    hipLaunchKernelGGL(lpc_grad_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)pa,
-                       (const float*)pg, g_a, g_gain, B, F, M, W, hop, p.seg, p.NSEG);
-    GOLF_LAUNCH_CHECK();
-    return GOLF_OK;
+    return launch_grad_tail(p, y, y_stride, ex, ex_stride, gain, g_ex, g_ex_stride, g_gain, g_a, B, T, F, M, hop, ws, tail, st);
 }
 
-// eight lanes per utterance while that leaves at most one wave per SIMD (the wave's time per sample falls from ~19 to ~14
+// The serial forward, 8 or 4 lanes per utterance; STATE (golf_ltv_allpole_fwd_state_f32): from and into a carried state.
+// Eight lanes per utterance while that leaves at most one wave per SIMD (the wave's time per sample falls from ~19 to ~14
 // instructions): measured 2673 -> 2381 us at B = 2048, 2785 -> 2481 at 8192; at 16 384 (two waves per SIMD) the quad wins,
 // 3071 vs 3351 -- there the chip is busy either way and the quad does the least total work
-template <int W, int NT>
-static bool serial_use8(int B) {
-    constexpr bool can8 = W % 8 == 0 && W % ((NT + 7) / 8) == 0;
-    return can8 && (int64_t)B * 8 <= (int64_t)64 * 1024;
-}
-
-template <int W, int NT>
-static int launch_serial_fwd(const SsPlan& p, const float* ex, int64_t ex_stride, const float* gain, const float* a,
-                             float* y, int64_t y_stride, int B, int T, int F, int M, int hop, hipStream_t st) {
-    constexpr bool can8 = W % 8 == 0 && W % ((NT + 7) / 8) == 0;
-    const bool use8 = serial_use8<W, NT>(B);
-    if constexpr (can8) {
-        if (use8) {
-            hipLaunchKernelGGL((lpc_serial_fwd_kernel<W, NT, 8>), dim3((unsigned)ceil_div(B, 32)), dim3(256), 0, st, ex, ex_stride,
-                               gain, a, y, y_stride, B, T, F, M, hop);
-            GOLF_LAUNCH_CHECK();
-            return GOLF_OK;
-        }
+template <int W, int NT, int LPU, bool STATE>
+static int serial_fwd_lanes(const float* ex, int64_t ex_stride, const float* gain, const float* a, float* y, int64_t y_stride,
+                             int B, int T, int F, int M, int hop, float* state, hipStream_t st) {
+    const dim3 grid((unsigned)ceil_div(B, 256 / LPU));
+    if constexpr (STATE) {
+        hipLaunchKernelGGL((lpc_serial_fwd_state_kernel<W, NT, LPU>), grid, dim3(256), 0, st, ex, ex_stride, gain, a, y,
+                           y_stride, B, T, F, M, hop, state);
+    } else {
+        hipLaunchKernelGGL((lpc_serial_fwd_kernel<W, NT, LPU>), grid, dim3(256), 0, st, ex, ex_stride, gain, a, y, y_stride,
+                           B, T, F, M, hop);
     }
-    hipLaunchKernelGGL((lpc_serial_fwd_kernel<W, NT, 4>), dim3((unsigned)ceil_div(B, 64)), dim3(256), 0, st, ex, ex_stride,
-                       gain, a, y, y_stride, B, T, F, M, hop);
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }
-
-// golf_ltv_allpole_fwd_state_f32: the serial forward above, from and into a carried state (same lane-count rule)
-template <int W, int NT>
-static int launch_serial_fwd_state(const SsPlan& p, const float* ex, int64_t ex_stride, const float* gain, const float* a,
-                                   float* y, int64_t y_stride, int B, int T, int F, int M, int hop, float* state, hipStream_t st) {
+template <int W, int NT, bool STATE>
+static int launch_serial_fwd(std::bool_constant<STATE>, const SsPlan& p, const float* ex, int64_t ex_stride, const float* gain, const float* a,
+                             float* y, int64_t y_stride, int B, int T, int F, int M, int hop, float* state, hipStream_t st) {
     constexpr bool can8 = W % 8 == 0 && W % ((NT + 7) / 8) == 0;
     if constexpr (can8) {
-        if (serial_use8<W, NT>(B)) {
-            hipLaunchKernelGGL((lpc_serial_fwd_state_kernel<W, NT, 8>), dim3((unsigned)ceil_div(B, 32)), dim3(256), 0, st, ex,
-                               ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state);
-            GOLF_LAUNCH_CHECK();
-            return GOLF_OK;
-        }
+        if ((int64_t)B * 8 <= (int64_t)64 * 1024)
+            return serial_fwd_lanes<W, NT, 8, STATE>(ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state, st);
     }
-    hipLaunchKernelGGL((lpc_serial_fwd_state_kernel<W, NT, 4>), dim3((unsigned)ceil_div(B, 64)), dim3(256), 0, st, ex, ex_stride,
-                       gain, a, y, y_stride, B, T, F, M, hop, state);
-    GOLF_LAUNCH_CHECK();
-    return GOLF_OK;
+    return serial_fwd_lanes<W, NT, 4, STATE>(ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state, st);
 }
 
 template <int W, int NT>
@@ -3803,62 +3589,23 @@ static int launch_serial_bwd(const SsPlan& p, const float* gy, int64_t gy_stride
                              const float* ex, int64_t ex_stride, const float* gain, const float* a, float* g_ex,
                              int64_t g_ex_stride, float* g_gain, float* g_a, int B, int T, int F, int M, int hop,
                              char* ws, int tail, hipStream_t st) {
-    float* gbuf = (float*)(ws + p.off_g);
-    float* pa = (float*)(ws + p.off_pa);
-    float* pg = (float*)(ws + p.off_pg);
     hipLaunchKernelGGL((lpc_serial_adj_kernel<W, NT>), dim3((unsigned)ceil_div(B, 64)), dim3(256), 0, st, gy, gy_stride,
-                       a, gbuf, (int64_t)T, B, T, F, M, hop);
+                       a, (float*)(ws + p.off_g), (int64_t)T, B, T, F, M, hop);
     GOLF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(lpc_grad_corr_kernel, dim3((unsigned)ceil_div(p.NSEG, 4), B), dim3(256), 0, st,
-                       (const float*)gbuf, (int64_t)T, y, y_stride, ex, ex_stride, gain, g_ex, g_ex_stride, pa, pg, T,
-                       F, NT, W, hop, p.seg, p.NSEG, tail);
-    GOLF_LAUNCH_CHECK();
-    const int64_t n4 = (int64_t)B * F * (M + 1);
-    hipLaunchKernelGGL(lpc_grad_reduce_kernel, dim3((unsigned)ceil_div(n4, 256)), dim3(256), 0, st, (const float*)pa,
-                       (const float*)pg, g_a, g_gain, B, F, M, W, hop, p.seg, p.NSEG);
-    GOLF_LAUNCH_CHECK();
-    return GOLF_OK;
+    return launch_grad_tail(p, y, y_stride, ex, ex_stride, gain, g_ex, g_ex_stride, g_gain, g_a, B, T, F, M, hop, ws, tail, st);
 }
 
-// (W, NT) instantiation table — must list exactly kTable.
-#define GOLF_SS_CASE(FN, w, nt, ...) case (w) * 100 + (nt): return FN<w, nt>(__VA_ARGS__);
-#ifdef GOLF_SS_ONLY_24_22   // dev builds (tools/build_variant.sh): only the benchmark's instantiation, a 10x shorter compile
-#define GOLF_SS_DISPATCH(FN, ...)               \
-    switch (p.W * 100 + p.NT) {                 \
-        GOLF_SS_CASE(FN, 24, 22, __VA_ARGS__)   \
-        default: break;                         \
+// One case per (W, NT) instantiation of lpc_ss_plan.h's table.
+#define GOLF_SS_CASE(w, nt, FN, ...) case (w) * 100 + (nt): return FN<w, nt>(__VA_ARGS__);
+#define GOLF_SS_DISPATCH(FN, ...)                                \
+    switch (p.W * 100 + p.NT) {                                  \
+        GOLF_SS_INSTANCES(GOLF_SS_CASE, FN, __VA_ARGS__)         \
+        default: break;                                          \
     }
-#else
-#define GOLF_SS_DISPATCH(FN, ...)               \
-    switch (p.W * 100 + p.NT) {                 \
-        GOLF_SS_CASE(FN, 8, 2, __VA_ARGS__)     \
-        GOLF_SS_CASE(FN, 8, 4, __VA_ARGS__)     \
-        GOLF_SS_CASE(FN, 8, 6, __VA_ARGS__)     \
-        GOLF_SS_CASE(FN, 16, 8, __VA_ARGS__)    \
-        GOLF_SS_CASE(FN, 16, 12, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 16, 14, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 24, 8, __VA_ARGS__)    \
-        GOLF_SS_CASE(FN, 24, 12, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 24, 16, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 24, 20, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 24, 22, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 32, 16, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 32, 22, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 32, 26, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 32, 30, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 40, 22, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 40, 26, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 40, 32, __VA_ARGS__)   \
-        GOLF_SS_CASE(FN, 40, 38, __VA_ARGS__)   \
-        default: break;                         \
-    }
-#endif
 
 static int ss_mode(int flags) {
     return (flags & GOLF_SS_SERIAL) ? GOLF_SS_SERIAL : ((flags & GOLF_SS_CHUNKED) ? GOLF_SS_CHUNKED : 0);
 }
-// rows of 16 utterances are addressed through one 32-bit buffer descriptor: the serial path needs 16 * stride * 4 B < 2 GB
-
 static bool plan_fast(int B, int T, int F, int M, int hop, SsPlan* p, int flags = 0) {
     return make_ss_plan(B, T, F, M, hop, p, ss_mode(flags));
 }
@@ -3866,6 +3613,12 @@ static bool plan_fast(int B, int T, int F, int M, int hop, SsPlan* p, int flags 
 }  // namespace golf
 
 using namespace golf;
+
+static int check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 255))
+        return fail(GOLF_EWORKSPACE, "%s: workspace needs %zu bytes, 256-aligned (got %zu)", who, need, ws_bytes);
+    return GOLF_OK;
+}
 
 static int check_ss_args(int B, int T, int F, int M, int hop) {
     if (B < 1 || T < 1 || F < 1 || M < 1 || hop < 1) return fail(GOLF_EINVAL, "ltv_allpole: non-positive size");
@@ -3895,12 +3648,9 @@ extern "C" int golf_ltv_allpole_transitions_f32(const float* a, int B, int T, in
     SsPlan p;
     if (!plan_fast(B, T, F, M, hop, &p, flags)) return GOLF_OK;  // no ring plan (lpc_any.hip): no transition matrices
     if (p.serial) return GOLF_OK;                                 // nor has the batch-parallel serial path
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws & 255))
-        return fail(GOLF_EWORKSPACE, "ltv_allpole_transitions: workspace needs %zu bytes, 256-aligned (got %zu)",
-                    p.total, ws_bytes);
-    hipStream_t st = (hipStream_t)stream;
-    const int fast = (flags & GOLF_SS_FAST_TRANSITIONS) ? 1 : 0;
-    GOLF_SS_DISPATCH(launch_transitions, p, a, B, T, F, M, hop, (char*)ws, fast, flags, st)
+    if (int rc = check_ws("ltv_allpole_transitions", ws, ws_bytes, p.total)) return rc;
+    const SsChain t = ss_transitions(p, B, flags, device_cu_count());
+    GOLF_SS_DISPATCH(launch_transitions, p, t, t.owed != SsOwed::None, a, B, F, M, hop, (char*)ws, (hipStream_t)stream)
     return fail(GOLF_EUNSUPPORTED, "ltv_allpole_transitions: no kernel for W=%d NT=%d", p.W, p.NT);
 }
 
@@ -3911,14 +3661,12 @@ extern "C" int golf_ltv_allpole_status_u32(const void* ws, size_t ws_bytes, int 
     hipStream_t st = (hipStream_t)stream;
     SsPlan p;
     // the serial and the wave-per-utterance algorithms have no transition matrices: nothing is recomputed, all four words are 0
-    if (!plan_fast(B, T, F, M, hop, &p, flags) || p.serial || p.NP <= 0) {
+    if (!plan_fast(B, T, F, M, hop, &p, flags) || !ss_has_maps(p)) {
         hipLaunchKernelGGL(lpc_status_zero_kernel, dim3(1), dim3(64), 0, st, (unsigned*)out);
         GOLF_LAUNCH_CHECK();
         return GOLF_OK;
     }
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws & 255))
-        return fail(GOLF_EWORKSPACE, "ltv_allpole_status: workspace needs %zu bytes, 256-aligned (got %zu)", p.total,
-                    ws_bytes);
+    if (int rc = check_ws("ltv_allpole_status", ws, ws_bytes, p.total)) return rc;
     const char* w = (const char*)ws;
     hipLaunchKernelGGL(lpc_status_kernel, dim3(1), dim3(256), 0, st, (const unsigned*)(w + p.off_tier),
                        (const unsigned*)(w + p.off_status), (const unsigned*)(w + p.off_fixcnt),
@@ -3941,16 +3689,16 @@ extern "C" int golf_ltv_allpole_fwd_f32(const float* ex, int64_t ex_stride, cons
         if (flags & GOLF_SS_SERIAL) return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd: serial path needs row strides < 2^24");
         plan_fast(B, T, F, M, hop, &p, GOLF_SS_CHUNKED);
     }
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws & 255))
-        return fail(GOLF_EWORKSPACE, "ltv_allpole_fwd: workspace needs %zu bytes, 256-aligned (got %zu)", p.total,
-                    ws_bytes);
+    if (int rc = check_ws("ltv_allpole_fwd", ws, ws_bytes, p.total)) return rc;
     if (p.serial) {
-        GOLF_SS_DISPATCH(launch_serial_fwd, p, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, st)
+        GOLF_SS_DISPATCH(launch_serial_fwd, std::false_type{}, p, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, nullptr, st)
         return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd: no kernel for W=%d NT=%d", p.W, p.NT);
     }
     hipStream_t side = (hipStream_t)side_stream;
     if (side == st) side = nullptr;
-    GOLF_SS_DISPATCH(launch_fwd, p, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, (char*)ws, flags, side, st)
+    const int n_cu = device_cu_count();
+    const SsChain c = ss_chain(p, B, flags, side != nullptr, n_cu);
+    GOLF_SS_DISPATCH(launch_fwd, p, c, n_cu, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, (char*)ws, side, st)
     return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd: no kernel for W=%d NT=%d", p.W, p.NT);
 }
 
@@ -3966,7 +3714,7 @@ extern "C" int golf_ltv_allpole_fwd_state_f32(const float* ex, int64_t ex_stride
         return launch_any_fwd(ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state, st);
     if (!serial_strides_ok(ex_stride, y_stride))
         return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd_state: serial path needs row strides < 2^24");
-    GOLF_SS_DISPATCH(launch_serial_fwd_state, p, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state, st)
+    GOLF_SS_DISPATCH(launch_serial_fwd, std::true_type{}, p, ex, ex_stride, gain, a, y, y_stride, B, T, F, M, hop, state, st)
     return fail(GOLF_EUNSUPPORTED, "ltv_allpole_fwd_state: no kernel for W=%d NT=%d", p.W, p.NT);
 }
 
@@ -3982,15 +3730,11 @@ extern "C" int golf_ltv_allpole_bwd_f32(const float* gy, int64_t gy_stride, cons
     SsPlan p;
     hipStream_t st = (hipStream_t)stream;
     if (!plan_fast(B, T, F, M, hop, &p, flags)) {   // no ring plan: adjoint by one wave per utterance, g in the workspace
-        if (!ws || ws_bytes < any_ws_bytes(B, T) || ((uintptr_t)ws & 255))
-            return fail(GOLF_EWORKSPACE, "ltv_allpole_bwd: workspace needs %zu bytes, 256-aligned (got %zu)",
-                        any_ws_bytes(B, T), ws_bytes);
+        if (int rc = check_ws("ltv_allpole_bwd", ws, ws_bytes, any_ws_bytes(B, T))) return rc;
         return launch_any_bwd(gy, gy_stride, y, y_stride, ex, ex_stride, gain, a, g_ex, g_ex_stride, g_gain, g_a, B, T, F, M,
                               hop, (char*)ws, (flags & GOLF_SS_ZERO_TAIL) ? g_ex_stride - (int64_t)T : 0, st);
     }
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws & 255))
-        return fail(GOLF_EWORKSPACE, "ltv_allpole_bwd: workspace needs %zu bytes, 256-aligned (got %zu)", p.total,
-                    ws_bytes);
+    if (int rc = check_ws("ltv_allpole_bwd", ws, ws_bytes, p.total)) return rc;
     const int64_t tail64 = (flags & GOLF_SS_ZERO_TAIL) ? g_ex_stride - (int64_t)T : 0;
     if (tail64 > 0x7fffffff) return fail(GOLF_EINVAL, "ltv_allpole_bwd: GOLF_SS_ZERO_TAIL with a row stride beyond 2^31");
     const int tail = (int)tail64;
@@ -4001,8 +3745,9 @@ extern "C" int golf_ltv_allpole_bwd_f32(const float* gy, int64_t gy_stride, cons
                          g_gain, g_a, B, T, F, M, hop, (char*)ws, tail, st)
         return fail(GOLF_EUNSUPPORTED, "ltv_allpole_bwd: no kernel for W=%d NT=%d", p.W, p.NT);
     }
-    GOLF_SS_DISPATCH(launch_bwd, p, gy, gy_stride, y, y_stride, ex, ex_stride, gain, a, g_ex, g_ex_stride, g_gain, g_a,
-                     B, T, F, M, hop, (char*)ws, flags, tail, st)
+    const bool two_level = ss_two_level(p, B, flags, device_cu_count());   // the forward's boundary scan: it left the composites
+    GOLF_SS_DISPATCH(launch_bwd, p, two_level, gy, gy_stride, y, y_stride, ex, ex_stride, gain, a, g_ex, g_ex_stride, g_gain, g_a,
+                     B, T, F, M, hop, (char*)ws, tail, st)
     return fail(GOLF_EUNSUPPORTED, "ltv_allpole_bwd: no kernel for W=%d NT=%d", p.W, p.NT);
 }
 

@@ -116,7 +116,7 @@ def ss_output_length(Tx: int, F: int, hop: int) -> int:
     return min(Tx, (F - 1) * hop + 1)
 
 
-# (ring width, largest order it serves) of the sample-wise filter's ring kernels (csrc/lpc_ss.hip kTable): the time-chunked
+# (ring width, largest order it serves) of the sample-wise filter's ring kernels (csrc/lpc_ss_plan.h GOLF_SS_TABLE): the time-chunked
 # scan and the batch-parallel serial recursion need one ring width that divides the hop and exceeds the order.  Every other
 # shape runs -- and trains -- on the wave-per-utterance kernels of csrc/lpc_any.hip.
 SS_RINGS = ((8, 6), (16, 14), (24, 22), (32, 30), (40, 38))
@@ -294,7 +294,7 @@ def ltv_allpole_ss(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: i
     ``mode``: None/"auto" picks the algorithm by batch size (time-chunked scan below 2048 utterances, batch-parallel
     serial recursion from there on: include/golf_amd.h GOLF_SS_SERIAL); "serial" / "chunked" force one.  "flat-scan"
     forces the chunked algorithm's flat boundary scan.  That is not only a diagnostic: "auto" itself takes the flat scan for
-    every lone batch of more than ~40 utterances below the serial threshold (lpc_ss.hip use_two_level_scan; the two-level scan
+    every lone batch of more than ~40 utterances below the serial threshold (lpc_ss_plan.h ss_two_level; the two-level scan
     is the faster form only while B x groups <= 2 x the CU count) and whenever an utterance has fewer than 48 chunk maps.  Both
     scans are held to the same bound -- 3 e_sequential_fp32 + 1e-4 of the float64 oracle forward, + 2e-4 for the gradients -- by
     the suite's soak (tests/test_gpu_lpc_ss.py::test_conditioning_soak_bounded, ::test_round5_soak_exceedances) and by

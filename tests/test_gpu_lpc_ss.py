@@ -1295,3 +1295,25 @@ def test_source_and_transition_maps_in_one_launch_is_bit_identical(B, seed, M, w
     y2 = GF.source_filter_ss(inp["phase"], inp["wsel"], table, taps, 1, inp["w_hop"], 4, True, inp["gain"], a, 240, add=add)
     y2.square().mean().backward()
     assert torch.isfinite(a.grad).all() and float(a.grad.abs().max()) > 0
+
+
+@pytest.mark.parametrize("fast", [True, False])
+@pytest.mark.parametrize("F", [51, 6])
+def test_split_p1_and_forked_transitions(monkeypatch, F, fast):
+    """GOLF_SS_SPLIT_P1 (functional.SPLIT_P1) and the transitions forked onto a side stream (functional.FORK_TRANSITIONS) take
+    the maps through launch_transitions and the zero-state pass as a launch of its own: other launches around the same
+    arithmetic, so y is the default call's bit for bit.  T 12001 runs the two-level scan (50 chunk maps, 4 groups), T 1201 the
+    flat one."""
+    from golf_amd import functional as GF
+    from oracle import golf_oracle as O
+
+    ex, gain, a = smooth_case(2, F, 22, 240, seed=F)
+    ref = O.ltv_allpole_ss_forward(ex, gain, a, 240)
+    y0 = run_fwd(ex, gain, a, 240, fast=fast)
+    check(y0, ref, f"default F{F} fast={fast}")
+    for knob in ("SPLIT_P1", "FORK_TRANSITIONS"):
+        with monkeypatch.context() as m:
+            m.setattr(GF, knob, True)
+            y = run_fwd(ex, gain, a, 240, fast=fast)
+        check(y, ref, f"{knob} F{F} fast={fast}")
+        assert np.array_equal(y, y0), knob
