@@ -19,7 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
+SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_f64.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
            "stft_filter.hip", "minphase_fir.hip", "lpc_analysis.hip")
 
 _c_f32p = ctypes.c_void_p
@@ -46,6 +46,10 @@ SIGNATURES = {
     "golf_ltv_allpole_status_u32": (_int, [_vp, _sz] + [_int] * 6 + [_vp, _vp]),
     "golf_ltv_allpole_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64,
                                         _c_f32p, _c_f32p] + [_int] * 5 + [_vp, _sz, _int, _vp]),
+    "golf_ltv_allpole_f64_workspace_bytes": (_sz, [_int] * 2),
+    "golf_ltv_allpole_fwd_f64": (_int, [_vp, _i64, _vp, _vp, _vp, _i64] + [_int] * 5 + [_vp, _int, _vp]),
+    "golf_ltv_allpole_bwd_f64": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]
+                                 + [_int] * 5 + [_vp, _sz, _int, _vp]),
     "golf_ltv_inverse_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _i64] + [_int] * 5 + [_vp]),
     "golf_ltv_inverse_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _i64, _c_f32p] + [_int] * 5
                                  + [_vp]),
@@ -257,15 +261,19 @@ def check(rc: int, what: str):
         raise GolfError(f"{what}: {kind} {rc}: {msg}")
 
 
-def require_device(*tensors: torch.Tensor):
+def require_device(*tensors: torch.Tensor, dtype: torch.dtype = torch.float32):
+    """Every tensor on a ROCm device and of ``dtype``: fp32 for every kernel but the float64 sample-wise filter
+    (csrc/lpc_f64.hip), whose callers ask for ``dtype=torch.float64`` explicitly."""
     for t in tensors:
         if t is None:
             continue
         if not t.is_cuda:
             raise GolfError("golf_amd kernels need ROCm device tensors (got a %s tensor); there is no CPU path"
                             % t.device.type)
-        if t.dtype != torch.float32:
-            raise GolfError(f"golf_amd kernels are fp32 (got {t.dtype})")
+        if t.dtype != dtype:
+            if dtype == torch.float32:
+                raise GolfError(f"golf_amd kernels are fp32 (got {t.dtype})")
+            raise GolfError(f"golf_amd: this call takes {dtype} tensors (got {t.dtype})")
 
 
 def stream_ptr() -> int:

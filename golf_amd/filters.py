@@ -48,7 +48,13 @@ def _check_filter_inputs(ex: AudioTensor, gain: AudioTensor, a: AudioTensor) -> 
 
 class LTVMinimumPhaseFilterPrecise(LTVFilterInterface):
     """GOLF-ss end filter: sample-wise time-varying all-pole filter with frame-rate controls
-    (reference models/filters.py:64-113).  ``forward`` runs golf_ltv_allpole_{fwd,bwd}_f32."""
+    (reference models/filters.py:64-113).  ``forward`` runs golf_ltv_allpole_{fwd,bwd}_f32; float64 AudioTensors run the
+    float64 recursion (golf_ltv_allpole_{fwd,bwd}_f64) and come back as float64."""
+
+    # "fp64", set per instance (``model.decoder.end_filter.precision = "fp64"``): fp32 tensors through the float64 recursion
+    # (functional.ltv_allpole_ss(mode="fp64")) -- for the utterances at the edge of stability, a parity check, a render
+    # that has to be right; one serial recursion per utterance instead of the time-chunked scan.  Any other value raises.
+    precision = "fp32"
 
     def __init__(self, lpc_order: int = None, lpc_parameterisation: str = "rc2lpc", max_abs_value: float = 1.0):
         super().__init__()
@@ -97,6 +103,8 @@ class LTVMinimumPhaseFilterPrecise(LTVFilterInterface):
         # the fp32 matrices of the inference path serve training too (ABI 3: the backward runs its own refinement sweep);
         # with grad mode on the handle also keeps what the backward reads -- whichever decoder input ends up requiring a
         # gradient (a frozen filter under a trainable source included: ADVICE r2), the forward can pick it up
+        if self.precision != "fp32" or a.as_tensor().dtype == torch.float64:
+            return   # the float64 recursion has no excitation-independent phase
         self._prepared = GF.ltv_allpole_prepare(a.as_tensor(), hop, T, overlap=overlap, fast=True,
                                                 training=torch.is_grad_enabled())
 
@@ -133,16 +141,21 @@ class LTVMinimumPhaseFilterPrecise(LTVFilterInterface):
         ``(AudioTensor, zf)`` with zf (B, M) the final state -- the ``zi`` of the segment that follows, differentiable
         (not in the reference module; torchlpc.sample_wise_lpc's ``zi``).  Without them: the reference's call."""
         hop = _check_filter_inputs(ex, gain, a)
+        if self.precision not in ("fp32", "fp64"):
+            raise ValueError(f"{type(self).__name__}.precision must be 'fp32' or 'fp64' (got {self.precision!r})")
         prepared, self._prepared = getattr(self, "_prepared", None), None
         x = ex.as_tensor()
+        mode = "fp64" if self.precision == "fp64" else None
+        f64 = mode is not None or x.dtype == torch.float64   # the float64 recursion: no status words to monitor
         st = None
-        if self.health_check and x.is_cuda and not torch.cuda.is_current_stream_capturing():
+        if self.health_check and not f64 and x.is_cuda and not torch.cuda.is_current_stream_capturing():
             self.health()
             st = torch.zeros(4, dtype=torch.int32, device=x.device)
         if zi is None and not return_zf:
-            y = GF.ltv_allpole_ss(x, gain.as_tensor(), a.as_tensor(), hop, prepared, status=st)
+            y = GF.ltv_allpole_ss(x, gain.as_tensor(), a.as_tensor(), hop, prepared, mode=mode, status=st)
         else:
-            y, zf = GF.ltv_allpole_ss(x, gain.as_tensor(), a.as_tensor(), hop, prepared, status=st, zi=zi, return_zf=True)
+            y, zf = GF.ltv_allpole_ss(x, gain.as_tensor(), a.as_tensor(), hop, prepared, mode=mode, status=st, zi=zi,
+                                      return_zf=True)
         if st is not None:
             host = torch.empty(4, dtype=torch.int32, pin_memory=True)
             host.copy_(st, non_blocking=True)

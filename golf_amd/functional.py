@@ -1,7 +1,9 @@
 """torch.autograd.Functions over the C ABI of libgolf_hip.so (include/golf_amd.h).
 
 Plain tensors in, plain tensors out; AudioTensor bookkeeping lives in the nn.Modules.
-Every function raises if the tensors are not fp32 ROCm-device tensors — no CPU path exists.
+Every function raises if the tensors are not ROCm-device tensors — no CPU path exists — and if they are not fp32, with one
+exception: the sample-wise all-pole filter (``ltv_allpole_ss``, ``ltv_allpole_ss_blocks``) also takes float64 tensors, and
+fp32 tensors with ``mode="fp64"``, and then runs its recursion in float64 on the device (csrc/lpc_f64.hip).
 """
 from __future__ import annotations
 
@@ -14,7 +16,7 @@ from . import _lib
 
 __all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "lti_frames_ola",
            "glottal_osc",
-           "ss_output_length", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
+           "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
            "zero_phase_fir_filter_precise", "min_phase_fir_basis", "min_phase_window", "min_phase_fir_kernels",
            "min_phase_fir_filter", "min_phase_fir_filter_precise", "ltv_fir_frames_causal",
@@ -133,6 +135,12 @@ def ss_has_backward(M: int, hop: int, F: int = 2) -> bool:
     return 1 <= M <= 64 and hop >= 1 and F >= 1
 
 
+def ss_has_f64(M: int, hop: int, F: int = 2) -> bool:
+    """True when ltv_allpole_ss runs -- and differentiates -- (lpc order, hop, frames) in float64 (double tensors, or
+    ``mode="fp64"``): every shape the fp32 filter serves, on or off the ring grid."""
+    return ss_has_backward(M, hop, F)
+
+
 # ------------------------------------------------------------------------------------------------
 class _LTVAllPoleSS(torch.autograd.Function):
     @staticmethod
@@ -222,6 +230,111 @@ class _LTVAllPoleSS(torch.autograd.Function):
         return g_ex, g_gain, g_a, None, None, None, None, None, None
 
 
+class _LTVAllPoleF64(torch.autograd.Function):
+    """The sample-wise filter with its recursion in float64 (golf_ltv_allpole_{fwd,bwd}_f64, csrc/lpc_f64.hip): returns
+    ``(y, state)``.  ``io`` = 1: float64 tensors in and out; 0: fp32 tensors, rounded once at the store.  ``zi`` (B, M) or None
+    enters through the kernel's carried-state prologue; it may be a float64 tensor with fp32 I/O -- the ``state`` output of
+    the block before, (B, M) float64 and NOT rounded to the I/O type, which is what keeps a chain of fp32 blocks on the bits
+    of the one-shot call (ltv_allpole_ss_blocks).  ``state`` is None unless ``want_state``; it is differentiable."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, ex, gain, a, zi, hop, length, io, want_state):
+        dtype = torch.float64 if io else torch.float32
+        _lib.require_device(ex, gain, a, dtype=dtype)
+        if zi is not None:
+            _lib.require_device(zi, dtype=dtype if zi.dtype == dtype else torch.float64)
+        lib = _lib.load()
+        ex = _rows(ex)
+        gain = gain.contiguous()
+        a = a.contiguous()
+        B, Tx = ex.shape
+        F, M = a.shape[1], a.shape[2]
+        assert gain.shape == (B, F) and a.shape[0] == B and (zi is None or zi.shape == (B, M))
+        T = ss_output_length(Tx, F, hop)
+        if length is not None:
+            T = min(T, int(length))
+            if T < 1:
+                raise _lib.GolfError(f"ltv_allpole_ss: length={length} leaves nothing to filter")
+        y = torch.empty(B, T, dtype=dtype, device=ex.device)
+        # the kernel's state buffer, in and out: the initial state on entry (zeros when only the final one is wanted)
+        zi64 = None if zi is None else zi.to(torch.float64).contiguous()
+        state = None
+        if zi is not None or want_state:
+            state = torch.zeros(B, M, dtype=torch.float64, device=ex.device) if zi is None else zi64.clone()
+        rc = lib.golf_ltv_allpole_fwd_f64(ex.data_ptr(), ex.stride(0), gain.data_ptr(), a.data_ptr(), y.data_ptr(),
+                                          y.stride(0), B, T, F, M, hop, _lib.ptr(state), io, _lib.stream_ptr())
+        _lib.check(rc, "golf_ltv_allpole_fwd_f64")
+        ctx.hop, ctx.io, ctx.zi_dtype = hop, io, None if zi is None else zi.dtype
+        ctx.save_for_backward(ex, gain, a, y, zi64)
+        ctx.set_materialize_grads(False)   # the cotangent of an unused state arrives as None
+        return y, (state if want_state else None)
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, gy, g_state):
+        ex, gain, a, y, zi64 = ctx.saved_tensors
+        lib = _lib.load()
+        hop, io = ctx.hop, ctx.io
+        B, Tx = ex.shape
+        F, M = a.shape[1], a.shape[2]
+        T = y.shape[1]
+        want_ex, want_gain, want_a, want_zi = ctx.needs_input_grad[:4]
+        if gy is None and g_state is None:
+            return (None,) * 8
+        gy = torch.zeros_like(y) if gy is None else gy.to(y.dtype)
+        H = min(M, T)
+        if g_state is not None:   # state[:, j] = y[:, T-1-j] (j < T), zi[:, j-T] beyond: its cotangent joins theirs
+            gy = gy.clone()
+            gy[:, T - H:] += g_state[:, :H].flip(1).to(y.dtype)
+        gy = _rows(gy)
+        g_ex = torch.empty(B, Tx, dtype=y.dtype, device=ex.device) if want_ex else None   # (the tail's zeros: the kernel)
+        g_gain = torch.empty_like(gain) if want_gain else None
+        g_a = torch.empty_like(a) if want_a else None
+        g_zi = torch.empty(B, M, dtype=torch.float64, device=ex.device) if want_zi else None
+        ws = _workspace(lib.golf_ltv_allpole_f64_workspace_bytes(B, T), ex.device)
+        rc = lib.golf_ltv_allpole_bwd_f64(gy.data_ptr(), gy.stride(0), y.data_ptr(), y.stride(0), ex.data_ptr(), ex.stride(0),
+                                          gain.data_ptr(), a.data_ptr(), _lib.ptr(zi64), _lib.ptr(g_ex), Tx, Tx,
+                                          _lib.ptr(g_gain), _lib.ptr(g_a), _lib.ptr(g_zi), B, T, F, M, hop, ws.data_ptr(),
+                                          ws.numel(), io, _lib.stream_ptr())
+        _lib.check(rc, "golf_ltv_allpole_bwd_f64")
+        if g_zi is not None:
+            if g_state is not None and T < M:
+                g_zi[:, :M - T] += g_state[:, T:]
+            g_zi = g_zi.to(ctx.zi_dtype)
+        return g_ex, g_gain, g_a, g_zi, None, None, None, None
+
+
+def _ss_route(ex, gain, a, zi, mode, status=None):
+    """The checks of ``zi`` and ``status`` and the choice of _ss_f64_io, for ltv_allpole_ss and ltv_allpole_ss_blocks."""
+    if zi is not None and (zi.dim() != 2 or a.dim() != 3 or tuple(zi.shape) != (a.shape[0], a.shape[2])):
+        raise _lib.GolfError(f"ltv_allpole_ss: zi {tuple(zi.shape)} for a {tuple(a.shape)}: a (B, M) initial state required")
+    io = _ss_f64_io(ex, gain, a, zi, mode)
+    if zi is not None and (zi.device != ex.device or not zi.is_floating_point()
+                           or (zi.dtype not in (torch.float32, torch.float64) and not torch.is_autocast_enabled())):
+        raise _lib.GolfError(f"ltv_allpole_ss: zi must be an fp32 (or, with float64 tensors, a float64) tensor on {ex.device} "
+                             f"(got {zi.dtype} on {zi.device})")
+    if io is not None and status is not None:
+        raise _lib.GolfError("ltv_allpole_ss: `status` does not apply to the float64 recursion (double tensors, mode=\"fp64\"): "
+                             "the status words describe the conditioning tiers of the time-chunked fp32 scan")
+    return io
+
+
+def _ss_f64_io(ex, gain, a, zi, mode):
+    """Which kernels serve a call of ltv_allpole_ss: None -- the fp32 ones; 1 -- the float64 recursion on float64 tensors;
+    0 -- the same recursion on fp32 tensors (``mode="fp64"``).  Tensors of different dtypes raise, whatever their device.
+    Under autocast every input is cast to fp32 as ever (float64 ones are left alone by torch.amp and refused as before)."""
+    if torch.is_autocast_enabled():
+        return 0 if mode == "fp64" else None
+    named = [(n, t) for n, t in (("ex", ex), ("gain", gain), ("a", a), ("zi", zi)) if t is not None]
+    if len({t.dtype for _, t in named}) > 1:
+        raise _lib.GolfError("ltv_allpole_ss: " + ", ".join(f"{n} is {t.dtype}" for n, t in named)
+                             + ": one dtype required (all fp32, or all float64 for the float64 recursion)")
+    if ex.dtype == torch.float64:
+        return 1
+    return 0 if mode == "fp64" else None
+
+
 class _LTVAllPoleHead(torch.autograd.Function):
     """xh = ex*up(gain) - c, c the part of the first min(M, T) samples' recursion that reads the initial state ``zi`` (B, M)
     (golf_ltv_allpole_head_{fwd,bwd}_f32): the zero-state filter of xh with gain == 1 IS the filter of ex from zi."""
@@ -288,10 +401,18 @@ def ltv_allpole_ss(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: i
                    zi: torch.Tensor = None, return_zf: bool = False):
     """y[t] = ex[t]*up(gain)[t] - sum_i up(a)[t,i] y[t-1-i]; ex (B,Tx), gain (B,F), a (B,F,M) at hop.
     Output (B, min(Tx,(F-1)*hop+1)).  Differentiable w.r.t. ex, gain, a (custom HIP backward).
+    Float64: with ``ex``, ``gain``, ``a`` (and ``zi``) all float64 the recursion, its adjoint and the gradient sums run in
+    double on the device (csrc/lpc_f64.hip: one wave per utterance, every shape with 1 <= M <= 64) and the result and the
+    gradients are float64 -- what torchlpc.sample_wise_lpc computes for double inputs, and what torch.autograd.gradcheck
+    can be pointed at.  ``prepared``, ``fast_inference`` and any ``mode`` are ignored then; ``status`` raises (its words
+    describe the chunked scan); ``length``, ``zi`` and ``return_zf`` work as in fp32.  Tensors of different dtypes raise.
     ``prepared``: handle from ltv_allpole_prepare(a, hop, T) (ignored if it does not match).
     ``fast_inference``: when no input requires grad, use fp32 transition matrices + one refinement sweep instead of
     fp64 matrices (same accuracy class as a sequential fp32 recursion, ~4x less work in the dominant kernel).
-    ``mode``: None/"auto" picks the algorithm by batch size (time-chunked scan below 2048 utterances, batch-parallel
+    ``mode``: "fp64" runs fp32 tensors through the float64 recursion -- fp32 in and out, every value widened at the load and
+    rounded once at the store: for the utterances at the edge of stability, where no fp32 recursion reaches 1e-4 (rows that
+    ``status`` counts as hot), at the cost of one serial recursion per utterance.  With float64 tensors
+    it is the same as no mode.  Otherwise None/"auto" picks the algorithm by batch size (time-chunked scan below 2048 utterances, batch-parallel
     serial recursion from there on: include/golf_amd.h GOLF_SS_SERIAL); "serial" / "chunked" force one.  "flat-scan"
     forces the chunked algorithm's flat boundary scan.  That is not only a diagnostic: "auto" itself takes the flat scan for
     every lone batch of more than ~40 utterances below the serial threshold (lpc_ss_plan.h ss_two_level; the two-level scan
@@ -313,21 +434,20 @@ def ltv_allpole_ss(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: i
     ``return_zf``: return ``(y, zf)`` with zf (B, M) the final state, zf[b, j] = y[b, T-1-j] (for T < M the initial state
     shifted in behind the T outputs): the ``zi`` of the block that follows.  It stays in the graph, so a chain of blocks is
     differentiable through the state (ltv_allpole_ss_blocks)."""
-    if zi is not None:
-        if zi.dim() != 2 or a.dim() != 3 or tuple(zi.shape) != (a.shape[0], a.shape[2]):
-            raise _lib.GolfError(f"ltv_allpole_ss: zi {tuple(zi.shape)} for a {tuple(a.shape)}: a (B, M) initial state required")
-        if zi.device != ex.device or not zi.is_floating_point() or (zi.dtype != torch.float32 and not torch.is_autocast_enabled()):
-            raise _lib.GolfError(f"ltv_allpole_ss: zi must be an fp32 tensor on {ex.device} (got {zi.dtype} on {zi.device})")
+    io = _ss_route(ex, gain, a, zi, mode, status)
     if ex.dim() == 2 and (ex.shape[0] == 0 or ex.shape[1] == 0):
         # an empty batch / zero samples: what the reference's tensor ops return (an empty result that stays in the graph);
         # the C ABI itself rejects non-positive sizes
-        _lib.require_device(ex, gain, a)
+        _lib.require_device(ex, gain, a, dtype=torch.float64 if io == 1 else torch.float32)
         T = ss_output_length(ex.shape[1], a.shape[1], int(hop)) if ex.shape[1] else 0
         if length is not None:
             T = min(T, max(int(length), 0))
         y = ex[:, :T] * 1.0 + 0.0 * (gain.sum() + a.sum())
         return (y, _final_state(y, zi, a.shape[2])) if return_zf else y
-    if zi is None:
+    if io is not None:
+        # the state enters through the kernel's prologue; zf below is read off y (and zi) like the fp32 path's
+        y = _LTVAllPoleF64.apply(ex, gain, a, zi, int(hop), length, io, False)[0]
+    elif zi is None:
         y = _LTVAllPoleSS.apply(ex, gain, a, int(hop), prepared, bool(fast_inference), SS_MODES[mode], status, length)
     else:
         T = ss_output_length(ex.shape[1], a.shape[1], int(hop))
@@ -359,7 +479,9 @@ def ltv_allpole_ss_blocks(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor,
     Block k filters the samples [k*n*hop, (k+1)*n*hop), n = frames_per_block, with the frames k*n .. (k+1)*n (a block needs
     the frame that ends it for the interpolation); the last block ends with the utterance, sample (F-1)*hop included.
     ``detach_state=True`` cuts the gradient at every block boundary (truncated back-propagation through time): same y.
-    ``zi``: the state in front of the first block.  ``**kw``: fast_inference / mode / status of ltv_allpole_ss."""
+    ``zi``: the state in front of the first block.  ``**kw``: fast_inference / mode / status of ltv_allpole_ss.
+    With float64 tensors, or ``mode="fp64"``, the blocks run the float64 recursion and hand each other its state in double --
+    with fp32 tensors too, where zf alone is rounded: y and zf are then the BITS of the one-shot call, wherever the blocks end."""
     hop, n = int(hop), int(frames_per_block)
     if n < 1:
         raise _lib.GolfError(f"ltv_allpole_ss_blocks: frames_per_block={frames_per_block} must be >= 1")
@@ -372,6 +494,15 @@ def ltv_allpole_ss_blocks(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor,
     if ex.shape[0] == 0 or T == 0:
         return ltv_allpole_ss(ex, gain, a, hop, length=length, zi=zi, return_zf=True, **kw)
     parts, state = [], zi
+    if _ss_route(ex, gain, a, zi, kw.get("mode"), kw.get("status")) == 0:
+        # fp32 tensors through the float64 recursion: zf as ltv_allpole_ss returns it is rounded to fp32, the kernel's own
+        # state is not (float64 tensors need nothing of the kind: their zf IS the state, and they take the loop below)
+        for f0, f1, t0, t1 in ss_block_bounds(T, F, hop, n):
+            y, state = _LTVAllPoleF64.apply(ex[:, t0:t1], gain[:, f0:f1 + 1], a[:, f0:f1 + 1], state, hop, None, 0, True)
+            parts.append(y)
+            if detach_state:
+                state = state.detach()
+        return (parts[0] if len(parts) == 1 else torch.cat(parts, 1)), state.to(parts[0].dtype)
     for f0, f1, t0, t1 in ss_block_bounds(T, F, hop, n):
         y, state = ltv_allpole_ss(ex[:, t0:t1], gain[:, f0:f1 + 1], a[:, f0:f1 + 1], hop, zi=state, return_zf=True, **kw)
         parts.append(y)

@@ -72,7 +72,8 @@ class SourceFilterSynth(Synth):
     def _source_and_end_filter(self, phase, osc_params, filt_params, nz) -> Optional[AudioTensor]:
         """``end_filter(harm_oscillator(phase, w, add=nz), gain, a)`` through functional.source_filter_ss where that is the same
         computation: the indexed glottal oscillator on its fused path (oversampled, no phase offset), the sample-wise end filter
-        (not its frame-wise subclass) with nothing prefetched and no health monitor, inference, no batches in flight.  None:
+        (not its frame-wise subclass) in fp32 ``precision`` with nothing prefetched and no health monitor, inference, no batches in
+        flight.  None:
         the caller composes the modules as ever."""
         from . import functional as GF
         from .filters import LTVMinimumPhaseFilterPrecise
@@ -82,6 +83,7 @@ class SourceFilterSynth(Synth):
         if not (FUSE_SOURCE_MAPS and not GF.THROUGHPUT_MODE and type(filt) is LTVMinimumPhaseFilterPrecise
                 and isinstance(osc, IndexedGlottalFlowTable) and osc.oversampling > 1 and len(osc_params) == 1
                 and len(filt_params) == 2 and getattr(filt, "_prepared", None) is None and not filt.health_check
+                and filt.precision == "fp32"
                 and not osc.check_ranges and phase.ndim == 2 and nz.hop_length == 1):
             return None
         w, (gain, a) = osc_params[0], filt_params

@@ -222,6 +222,43 @@ int golf_ltv_allpole_bwd_f32(const float* gy, int64_t gy_stride, const float* y,
                              int B, int T, int F, int M, int hop,
                              void* ws, size_t ws_bytes, int flags, void* stream);
 
+/* a-1 in FLOAT64 (additive in ABI 6; csrc/lpc_f64.hip).  The same filter, the same up() interpolation and the same
+ * T <= (F-1)*hop+1 rule as golf_ltv_allpole_fwd_f32 / _bwd_f32 -- models/filters.py:99-113, where torchlpc.sample_wise_lpc
+ * (models/filters.py:112) is dtype-generic and is run, gradcheck'ed and rendered in double -- with everything on the recursion's
+ * dependent chain in double: accumulators, interpolated coefficients, up(gain), the fed-back output.  For the utterances at the
+ * edge of stability on which no fp32 recursion reaches 1e-4 (the status words above), for parity checks and for ground truth.
+ *   io = 1  ex, gain, a, gy, y, g_ex, g_gain, g_a are DOUBLE buffers
+ *   io = 0  they are fp32 buffers: widened at the load (exact), rounded once at the store; the arithmetic is the same
+ *   state, zi, g_zi (B, M) and the workspace are doubles for either io (a chain of fp32 blocks continues from the unrounded
+ *   outputs, and so stays on the bits of the one-shot call).
+ * One wave per utterance, one lane per tap (the wave-per-utterance design of csrc/lpc_any.hip, for every shape: any
+ * 1 <= M <= 64, hop >= 1, F >= 1, on or off the ring grid); the cost is that of one serial recursion per utterance.  Strides are
+ * in elements of the io type, rows 64-bit addressed.  GOLF_EINVAL: a null required pointer, a non-positive size, T beyond
+ * (F-1)*hop+1, a row stride below its width, io outside {0, 1}, a workspace that is missing, misaligned or too small;
+ * GOLF_EUNSUPPORTED: M > 64 (or B*F >= 2^31 in the backward). */
+/* The workspace of the backward below (autograd through models/filters.py:99-113): g (B, T) doubles, 256-byte aligned size;
+ * 0 for a non-positive size.  The forward needs none. */
+size_t golf_ltv_allpole_f64_workspace_bytes(int B, int T);
+/* Forward, models/filters.py:99-113.  state == NULL: y[<0] = 0.  Else state (B, M) doubles, in and out, as in
+ * golf_ltv_allpole_fwd_state_f32: y[b][-1-i] = state[b][i] on entry (replayed through the update by a prologue, so the
+ * accumulators are rebuilt with the one-shot's operation sequence), state[b][i] = y[b][T-1-i] on return (for T < M the old
+ * state shifted in behind them).  A sample's bits depend neither on where a block starts nor on the 64-sample I/O blocks:
+ * blocks that start on frame boundaries, chained through `state` from zeros, give the bits of the one-shot call. */
+int golf_ltv_allpole_fwd_f64(const void* ex, int64_t ex_stride, const void* gain, const void* a, void* y, int64_t y_stride,
+                             int B, int T, int F, int M, int hop, double* state, int io, void* stream);
+/* Backward of the above (models/filters.py:99-113 under autograd; the closed form of golf_ltv_allpole_bwd_f32), y the
+ * forward's output and zi (nullable) the state it started from:
+ *     g[t]      = gy[t] - sum_i A[t+1+i,i]*g[t+1+i]          into ws, (B, T) doubles
+ *     g_ex[t]   = g[t]*G[t] (t < T), 0 (T <= t < g_ex_width)  (B, g_ex_width) stride g_ex_stride, fully written
+ *     g_gain[f] = up^T(g*ex)[f]      g_a[f,i] = up^T(-g[t]*y[t-1-i])[f,i],  y[-1-j] = zi[j]
+ *     g_zi[j]   = -sum_{t < min(T, M-j)} A[t,t+j]*g[t]       (the cotangent of a final state is the caller's to add)
+ * Each of g_ex, g_gain, g_a, g_zi may be NULL: that gradient is not stored.  Two launches (the reverse recursion, one wave per
+ * utterance; then one workgroup per (utterance, frame)), fixed summation order, no atomics: bit-reproducible. */
+int golf_ltv_allpole_bwd_f64(const void* gy, int64_t gy_stride, const void* y, int64_t y_stride, const void* ex,
+                             int64_t ex_stride, const void* gain, const void* a, const double* zi, void* g_ex,
+                             int64_t g_ex_stride, int64_t g_ex_width, void* g_gain, void* g_a, double* g_zi, int B, int T,
+                             int F, int M, int hop, void* ws, size_t ws_bytes, int io, void* stream);
+
 /* a-5: inverse (analysis) filter e[t] = y[t] + sum_i A[t,i]*y[t-1-i].
  * Replaces LTVMinimumPhaseFilter.reverse -> fir_filt, models/filters.py:186-195, utils.py:433-441. */
 int golf_ltv_inverse_f32(const float* y, int64_t y_stride, const float* a, float* e, int64_t e_stride,
