@@ -993,7 +993,17 @@ extern "C" int golf_lti_frames_ola_bwd_f32(const float* gy, int64_t gy_stride, c
 //            accumulates d/d(a0,a1,a2) of its section = -sum_n u_{k-1}[n] * y_k[n - i];
 //   lane 0's output u_0 is the gradient w.r.t. the scaled input frame: stored (times the frame gain in gain mode 1) for the
 //   overlap-add kernel below; gain mode 1 also reduces g_gain[b,f] = sum_n u_0[n] x[n] here.
+// Both recursions carry their state, and hand it from lane to lane, in float64 (LDS rows stay fp32, rounded once at the
+// store): K sections with poles at the edge of stability amplify the rounding of an fp32 state by 1e3 and more, and the
+// gradients are sums over a whole frame of products of two such signals.  In fp32 the gain gradient of one frame with
+// sixteen sections at radius 0.99 came out 2.7 % off; the float64 state leaves what the fp32 rows lose, about 1e-7.
 #define DPP_ROW_SHL1 0x101
+template <int CTRL>
+__device__ __forceinline__ double bq_dpp_f64(double v) {   // the row shift of a double: its two halves, lane 0 / 15 reads 0
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
 __global__ __launch_bounds__(64) void ff_biquad_bwd_kernel(const float* __restrict__ gq, int64_t gq_stride,
                                                            const float* __restrict__ ex, int64_t ex_stride,
                                                            const float* __restrict__ gain, const float* __restrict__ bq,
@@ -1027,56 +1037,54 @@ __global__ __launch_bounds__(64) void ff_biquad_bwd_kernel(const float* __restri
         const int to = tb + n;              // output sample index of frame position n: f*hop - pad + n
         U[n] = (to >= 0 && to < Ty) ? window[n] * gq[(size_t)b * gq_stride + to] : 0.f;
     }
-    float a1 = 0.f, a2 = 0.f, ia0 = 1.f;
+    double a1 = 0., a2 = 0., ia0 = 1.;
     if (k < K) {
         const float* c = bq + (((size_t)b * F + f) * K + k) * 3;
-        ia0 = 1.0f / c[0];
-        a1 = c[1] * ia0;
-        a2 = c[2] * ia0;
+        ia0 = 1.0 / (double)c[0];
+        a1 = (double)c[1] * ia0;
+        a2 = (double)c[2] * ia0;
     }
     wave_lds_fence();
     // ---- phase 1: forward cascade, lane k = section k filters sample m - k at step m
     {
-        float s1 = 0.f, s2 = 0.f, outp = 0.f;
+        double s1 = 0., s2 = 0., outp = 0.;
         for (int m = 0; m < Wl + K - 1; ++m) {
-            const float sh = __builtin_bit_cast(
-                float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, outp), DPP_ROW_SHR1, 0xF, 0xF, true));
+            const double sh = bq_dpp_f64<DPP_ROW_SHR1>(outp);
             const int n = m - k;
             const bool on = k < K && n >= 0 && n < Wl;
-            const float in = k == 0 ? Y[2 + (on ? n : 0)] : sh;
-            const float y = on ? fmaf(ia0, in, fmaf(-a1, s1, -a2 * s2)) : 0.f;
-            if (on) { s2 = s1; s1 = y; Y[(size_t)(k + 1) * WS + 2 + n] = y; }
+            const double in = k == 0 ? (double)Y[2 + (on ? n : 0)] : sh;
+            const double y = on ? fma(ia0, in, fma(-a1, s1, -a2 * s2)) : 0.;
+            if (on) { s2 = s1; s1 = y; Y[(size_t)(k + 1) * WS + 2 + n] = (float)y; }
             outp = y;
         }
     }
     wave_lds_fence();
     // ---- phase 2: adjoint cascade in reverse time, lane k = section k handles sample Wl-1 - (m - (K-1-k)) at step m
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    double g0 = 0., g1 = 0., g2 = 0.;
     {
-        float s1 = 0.f, s2 = 0.f, outp = 0.f;
+        double s1 = 0., s2 = 0., outp = 0.;
         const float* yk = Y + (size_t)(k < K ? k + 1 : 0) * WS + 2;   // this section's OUTPUT
         for (int m = 0; m < Wl + K - 1; ++m) {
-            const float sh = __builtin_bit_cast(
-                float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, outp), DPP_ROW_SHL1, 0xF, 0xF, true));
+            const double sh = bq_dpp_f64<DPP_ROW_SHL1>(outp);
             const int n = Wl - 1 - (m - (K - 1 - k));
             const bool on = k < K && n >= 0 && n < Wl;
-            const float in = k == K - 1 ? U[on ? n : 0] : sh;
-            const float u = on ? fmaf(ia0, in, fmaf(-a1, s1, -a2 * s2)) : 0.f;   // (a1, a2 already divided by a0)
+            const double in = k == K - 1 ? (double)U[on ? n : 0] : sh;
+            const double u = on ? fma(ia0, in, fma(-a1, s1, -a2 * s2)) : 0.;   // (a1, a2 already divided by a0)
             if (on) {
                 s2 = s1; s1 = u;
-                g0 = fmaf(-u, yk[n], g0);
-                g1 = fmaf(-u, yk[n - 1], g1);
-                g2 = fmaf(-u, yk[n - 2], g2);
+                g0 = fma(-u, (double)yk[n], g0);
+                g1 = fma(-u, (double)yk[n - 1], g1);
+                g2 = fma(-u, (double)yk[n - 2], g2);
             }
             outp = u;
             // lane 0's outputs replace U behind the read front of lane K-1 (it is K-1 samples ahead): no hazard, U[n] of
             // lane K-1 at this step has index n - (K-1) < n of lane 0
-            if (on && k == 0) U[n] = u;
+            if (on && k == 0) U[n] = (float)u;
         }
     }
     if (k < K) {
         float* o = g_bq + (((size_t)b * F + f) * K + k) * 3;
-        o[0] = g0; o[1] = g1; o[2] = g2;
+        o[0] = (float)g0; o[1] = (float)g1; o[2] = (float)g2;
     }
     wave_lds_fence();
     // ---- u_0 -> frame gradient store; gain mode 1: g_gain[b,f] = sum_n u_0[n] * x[n]

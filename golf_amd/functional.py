@@ -1917,11 +1917,15 @@ def upsample_adjoint(v: torch.Tensor, hop: int, F: int) -> torch.Tensor:
     if hop == 1 or F == 1:
         out[:, :T] = v
         return out
-    n = torch.arange(T, device=v.device)
-    f = torch.clamp(torch.div(n, hop, rounding_mode="floor"), max=F - 2)
-    w = (n - f * hop).to(v.dtype) / hop
-    out.index_add_(1, f, v * (1 - w))
-    out.index_add_(1, f + 1, v * w)
+    # sample f*hop + r gives (1 - r/hop) of itself to frame f and r/hop to frame f+1; the last one, (F-1)*hop, is frame F-1's
+    # alone.  Plain reductions over r: index_add_ sums with atomics, in an order (and to a last bit) that varies between calls
+    L = (F - 1) * hop
+    vp = torch.nn.functional.pad(v, (0, L + 1 - T))
+    seg = vp[:, :L].reshape(B, F - 1, hop)
+    w = torch.arange(hop, device=v.device, dtype=v.dtype) / hop
+    out[:, :F - 1] = (seg * (1 - w)).sum(-1)
+    out[:, 1:] += (seg * w).sum(-1)
+    out[:, F - 1] += vp[:, L]
     return out
 
 
