@@ -569,6 +569,19 @@ static inline int zp_pad(int n_mag) { return (int)align_up((size_t)n_mag, ZG_COL
 
 using namespace golf;
 
+// Dynamic LDS of the packed-FIR kernels: one staging region of fir_region(256 + taps + 4) floats per wave.  A workgroup may ask
+// for 64 KiB (the bound launch_decimate uses too); a longer filter is refused on the host, before any launch.
+constexpr size_t FIR_LDS_MAX = 64 * 1024;
+constexpr int FIR_SPAN_MAX = (int)(FIR_LDS_MAX / (FIR_WAVES * sizeof(float))) / (64 * FIR_STAGE_U) * (64 * FIR_STAGE_U);
+constexpr int FIR_TAPS_MAX = (FIR_SPAN_MAX - 256 - 4) & ~3;   // 3836: the largest (4-aligned) tap count of the core
+static int fir_lds_check(const char* who, const char* what, int n) {
+    const size_t bytes = (size_t)FIR_WAVES * fir_region(256 + ((n + 3) & ~3) + 4) * sizeof(float);
+    if (bytes > FIR_LDS_MAX)
+        return fail(GOLF_EUNSUPPORTED, "%s: %s=%d needs %zu bytes of LDS (limit %zu): the largest accepted %s is %d", who, what,
+                    n, bytes, FIR_LDS_MAX, what, FIR_TAPS_MAX);
+    return GOLF_OK;
+}
+
 // pad = total zero padding of the excitation: 2P (zero-phase, P each side) or N-1 (causal, all in front)
 static int fir_geometry(const char* who, int B, int T, int F, int N, int hop, int KS, int frame0, int* nfr_out,
                         bool causal = false) {
@@ -590,6 +603,7 @@ static int fir_frames_fwd(const char* who, const float* ex, int64_t ex_stride, c
     if (!ex || !kern || !y) return fail(GOLF_EINVAL, "%s: null pointer", who);
     int nfr = 0;
     if (int rc = fir_geometry(who, B, T, F, N, hop, kern_row_stride, frame0, &nfr, CAUSAL)) return rc;
+    if (int rc = fir_lds_check(who, "N", N)) return rc;
     const int npass = (hop + FIR_TILE - 1) / FIR_TILE;
     const int RS = fir_region(256 + ((N + 3) & ~3) + 4);
     const long long units = (long long)B * nfr * npass;
@@ -610,6 +624,7 @@ static int fir_frames_bwd(const char* who, const float* gy, int64_t gy_stride, c
     if (hop % 4 != 0)
         return fail(GOLF_EUNSUPPORTED, "%s: hop=%d must be a multiple of 4 (the frame's gradient "
                     "samples are the packed taps of the backward kernels)", who, hop);
+    if (int rc = fir_lds_check(who, "hop", hop)) return rc;
     const int RS = fir_region(256 + hop + 4);
     hipStream_t st = (hipStream_t)stream;
     if (g_kern) {
@@ -738,6 +753,7 @@ int golf_lti_fir_f32(const float* ex, int64_t ex_stride, const float* taps, int 
     const bool rev = ntaps < 0;   // ABI 5: a negative tap count applies the |ntaps| taps in reverse order (the adjoint, no flipped copy)
     if (rev) ntaps = -ntaps;
     if (int rc = lti_check("lti_fir", B, T, ntaps, lead)) return rc;
+    if (int rc = fir_lds_check("lti_fir", "ntaps", ntaps)) return rc;
     const int ntile = (T + FIR_TILE - 1) / FIR_TILE;
     const int RS = fir_region(256 + ntaps + 4);
     const long long units = (long long)B * ntile;

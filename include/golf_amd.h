@@ -623,11 +623,13 @@ int golf_ltv_fir_frames_length(int T, int F, int N, int hop);
 /* ex (B, >=T) stride ex_stride; kern (B*F, kern_row_stride), zero in [N, ceil4(N)); y (B, nfr*hop) stride y_stride.
  * frame0 (normally 0): output frame f is filtered with kernel row f + frame0, nfr = min(frames in T, F - frame0) —
  * what the sample-wise variant (LTVZeroPhaseFIRFilterPrecise, models/filters.py:286-337: kernels interpolated between
- * frames f and f+1) needs for its second term. */
+ * frames f and f+1) needs for its second term.  N <= 3836: a wave stages 256 + ceil4(N) + 4 floats and the four waves of
+ * a workgroup share 64 KiB of dynamic LDS; a longer kernel is GOLF_EUNSUPPORTED (checked on the host, nothing is launched). */
 int golf_ltv_fir_frames_fwd_f32(const float* ex, int64_t ex_stride, const float* kern, int kern_row_stride, float* y,
                                 int64_t y_stride, int B, int T, int F, int N, int hop, int frame0, void* stream);
 /* gy (B, nfr*hop).  g_ex (B,T) and g_kern (B*F, kern_row_stride; rows of unused frames and the padding taps [N, kern_row_stride) zeroed) are fully
- * overwritten; either may be NULL to skip it.  Requires hop % 4 == 0. */
+ * overwritten; either may be NULL to skip it.  Requires hop % 4 == 0 and, by the same 64 KiB of LDS (the frame's hop gradient
+ * samples are the packed taps here), hop <= 3836: GOLF_EUNSUPPORTED otherwise. */
 int golf_ltv_fir_frames_bwd_f32(const float* gy, int64_t gy_stride, const float* ex, int64_t ex_stride,
                                 const float* kern, int kern_row_stride, float* g_ex, int64_t g_ex_stride,
                                 float* g_kern, int B, int T, int F, int N, int hop, int frame0, void* stream);
@@ -674,7 +676,8 @@ int golf_ltv_fir_frames_causal_bwd_f32(const float* gy, int64_t gy_stride, const
  * Replaces LTIAcousticFilter.forward, models/filters.py:426-449 (pad + F.conv1d with one learnable kernel):
  *     y[b,t] = sum_{n<ntaps} taps[n] * ex[b, t - lead + n],   ex = 0 outside [0,T)
  *   (the reference's y = ex + conv(pad(ex[:, :-1], (K,0)), kernel) is taps = [kernel, 1], lead = K).
- *   ntaps must be a multiple of 4 (pad with zero taps), 0 <= lead < ntaps.
+ *   ntaps must be a multiple of 4 (pad with zero taps), 0 <= lead < ntaps, |ntaps| <= 3836 (64 KiB of dynamic LDS per
+ *   workgroup; more is GOLF_EUNSUPPORTED, checked on the host before any launch; the taps gradient has no such limit).
  *   The adjoint w.r.t. ex is the same call with the taps reversed and lead' = ntaps-1-lead; ABI 5: ntaps < 0 applies the
  *   |ntaps| taps in reverse order, so the adjoint needs no flipped copy of them.
  * golf_lti_fir_taps_grad_f32: g_taps[n] = sum_{b,t} gy[b,t] * ex[b, t - lead + n]  (deterministic two-stage sum).
