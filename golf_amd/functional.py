@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "lti_frames_ola",
+__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "lti_frames_ola",
            "glottal_osc",
            "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
@@ -705,6 +705,90 @@ def lpc_analysis(x: torch.Tensor, window: torch.Tensor, hop: int, order: int, ce
         return out if return_rc else out[:2]
     return _LPCAnalysis.apply(x, window, hop, M, -(W // 2) if centred else 0, F, float(eps_rel), float(eps_abs),
                               bool(return_rc))
+
+
+# ------------------------------------------------------------------------------------------------
+# f0 analysis: audio -> (f0, period, aperiodicity) per frame by YIN (include/golf_amd.h, csrc/f0_yin.hip)
+# ------------------------------------------------------------------------------------------------
+F0_MAX_FRAME = 16384   # W + tau_max samples of one frame (csrc/f0_yin.hip YIN_MAX_S)
+
+
+def f0_frames(T: int, S: int, hop: int, centred: bool = True) -> int:
+    """Frames of the f0 analysis for frames of ``S = W + tau_max`` samples: ``T // hop + 1`` centred (the filters' frame
+    grid), ``max(T - S, 0) // hop + 1`` for frames that start at sample 0."""
+    return lpc_analysis_frames(T, S, hop, centred)
+
+
+def f0_lags(sample_rate: float, f0_min: float = 60.0, f0_max: float = 1000.0, window_length: int = None):
+    """``(tau_min, tau_max, W)`` of the f0 analysis: ``floor(sr / f0_max)``, ``ceil(sr / f0_min)`` and the integration window,
+    two of the longest periods unless ``window_length`` is given."""
+    if not (sample_rate > 0 and 0 < f0_min < f0_max):
+        raise _lib.GolfError(f"f0_yin: need sample_rate > 0 and 0 < f0_min < f0_max (got {sample_rate}, {f0_min}, {f0_max})")
+    tau_min, tau_max = int(math.floor(sample_rate / f0_max)), int(math.ceil(sample_rate / f0_min))
+    return tau_min, tau_max, 2 * tau_max if window_length is None else int(window_length)
+
+
+class _F0Yin(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, sample_rate, hop, W, tau_min, tau_max, origin, F, threshold, rms_floor, want_all):
+        _lib.require_device(x)
+        lib = _lib.load()
+        x = _rows(x)
+        B, T = x.shape
+        f0 = torch.empty(B, F, dtype=torch.float32, device=x.device)
+        period = torch.empty_like(f0) if want_all else None   # not asked for: not written
+        ap = torch.empty_like(f0) if want_all else None
+        rcode = lib.golf_f0_yin_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), _lib.ptr(period), _lib.ptr(ap), B, T, F, hop, W,
+                                    tau_min, tau_max, origin, sample_rate, threshold, rms_floor, _lib.stream_ptr())
+        _lib.check(rcode, "golf_f0_yin_f32")
+        out = (f0, period, ap) if want_all else (f0,)
+        ctx.mark_non_differentiable(*out)   # a search over lags: no gradient reaches the waveform
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return (None,) * 11
+
+
+def f0_yin(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, f0_max: float = 1000.0,
+           window_length: int = None, threshold: float = 0.15, rms_floor: float = 0.0, centred: bool = True,
+           n_frames: int = None, return_all: bool = False):
+    """f0 by YIN (de Cheveigne & Kawahara 2002, steps 1-5; the definition is in include/golf_amd.h): x (B, T) -> ``f0 (B, F)``
+    in Hz with 0 for unvoiced frames, or with ``return_all`` ``(f0, period, ap)``: the refined period in samples (finite in
+    every frame) and the aperiodicity d'(period), small for a periodic frame and about 1 for noise.  Lags run from
+    ``floor(sample_rate / f0_max)`` to ``tau_max = ceil(sample_rate / f0_min)`` and the difference function integrates over
+    ``window_length`` samples (default ``2 * tau_max``), so frame f reads ``S = window_length + tau_max`` samples from
+    ``f * hop - S // 2`` (``centred``, F = T // hop + 1: the frame grid of the filters and of ``lpc_analysis``) or from
+    ``f * hop`` (F = max(T - S, 0) // hop + 1); x is zero outside [0, T) and ``n_frames`` overrides F.  A frame is voiced
+    if a lag falls below ``threshold`` and its RMS over the window exceeds ``rms_floor``.  The outputs never require grad;
+    a waveform that does is accepted.  S <= 16384."""
+    if x.dim() != 2:
+        raise _lib.GolfError(f"f0_yin: x must be (B, T) (got {tuple(x.shape)})")
+    hop = int(hop)
+    if hop < 1:
+        raise _lib.GolfError(f"f0_yin: hop={hop} must be >= 1")
+    tau_min, tau_max, W = f0_lags(float(sample_rate), float(f0_min), float(f0_max), window_length)
+    if tau_min < 1 or tau_max <= tau_min:
+        raise _lib.GolfError(f"f0_yin: lags {tau_min}..{tau_max} (need 1 <= tau_min < tau_max: f0_max <= sample_rate, "
+                             "f0_min < f0_max)")
+    if W < 1:
+        raise _lib.GolfError(f"f0_yin: window_length={W} must be >= 1")
+    S = W + tau_max
+    if S > F0_MAX_FRAME:
+        raise _lib.GolfError(f"f0_yin: frame window_length + tau_max = {S} samples exceeds {F0_MAX_FRAME}")
+    F = f0_frames(x.shape[1], S, hop, centred) if n_frames is None else int(n_frames)
+    if F < 1:
+        raise _lib.GolfError(f"f0_yin: n_frames={F} must be >= 1")
+    if x.shape[0] * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
+        raise _lib.GolfError(f"f0_yin: B*F = {x.shape[0] * F} frames, must be < 2^31")
+    if x.shape[0] == 0:
+        _lib.require_device(x.float())
+        z = torch.empty(0, F, dtype=torch.float32, device=x.device)
+        return (z, z.clone(), z.clone()) if return_all else z
+    out = _F0Yin.apply(x, float(sample_rate), hop, W, tau_min, tau_max, -(S // 2) if centred else 0, F, float(threshold),
+                       float(rms_floor), bool(return_all))
+    return out if return_all else out[0]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -300,6 +300,37 @@ int golf_lpc_analysis_bwd_f32(const float* g_gain, const float* g_a, const float
                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * f0 analysis (additive in ABI 6): audio -> (f0, period, aperiodicity) per frame by YIN (de Cheveigne & Kawahara, JASA
+ * 2002, steps 1-5) -- the f0 track that every decoder takes as an input, on the frame grid of the LPC analysis above.  The
+ * reference gets f0 from a third-party CPU package (pyworld.dio, models/utils.py:596-602); this is not that estimator and
+ * its tracks differ from the reference's f0 files.  The float64 restatement in tests/f0_ref.py is the checker.
+ * Inputs: x (B, T) fp32 with unit inner stride and row stride x_stride; sample_rate; hop; W (integration window); tau_min,
+ * tau_max (lag range in samples); threshold; rms_floor; origin; F.  Frame f of row b, with S = W + tau_max:
+ *     s[k] = x[b, origin + f*hop + k]  for k in [0, S),  x = 0 outside [0, T);
+ *  1. difference function   d[tau] = sum_{j<W} (s[j] - s[j+tau])^2                       tau = 0..tau_max
+ *  2. cumulative-mean normalisation   d'[0] = 1,  d'[tau] = d[tau] tau / sum_{k=1..tau} d[k],  and d'[tau] = 1 where that
+ *     running sum is 0 (a silent frame)
+ *  3. search over [tau_min, tau_max]: the smallest tau with d'[tau] < threshold, then forward while tau+1 <= tau_max and
+ *     d'[tau+1] < d'[tau]: that is tau* and found = true.  If no lag is below the threshold: tau* = argmin d' over the
+ *     range, the smallest tau on ties, and found = false.
+ *  4. parabolic refinement on d': with (a, b, c) = d'[tau*-1], d'[tau*], d'[tau*+1]: if tau*-1 >= 1, tau*+1 <= tau_max and
+ *     a - 2b + c > 0 then delta = clamp((a - c) / (2 (a - 2b + c)), -1, 1), else delta = 0;
+ *     period = tau* + delta;  ap = b - (a - c) delta / 4  (ap = b when delta = 0)
+ *  5. voiced = found and mean_{j<W} s[j]^2 > rms_floor^2;  f0 = sample_rate / period if voiced, else 0 (the reference's
+ *     convention: f0 == 0 is unvoiced, ltng/ae.py:98-101).
+ * Outputs f0, period, ap, each (B, F) fp32 and each may be NULL (not written) as long as one is given; written in full by
+ * one launch, no atomics, every sum in a fixed order: bit-reproducible, and a row's result does not depend on the batch it
+ * sits in.  d is summed in fp32 (four partial sums per lag), the running sum of step 2 and steps 4-5 in fp64 from the fp32
+ * d'.  Every loop is bounded by tau_max whatever the data.  No call allocates or synchronises; graph-capturable.
+ * Refused before any launch: x NULL with T > 0, all three outputs NULL, B < 1, T < 0, F < 1, x_stride < T, sample_rate <= 0
+ * (GOLF_EINVAL); hop < 1, tau_min < 1, tau_max <= tau_min, W < 1, S = W + tau_max > 16384 samples (a frame, its d' and the
+ * partial sums must fit the 160 KiB of LDS: at most 132 KiB at S = 16384), B*F >= 2^31 (GOLF_EUNSUPPORTED).
+ * ------------------------------------------------------------------------------------------- */
+int golf_f0_yin_f32(const float* x, int64_t x_stride, float* f0, float* period, float* ap, int B, int T, int F, int hop,
+                    int W, int tau_min, int tau_max, int64_t origin, double sample_rate, double threshold, double rms_floor,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a-4: frame-wise LTI all-pole + windowed overlap-add — GOLF-ff end filter.
  * Replaces LTVMinimumPhaseFilter.forward, models/filters.py:131-184 (pad, unfold, lpc_synthesis ->
  * torchaudio.functional.lfilter models/lpc.py:11-16, diagonal conv_transpose1d OLA, normalise).
