@@ -19,6 +19,13 @@
 //      descent stops), the fallback argmin as a wave reduction on (value, index) that keeps the smaller index on ties.
 //      Every loop runs at most tau_max / 64 + 1 times whatever the data, NaN included.
 //   6. Lane 0 refines in fp64 from the fp32 d' and stores.  The frame's energy (voicing) is an fp64 sum in a fixed order.
+//
+// golf_f0_candidates_f32 (the front end of the path search in f0_viterbi.hip) is the same launch with another search: steps
+// 1-4 are one device function, yin_dprime, that both kernels inline, and step 6 is one function, yin_refine.  Its wave 0
+// picks the K <= 7 local minima of d' with the smallest values in K rounds: a round scans [tau_min, tau_max] 64 lags at a
+// time for the smallest (value, lag) pair above the pair of the round before and ends in a wave reduction that keeps the
+// smaller lag on ties, so a round is tau_max / 64 + 1 steps whatever the data and a NaN is never picked.  Lane k < n then
+// refines pick k and stores it at its rank among the picks' lags (ascending lag); lanes n .. K-1 store the absent slots.
 #include "common.h"
 #include "device_common.h"
 
@@ -51,23 +58,24 @@ __device__ __forceinline__ double yin_wave_sum(double v) {
     return v;
 }
 
-__global__ __launch_bounds__(YIN_THREADS) void f0_yin_kernel(const float* __restrict__ x, int64_t x_stride,
-                                                             float* __restrict__ f0_out, float* __restrict__ period_out,
-                                                             float* __restrict__ ap_out, int G, int T, int F, int hop, int W,
-                                                             int tau_min, int tau_max, int64_t origin, int s_len,
-                                                             double sample_rate, double threshold, double floor2) {
-    extern __shared__ __attribute__((aligned(16))) double yin_lds[];
+// Steps 1-4 for the frame of this workgroup: on return d' [0, tau_max] is in LDS at *d_out (fp32) and the four partial
+// energies of the window at *en_out, both visible to wave 0.  Returns the frame's index for wave 0 and -1 for the waves
+// that are done (waves 1-3, and every wave of a workgroup behind the last frame).
+__device__ __forceinline__ int yin_dprime(double* yin_lds, const float* __restrict__ x, int64_t x_stride, int G, int T, int F,
+                                          int hop, int W, int tau_max, int64_t origin, int s_len, float** d_out,
+                                          double** en_out) {
     double* en = yin_lds;                               // YIN_WAVES partial energies
     float* s = (float*)(yin_lds + YIN_WAVES);           // s_len floats, 16-byte aligned
     float* part = s + s_len;                            // YIN_WAVES rows of YIN_TILE partial sums
     float* d = part + YIN_WAVES * YIN_TILE;             // tau_max + 1: d, then d' in place
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar loop bounds
     const int64_t g64 = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;   // 2-D grid: 256 G threads may pass 2^32 in one dimension
-    if (g64 >= G) return;
+    if (g64 >= G) return -1;
     const int g = (int)g64, b = g / F, f = g - b * F;
     const int S = W + tau_max;
     const int64_t o = origin + (int64_t)f * hop;
     const float* xr = x + (int64_t)b * x_stride;
+    *d_out = d, *en_out = en;
 
     double e = 0.0;
     for (int k0 = tid; k0 < s_len; k0 += YIN_STAGE * YIN_THREADS) {   // YIN_STAGE loads in flight, then their stores
@@ -146,7 +154,7 @@ __global__ __launch_bounds__(YIN_THREADS) void f0_yin_kernel(const float* __rest
         }
         __syncthreads();   // the next tile's partial sums; after the last tile, d for wave 0
     }
-    if (w != 0) return;
+    if (w != 0) return -1;
 
     // d -> d' in place, 64 lags at a time
     double carry = 0.0;
@@ -164,6 +172,43 @@ __global__ __launch_bounds__(YIN_THREADS) void f0_yin_kernel(const float* __rest
         if (tau <= tau_max) d[tau] = (tau >= 1 && run != 0.0) ? (float)(dv * (double)tau / run) : 1.f;
     }
     wave_lds_fence();
+    return g;
+}
+
+// Step 6 at the integer lag star, in fp64 from the fp32 d'.
+__device__ __forceinline__ void yin_refine(const float* d, int star, int tau_max, double& period, double& apv) {
+    const double bq = (double)d[star];
+    double delta = 0.0;
+    apv = bq;
+    if (star - 1 >= 1 && star + 1 <= tau_max) {
+        const double aq = (double)d[star - 1], cq = (double)d[star + 1];
+        const double den = aq - 2.0 * bq + cq;
+        if (den > 0.0) {
+            delta = fmin(fmax((aq - cq) / (2.0 * den), -1.0), 1.0);
+            if (delta != 0.0) apv = bq - (aq - cq) * delta * 0.25;
+        }
+    }
+    period = (double)star + delta;
+}
+
+__device__ __forceinline__ double yin_energy(const double* en) {
+    double energy = en[0];
+#pragma unroll
+    for (int ww = 1; ww < YIN_WAVES; ++ww) energy += en[ww];
+    return energy;
+}
+
+__global__ __launch_bounds__(YIN_THREADS) void f0_yin_kernel(const float* __restrict__ x, int64_t x_stride,
+                                                             float* __restrict__ f0_out, float* __restrict__ period_out,
+                                                             float* __restrict__ ap_out, int G, int T, int F, int hop, int W,
+                                                             int tau_min, int tau_max, int64_t origin, int s_len,
+                                                             double sample_rate, double threshold, double floor2) {
+    extern __shared__ __attribute__((aligned(16))) double yin_lds[];
+    float* d;
+    double* en;
+    const int g = yin_dprime(yin_lds, x, x_stride, G, T, F, hop, W, tau_max, origin, s_len, &d, &en);
+    if (g < 0) return;
+    const int lane = threadIdx.x & 63;
 
     // first lag below the threshold, then down to where the descent stops
     int star = -1;
@@ -203,20 +248,9 @@ __global__ __launch_bounds__(YIN_THREADS) void f0_yin_kernel(const float* __rest
     }
 
     if (lane == 0) {
-        const double bq = (double)d[star];
-        double delta = 0.0, apv = bq;
-        if (star - 1 >= 1 && star + 1 <= tau_max) {
-            const double aq = (double)d[star - 1], cq = (double)d[star + 1];
-            const double den = aq - 2.0 * bq + cq;
-            if (den > 0.0) {
-                delta = fmin(fmax((aq - cq) / (2.0 * den), -1.0), 1.0);
-                if (delta != 0.0) apv = bq - (aq - cq) * delta * 0.25;
-            }
-        }
-        const double period = (double)star + delta;
-        double energy = en[0];
-#pragma unroll
-        for (int ww = 1; ww < YIN_WAVES; ++ww) energy += en[ww];
+        double period, apv;
+        yin_refine(d, star, tau_max, period, apv);
+        const double energy = yin_energy(en);
         const bool voiced = found && energy / (double)W > floor2;
         if (f0_out) f0_out[g] = voiced ? (float)(sample_rate / period) : 0.f;
         if (period_out) period_out[g] = (float)period;
@@ -224,9 +258,90 @@ __global__ __launch_bounds__(YIN_THREADS) void f0_yin_kernel(const float* __rest
     }
 }
 
+constexpr int YIN_MAX_K = 7;                 // candidates per frame
+
+__global__ __launch_bounds__(YIN_THREADS) void f0_candidates_kernel(const float* __restrict__ x, int64_t x_stride,
+                                                                    float* __restrict__ period_out,
+                                                                    float* __restrict__ ap_out, int G, int T, int F, int hop,
+                                                                    int W, int tau_min, int tau_max, int K, int64_t origin,
+                                                                    int s_len, double floor2) {
+    extern __shared__ __attribute__((aligned(16))) double yin_lds[];
+    float* d;
+    double* en;
+    const int g = yin_dprime(yin_lds, x, x_stride, G, T, F, hop, W, tau_max, origin, s_len, &d, &en);
+    if (g < 0) return;
+    const int lane = threadIdx.x & 63;
+
+    // K rounds: the smallest (value, lag) among the local minima that lie above the pick of the round before
+    int ct[YIN_MAX_K], n = 0;
+    float pv = -INFINITY;
+    int pt = -1;
+    bool more = yin_energy(en) / (double)W > floor2;   // a quiet frame (and one of NaN) has no candidate
+#pragma unroll
+    for (int r = 0; r < YIN_MAX_K; ++r) {
+        ct[r] = 0x7fffffff;
+        if (r < K && more) {
+            float bv = INFINITY;
+            int bi = 0x7fffffff;
+            for (int tau = tau_min + lane; tau <= tau_max; tau += 64) {
+                const float v = d[tau], left = d[tau - 1], right = tau < tau_max ? d[tau + 1] : INFINITY;
+                const bool is_min = v < left && v <= right;               // false on a NaN
+                const bool above = v > pv || (v == pv && tau > pt);
+                if (is_min && above && (v < bv || bi == 0x7fffffff)) bv = v, bi = tau;   // ascending tau: the first of equals stays
+            }
+#pragma unroll
+            for (int off = 32; off; off >>= 1) {
+                const float ov = __shfl_xor(bv, off);
+                const int oi = __shfl_xor(bi, off);
+                if (oi != 0x7fffffff && (bi == 0x7fffffff || ov < bv || (ov == bv && oi < bi))) bv = ov, bi = oi;
+            }
+            if (bi == 0x7fffffff) {
+                more = false;
+            } else {
+                ct[r] = bi, pv = bv, pt = bi, n = r + 1;
+            }
+        }
+    }
+
+    // lane k < n refines pick k and stores it at the rank of its lag; lanes n .. K-1 store the absent slots
+    if (lane < K) {
+        int mine = 0x7fffffff, slot = lane;
+        float pf = 0.f, af = INFINITY;
+#pragma unroll
+        for (int r = 0; r < YIN_MAX_K; ++r)
+            if (lane == r) mine = ct[r];
+        if (lane < n) {
+            slot = 0;
+#pragma unroll
+            for (int r = 0; r < YIN_MAX_K; ++r) slot += ct[r] < mine;
+            double period, apv;
+            yin_refine(d, mine, tau_max, period, apv);
+            pf = (float)period, af = (float)apv;
+        }
+        period_out[(int64_t)g * K + slot] = pf;
+        ap_out[(int64_t)g * K + slot] = af;
+    }
+}
+
 }  // namespace golf
 
 using namespace golf;
+
+// the refusals that golf_f0_yin_f32 and golf_f0_candidates_f32 share; GOLF_OK if none applies
+static int yin_refuse(const char* who, int64_t x_stride, int B, int T, int F, int hop, int W, int tau_min, int tau_max) {
+    if (B < 1 || T < 0 || F < 1) return fail(GOLF_EINVAL, "%s: bad size (B=%d T=%d F=%d)", who, B, T, F);
+    if (x_stride < T) return fail(GOLF_EINVAL, "%s: row stride %lld < T=%d", who, (long long)x_stride, T);
+    if (hop < 1) return fail(GOLF_EUNSUPPORTED, "%s: hop=%d must be >= 1", who, hop);
+    if (tau_min < 1) return fail(GOLF_EUNSUPPORTED, "%s: tau_min=%d must be >= 1", who, tau_min);
+    if (tau_max <= tau_min) return fail(GOLF_EUNSUPPORTED, "%s: tau_max=%d must exceed tau_min=%d", who, tau_max, tau_min);
+    if (W < 1) return fail(GOLF_EUNSUPPORTED, "%s: window W=%d must be >= 1", who, W);
+    if ((int64_t)W + tau_max > YIN_MAX_S)
+        return fail(GOLF_EUNSUPPORTED, "%s: frame W + tau_max = %lld samples exceeds %d (a frame must fit LDS)", who,
+                    (long long)W + tau_max, YIN_MAX_S);
+    if ((int64_t)B * F >= ((int64_t)1 << 31))
+        return fail(GOLF_EUNSUPPORTED, "%s: B*F = %lld frames, must be < 2^31", who, (long long)B * F);
+    return GOLF_OK;
+}
 
 extern "C" {
 
@@ -235,18 +350,8 @@ int golf_f0_yin_f32(const float* x, int64_t x_stride, float* f0, float* period, 
                     void* stream) {
     if ((!x && T > 0) || (!f0 && !period && !ap))
         return fail(GOLF_EINVAL, "f0_yin: null pointer (x=%p f0=%p period=%p ap=%p; at least one output)", x, f0, period, ap);
-    if (B < 1 || T < 0 || F < 1) return fail(GOLF_EINVAL, "f0_yin: bad size (B=%d T=%d F=%d)", B, T, F);
-    if (x_stride < T) return fail(GOLF_EINVAL, "f0_yin: row stride %lld < T=%d", (long long)x_stride, T);
     if (!(sample_rate > 0.0)) return fail(GOLF_EINVAL, "f0_yin: sample_rate=%g must be positive", sample_rate);
-    if (hop < 1) return fail(GOLF_EUNSUPPORTED, "f0_yin: hop=%d must be >= 1", hop);
-    if (tau_min < 1) return fail(GOLF_EUNSUPPORTED, "f0_yin: tau_min=%d must be >= 1", tau_min);
-    if (tau_max <= tau_min) return fail(GOLF_EUNSUPPORTED, "f0_yin: tau_max=%d must exceed tau_min=%d", tau_max, tau_min);
-    if (W < 1) return fail(GOLF_EUNSUPPORTED, "f0_yin: window W=%d must be >= 1", W);
-    if ((int64_t)W + tau_max > YIN_MAX_S)
-        return fail(GOLF_EUNSUPPORTED, "f0_yin: frame W + tau_max = %lld samples exceeds %d (a frame must fit LDS)",
-                    (long long)W + tau_max, YIN_MAX_S);
-    if ((int64_t)B * F >= ((int64_t)1 << 31))
-        return fail(GOLF_EUNSUPPORTED, "f0_yin: B*F = %lld frames, must be < 2^31", (long long)B * F);
+    if (const int rc = yin_refuse("f0_yin", x_stride, B, T, F, hop, W, tau_min, tau_max)) return rc;
     const size_t lds = yin_lds_bytes(W, tau_max);
     if (lds > 64 * 1024) {   /* > 64 KB of dynamic LDS per workgroup needs the opt-in */
         static const hipError_t attr =
@@ -259,6 +364,27 @@ int golf_f0_yin_f32(const float* x, int64_t x_stride, float* f0, float* period, 
                        (hipStream_t)stream, x, x_stride, f0, period, ap, G, T, F, hop, W, tau_min, tau_max, origin,
                        yin_frame_floats(W, tau_max), sample_rate,
                        threshold, rms_floor * rms_floor);
+    GOLF_LAUNCH_CHECK();
+    return GOLF_OK;
+}
+
+int golf_f0_candidates_f32(const float* x, int64_t x_stride, float* cand_period, float* cand_ap, int B, int T, int F, int hop,
+                           int W, int tau_min, int tau_max, int K, int64_t origin, double rms_floor, void* stream) {
+    if ((!x && T > 0) || !cand_period || !cand_ap)
+        return fail(GOLF_EINVAL, "f0_candidates: null pointer (x=%p cand_period=%p cand_ap=%p)", x, cand_period, cand_ap);
+    if (const int rc = yin_refuse("f0_candidates", x_stride, B, T, F, hop, W, tau_min, tau_max)) return rc;
+    if (K < 1 || K > YIN_MAX_K) return fail(GOLF_EUNSUPPORTED, "f0_candidates: K=%d candidates, must be 1..%d", K, YIN_MAX_K);
+    const size_t lds = yin_lds_bytes(W, tau_max);
+    if (lds > 64 * 1024) {   /* > 64 KB of dynamic LDS per workgroup needs the opt-in */
+        static const hipError_t attr = hipFuncSetAttribute((const void*)f0_candidates_kernel,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, YIN_LDS_OPT_IN);
+        if (attr != hipSuccess)
+            return fail((int)attr, "f0_candidates: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
+    }
+    const int G = B * F, gx = G < YIN_GRID_X ? G : YIN_GRID_X;
+    hipLaunchKernelGGL(f0_candidates_kernel, dim3((unsigned)gx, (unsigned)ceil_div(G, gx)), dim3(YIN_THREADS), lds,
+                       (hipStream_t)stream, x, x_stride, cand_period, cand_ap, G, T, F, hop, W, tau_min, tau_max, K, origin,
+                       yin_frame_floats(W, tau_max), rms_floor * rms_floor);
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "lti_frames_ola",
+__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "lti_frames_ola",
            "glottal_osc",
            "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
@@ -789,6 +789,140 @@ def f0_yin(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, 
     out = _F0Yin.apply(x, float(sample_rate), hop, W, tau_min, tau_max, -(S // 2) if centred else 0, F, float(threshold),
                        float(rms_floor), bool(return_all))
     return out if return_all else out[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# f0 tracking: per-frame candidate periods (csrc/f0_yin.hip) and the minimum-cost path through them (csrc/f0_viterbi.hip)
+# ------------------------------------------------------------------------------------------------
+F0_MAX_CANDIDATES = 7      # csrc/f0_yin.hip YIN_MAX_K, csrc/f0_viterbi.hip VIT_MAX_K: 8 states, the 64 lanes are their pairs
+F0_VITERBI_COSTS = dict(unvoiced_cost=0.3, lag_cost=0.02, jump_cost=0.35, switch_cost=0.14)
+
+
+class _F0Candidates(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, hop, W, tau_min, tau_max, K, origin, F, rms_floor):
+        _lib.require_device(x)
+        lib = _lib.load()
+        x = _rows(x)
+        B, T = x.shape
+        period = torch.empty(B, F, K, dtype=torch.float32, device=x.device)
+        ap = torch.empty_like(period)
+        rcode = lib.golf_f0_candidates_f32(x.data_ptr(), x.stride(0), period.data_ptr(), ap.data_ptr(), B, T, F, hop, W,
+                                           tau_min, tau_max, K, origin, rms_floor, _lib.stream_ptr())
+        _lib.check(rcode, "golf_f0_candidates_f32")
+        ctx.mark_non_differentiable(period, ap)   # a search over lags: no gradient reaches the waveform
+        return period, ap
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return (None,) * 9
+
+
+def f0_candidates(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, f0_max: float = 1000.0,
+                  window_length: int = None, n_candidates: int = 7, rms_floor: float = 0.0, centred: bool = True,
+                  n_frames: int = None):
+    """Candidate periods per frame for ``f0_viterbi`` (the definition is in include/golf_amd.h): x (B, T) ->
+    ``(cand_period, cand_ap)``, each (B, F, n_candidates).  The frames, lags and the normalised difference d' are those of
+    ``f0_yin``; the candidates are the ``n_candidates`` (1..7) local minima of d' with the smallest values, listed by
+    ascending lag and refined like ``f0_yin``'s period.  A slot that is not used holds period 0 and ap +inf; a frame whose
+    RMS over the window is at most ``rms_floor`` has none.  The outputs never require grad."""
+    if x.dim() != 2:
+        raise _lib.GolfError(f"f0_candidates: x must be (B, T) (got {tuple(x.shape)})")
+    hop, K = int(hop), int(n_candidates)
+    if hop < 1:
+        raise _lib.GolfError(f"f0_candidates: hop={hop} must be >= 1")
+    if not 1 <= K <= F0_MAX_CANDIDATES:
+        raise _lib.GolfError(f"f0_candidates: n_candidates={K} must be 1..{F0_MAX_CANDIDATES}")
+    tau_min, tau_max, W = f0_lags(float(sample_rate), float(f0_min), float(f0_max), window_length)
+    if tau_min < 1 or tau_max <= tau_min:
+        raise _lib.GolfError(f"f0_candidates: lags {tau_min}..{tau_max} (need 1 <= tau_min < tau_max: f0_max <= sample_rate, "
+                             "f0_min < f0_max)")
+    if W < 1:
+        raise _lib.GolfError(f"f0_candidates: window_length={W} must be >= 1")
+    S = W + tau_max
+    if S > F0_MAX_FRAME:
+        raise _lib.GolfError(f"f0_candidates: frame window_length + tau_max = {S} samples exceeds {F0_MAX_FRAME}")
+    F = f0_frames(x.shape[1], S, hop, centred) if n_frames is None else int(n_frames)
+    if F < 1:
+        raise _lib.GolfError(f"f0_candidates: n_frames={F} must be >= 1")
+    if x.shape[0] * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
+        raise _lib.GolfError(f"f0_candidates: B*F = {x.shape[0] * F} frames, must be < 2^31")
+    if x.shape[0] == 0:
+        _lib.require_device(x.float())
+        z = torch.empty(0, F, K, dtype=torch.float32, device=x.device)
+        return z, z.clone()
+    return _F0Candidates.apply(x, hop, W, tau_min, tau_max, K, -(S // 2) if centred else 0, F, float(rms_floor))
+
+
+class _F0Viterbi(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, cand_period, cand_ap, sample_rate, lag_ref, unvoiced_cost, lag_cost, jump_cost, switch_cost, want_state):
+        _lib.require_device(cand_period, cand_ap)
+        lib = _lib.load()
+        cand_period, cand_ap = cand_period.contiguous(), cand_ap.contiguous()
+        B, F, K = cand_period.shape
+        f0 = torch.empty(B, F, dtype=torch.float32, device=cand_period.device)
+        state = torch.empty(B, F, dtype=torch.int32, device=cand_period.device) if want_state else None
+        ws_bytes = lib.golf_f0_viterbi_workspace_bytes(B, F, K)   # the backpointers of more frames than LDS holds
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=cand_period.device) if ws_bytes else None
+        rcode = lib.golf_f0_viterbi_f32(cand_period.data_ptr(), cand_ap.data_ptr(), f0.data_ptr(), _lib.ptr(state),
+                                        _lib.ptr(ws), ws_bytes, B, F, K, sample_rate, lag_ref, unvoiced_cost, lag_cost,
+                                        jump_cost, switch_cost, _lib.stream_ptr())
+        _lib.check(rcode, "golf_f0_viterbi_f32")
+        out = (f0, state) if want_state else (f0,)
+        ctx.mark_non_differentiable(*out)   # an argmin over paths: no gradient reaches the candidates
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return (None,) * 9
+
+
+def f0_viterbi(cand_period: torch.Tensor, cand_ap: torch.Tensor, sample_rate: float, lag_ref: float,
+               unvoiced_cost: float = 0.3, lag_cost: float = 0.02, jump_cost: float = 0.35, switch_cost: float = 0.14,
+               return_state: bool = False):
+    """The minimum-cost path through the candidates of ``f0_candidates`` (B, F, K), K <= 7, over each row (the definition is
+    in include/golf_amd.h): ``f0 (B, F)`` in Hz with 0 for the frames the path calls unvoiced, or with ``return_state``
+    ``(f0, state)``, state (B, F) int32 with 0 for unvoiced and k + 1 for slot k.  A frame costs ``unvoiced_cost`` unvoiced
+    and ``max(ap, 0) + lag_cost * log2(period / lag_ref)`` on a candidate; a step between two candidates costs ``jump_cost``
+    per octave, one between voiced and unvoiced ``switch_cost``.  The defaults are Praat's path-finder settings (Boersma
+    1993) moved to the scale of d'; they are not tuned on speech.  Float64 inside; the outputs never require grad."""
+    if cand_period.dim() != 3 or cand_period.shape != cand_ap.shape:
+        raise _lib.GolfError(f"f0_viterbi: cand_period and cand_ap must both be (B, F, K) (got {tuple(cand_period.shape)} and "
+                             f"{tuple(cand_ap.shape)})")
+    B, F, K = cand_period.shape
+    if not 1 <= K <= F0_MAX_CANDIDATES:
+        raise _lib.GolfError(f"f0_viterbi: K={K} candidates must be 1..{F0_MAX_CANDIDATES}")
+    if F < 1:
+        raise _lib.GolfError(f"f0_viterbi: F={F} frames must be >= 1")
+    if not (float(sample_rate) > 0 and float(lag_ref) > 0):
+        raise _lib.GolfError(f"f0_viterbi: sample_rate={sample_rate} and lag_ref={lag_ref} must be positive")
+    if B * F >= 2 ** 31:
+        raise _lib.GolfError(f"f0_viterbi: B*F = {B * F} frames, must be < 2^31")
+    if B == 0:
+        _lib.require_device(cand_period.float(), cand_ap.float())
+        z = torch.empty(0, F, dtype=torch.float32, device=cand_period.device)
+        return (z, torch.empty(0, F, dtype=torch.int32, device=cand_period.device)) if return_state else z
+    out = _F0Viterbi.apply(cand_period, cand_ap, float(sample_rate), float(lag_ref), float(unvoiced_cost), float(lag_cost),
+                           float(jump_cost), float(switch_cost), bool(return_state))
+    return out if return_state else out[0]
+
+
+def f0_track(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, f0_max: float = 1000.0,
+             window_length: int = None, n_candidates: int = 7, rms_floor: float = 0.0, centred: bool = True,
+             n_frames: int = None, unvoiced_cost: float = 0.3, lag_cost: float = 0.02, jump_cost: float = 0.35,
+             switch_cost: float = 0.14, return_all: bool = False):
+    """f0 by ``f0_candidates`` and ``f0_viterbi`` with ``lag_ref = tau_min``: x (B, T) -> ``f0 (B, F)`` in Hz, 0 where the path
+    is unvoiced, or with ``return_all`` ``(f0, state, cand_period, cand_ap)``.  Where ``f0_yin`` decides every frame on its
+    own, this decides the utterance: an octave jump or a dropped frame costs more than it gains."""
+    cand_period, cand_ap = f0_candidates(x, sample_rate, hop, f0_min, f0_max, window_length, n_candidates, rms_floor, centred,
+                                         n_frames)
+    tau_min = f0_lags(float(sample_rate), float(f0_min), float(f0_max), window_length)[0]
+    out = f0_viterbi(cand_period, cand_ap, sample_rate, float(tau_min), unvoiced_cost, lag_cost, jump_cost, switch_cost,
+                     return_state=return_all)
+    return (out[0], out[1], cand_period, cand_ap) if return_all else out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -331,6 +331,48 @@ int golf_f0_yin_f32(const float* x, int64_t x_stride, float* f0, float* period, 
                     void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * f0 tracking (additive in ABI 6): per-frame candidate periods and a minimum-cost path through them over the utterance, in
+ * the manner of Praat's path finder (Boersma 1993), so that a frame is no longer decided on its own.  Two calls; the float64
+ * restatement in tests/f0_track_ref.py is the checker of both.
+ *
+ * golf_f0_candidates_f32: the frames, d and the fp32-rounded d' of golf_f0_yin_f32 above (its steps 1-2 with the same
+ * summation order, origin and F: one device function serves both), then instead of its search:
+ *  3c. local minima: tau in [tau_min, tau_max] with d'[tau] < d'[tau-1] and (tau == tau_max or d'[tau] <= d'[tau+1]).  A NaN
+ *      makes both comparisons false: a frame of NaN has none, and neither has a frame of zeros (d' = 1 everywhere).
+ *  4c. of these the K with the smallest d'[tau] are kept, the smaller tau first among equal values; the n <= K kept ones
+ *      are listed by ascending tau in slots 0 .. n-1, each refined as in step 4 above (period = tau + delta, ap).
+ *  5c. slots n .. K-1 are absent: period = 0, ap = +inf.  A frame with mean_{j<W} s[j]^2 <= rms_floor^2 has n = 0.
+ * Outputs cand_period, cand_ap, each (B, F, K) fp32 contiguous, every slot written by one launch; no atomics, fixed order,
+ * bit-reproducible, a row does not depend on its batch; every loop is bounded by K (tau_max / 64 + 1) whatever the data;
+ * no allocation or synchronisation, graph-capturable.  Refused before any launch: as golf_f0_yin_f32 (x NULL with T > 0 or
+ * an output NULL, B < 1, T < 0, F < 1, x_stride < T: GOLF_EINVAL; hop < 1, tau_min < 1, tau_max <= tau_min, W < 1,
+ * W + tau_max > 16384, B*F >= 2^31: GOLF_EUNSUPPORTED) and K outside 1..7 (GOLF_EUNSUPPORTED).
+ *
+ * golf_f0_viterbi_f32: cand_period, cand_ap (B, F, K) fp32 contiguous -> the path.  States: 0 is unvoiced, k+1 is slot k; a
+ * slot is present iff period > 0 and ap is neither NaN nor +inf (periods are expected finite).  In float64, with u =
+ * unvoiced_cost, lambda = lag_cost, gamma = jump_cost, sigma = switch_cost and p the period:
+ *     local cost       l[f,0] = u;   l[f,k+1] = max(ap, 0) + lambda (log2 p - log2 lag_ref)   for a present slot
+ *     transition cost  t(0,0) = 0;   t(0,j) = t(i,0) = sigma;   t(i,j) = gamma |log2 p[f,j] - log2 p[f-1,i]|   (i, j > 0)
+ *     C[0,s] = l[0,s];   C[f,j] = l[f,j] + min_i (C[f-1,i] + t(i,j))   over the present i, the smaller i on a tie
+ *     end state argmin_s C[F-1,s], the smaller s on a tie; then the backpointers are followed to frame 0.
+ * Absent states are never entered and never predecessors, and no difference of infinities is formed; state 0 always
+ * exists, so a path always exists.  Outputs: f0 (B, F) fp32, sample_rate / period of the chosen slot or 0 in state 0, and
+ * state (B, F) int32; either may be NULL (not written), not both.  One launch, one wave per row, no atomics, one fixed
+ * order: bit-reproducible and independent of the batch; no allocation or synchronisation, graph-capturable.  F is limited
+ * only by B*F < 2^31: up to 4096 frames the backpointers live in LDS; beyond that the call needs a workspace of
+ * golf_f0_viterbi_workspace_bytes(B, F, K) = 8 B F bytes (0 for F <= 4096, and 0 for sizes the call refuses), 8-byte
+ * aligned, whose contents need not survive the call.  Refused before any launch: cand_period or cand_ap NULL, both outputs
+ * NULL, B < 1, F < 1, sample_rate <= 0, lag_ref <= 0, a workspace that is needed and NULL or too small (GOLF_EINVAL); K
+ * outside 1..7, B*F >= 2^31 (GOLF_EUNSUPPORTED).
+ * ------------------------------------------------------------------------------------------- */
+int golf_f0_candidates_f32(const float* x, int64_t x_stride, float* cand_period, float* cand_ap, int B, int T, int F, int hop,
+                           int W, int tau_min, int tau_max, int K, int64_t origin, double rms_floor, void* stream);
+size_t golf_f0_viterbi_workspace_bytes(int B, int F, int K);
+int golf_f0_viterbi_f32(const float* cand_period, const float* cand_ap, float* f0, int* state, void* ws, size_t ws_bytes,
+                        int B, int F, int K, double sample_rate, double lag_ref, double unvoiced_cost, double lag_cost,
+                        double jump_cost, double switch_cost, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a-4: frame-wise LTI all-pole + windowed overlap-add — GOLF-ff end filter.
  * Replaces LTVMinimumPhaseFilter.forward, models/filters.py:131-184 (pad, unfold, lpc_synthesis ->
  * torchaudio.functional.lfilter models/lpc.py:11-16, diagonal conv_transpose1d OLA, normalise).
