@@ -14,7 +14,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "lti_frames_ola",
+__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "f0_viterbi_stream",
+           "f0_viterbi_stream_state", "lti_frames_ola",
            "glottal_osc",
            "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
@@ -908,6 +909,77 @@ def f0_viterbi(cand_period: torch.Tensor, cand_ap: torch.Tensor, sample_rate: fl
     out = _F0Viterbi.apply(cand_period, cand_ap, float(sample_rate), float(lag_ref), float(unvoiced_cost), float(lag_cost),
                            float(jump_cost), float(switch_cost), bool(return_state))
     return out if return_state else out[0]
+
+
+F0_STREAM_MAX_LAG = 1024   # csrc/f0_viterbi_stream.hip VS_MAX_LAG
+
+
+def f0_viterbi_stream_decided(n: int, lag: int, flush: bool = False) -> int:
+    """Frames of an utterance that are final once ``n`` of them have been consumed at ``lag``: all of them after a flush,
+    ``max(n - lag, 0)`` before."""
+    return n if flush else max(n - lag, 0)
+
+
+def f0_viterbi_stream_state(B: int, K: int, lag: int, device) -> torch.Tensor:
+    """The carry of ``f0_viterbi_stream`` for ``B`` rows of ``K`` candidates at ``lag`` frames: an opaque tensor that a call
+    with ``f_done == 0`` need not find cleared."""
+    B, K, lag = int(B), int(K), int(lag)
+    if not 1 <= K <= F0_MAX_CANDIDATES:
+        raise _lib.GolfError(f"f0_viterbi_stream: K={K} candidates must be 1..{F0_MAX_CANDIDATES}")
+    if not 0 <= lag <= F0_STREAM_MAX_LAG:
+        raise _lib.GolfError(f"f0_viterbi_stream: lag={lag} frames must be 0..{F0_STREAM_MAX_LAG}")
+    if B < 1:
+        raise _lib.GolfError(f"f0_viterbi_stream: B={B} rows must be >= 1")
+    nbytes = _lib.load().golf_f0_viterbi_stream_state_bytes(B, K, lag)
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def f0_viterbi_stream(cand_period: torch.Tensor, cand_ap: torch.Tensor, carry: torch.Tensor, f_done: int, lag: int,
+                      sample_rate: float, lag_ref: float, unvoiced_cost: float = 0.3, lag_cost: float = 0.02,
+                      jump_cost: float = 0.35, switch_cost: float = 0.14, flush: bool = False, return_state: bool = False):
+    """``f0_viterbi`` block by block (the definition is in include/golf_amd.h): the candidates (B, nf, K) of frames
+    ``[f_done, f_done + nf)`` -> ``f0 (B, n_out)``, or with ``return_state`` ``(f0, state)``, of the frames that became final:
+    frame g is decided once frame ``g + lag`` has been consumed, from the best path that ends there, and ``flush`` ends the
+    utterance and decides the rest.  ``n_out = decided(f_done + nf, flush) - decided(f_done)`` with
+    ``f0_viterbi_stream_decided``; it may be 0.  The result depends on the candidates and ``lag`` alone, not on the cuts, and
+    for ``lag >= F - 1`` it is ``f0_viterbi``'s.  ``carry`` comes from ``f0_viterbi_stream_state`` and is updated in place;
+    ``f_done == 0`` starts an utterance.  The outputs never require grad."""
+    if cand_period.dim() != 3 or cand_period.shape != cand_ap.shape:
+        raise _lib.GolfError(f"f0_viterbi_stream: cand_period and cand_ap must both be (B, F, K) (got "
+                             f"{tuple(cand_period.shape)} and {tuple(cand_ap.shape)})")
+    B, nf, K = cand_period.shape
+    f_done, lag, flush = int(f_done), int(lag), bool(flush)
+    if not 1 <= K <= F0_MAX_CANDIDATES:
+        raise _lib.GolfError(f"f0_viterbi_stream: K={K} candidates must be 1..{F0_MAX_CANDIDATES}")
+    if not 0 <= lag <= F0_STREAM_MAX_LAG:
+        raise _lib.GolfError(f"f0_viterbi_stream: lag={lag} frames must be 0..{F0_STREAM_MAX_LAG}")
+    if f_done < 0:
+        raise _lib.GolfError(f"f0_viterbi_stream: f_done={f_done} frames must be >= 0")
+    if flush and f_done + nf < 1:
+        raise _lib.GolfError("f0_viterbi_stream: F=0 frames must be >= 1 (a flush of an utterance of no frames)")
+    if not (float(sample_rate) > 0 and float(lag_ref) > 0):
+        raise _lib.GolfError(f"f0_viterbi_stream: sample_rate={sample_rate} and lag_ref={lag_ref} must be positive")
+    if B * nf >= 2 ** 31 or f_done + nf >= 2 ** 31:
+        raise _lib.GolfError(f"f0_viterbi_stream: B*F = {B * nf} and f_done + F = {f_done + nf} frames, must be < 2^31")
+    if B < 1:
+        raise _lib.GolfError(f"f0_viterbi_stream: B={B} rows must be >= 1")
+    _lib.require_device(carry, dtype=torch.int64)
+    if torch.is_autocast_enabled():   # as the one-shot functions: under autocast fp16 / bf16 candidates become fp32
+        cand_period, cand_ap = cand_period.float(), cand_ap.float()
+    _lib.require_device(cand_period, cand_ap)
+    n_out = f0_viterbi_stream_decided(f_done + nf, lag, flush) - f0_viterbi_stream_decided(f_done, lag)
+    dev = cand_period.device
+    f0 = torch.empty(B, n_out, dtype=torch.float32, device=dev)
+    state = torch.empty(B, n_out, dtype=torch.int32, device=dev) if return_state else None
+    if nf > 0 or n_out > 0:   # nothing to consume and nothing to decide: nothing to launch
+        lib = _lib.load()
+        cand_period, cand_ap = cand_period.detach().contiguous(), cand_ap.detach().contiguous()
+        rcode = lib.golf_f0_viterbi_stream_f32(cand_period.data_ptr(), cand_ap.data_ptr(), f0.data_ptr(), _lib.ptr(state),
+                                               max(n_out, 1), carry.data_ptr(), carry.numel() * 8, B, nf, K, lag, f_done,
+                                               int(flush), float(sample_rate), float(lag_ref), float(unvoiced_cost),
+                                               float(lag_cost), float(jump_cost), float(switch_cost), _lib.stream_ptr())
+        _lib.check(rcode, "golf_f0_viterbi_stream_f32")
+    return (f0, state) if return_state else f0
 
 
 def f0_track(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, f0_max: float = 1000.0,

@@ -373,6 +373,41 @@ int golf_f0_viterbi_f32(const float* cand_period, const float* cand_ap, float* f
                         double jump_cost, double switch_cost, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Streaming f0 tracking (additive in ABI 6): the path search of golf_f0_viterbi_f32 with its costs carried from call to call
+ * and every frame decided a fixed number of frames late, so that a live analysis can feed a decoder stream.  The float64
+ * restatement in tests/f0_stream_ref.py is the checker.
+ * A call consumes frames [f_done, f_done + nf) of every row: cand_period, cand_ap (B, nf, K) fp32 contiguous.  States,
+ * presence, l, t, C[f,j] and both tie rules are those of golf_f0_viterbi_f32 above, in float64 and summed in the same order:
+ * C after frame f has the one-shot call's bits however the frames were cut into calls.  With e(f) = argmin_s C[f,s] (the
+ * smaller s on a tie) and bp[f][j] the predecessor chosen for state j of frame f, the path to frame g seen from h >= g is
+ *     s(g | h) = bp[g+1][ bp[g+2][ ... bp[h][ e(h) ] ... ] ],        s(g | g) = e(g).
+ * With lag = L, frame g is decided once frame g + L has been consumed, as s(g | g + L); a call with flush != 0 ends the
+ * utterance at F = f_done + nf and decides the frames still open as s(g | F - 1).  The result is a function of the candidates
+ * and L alone; for L >= F - 1 it is the path of golf_f0_viterbi_f32.  With
+ *     decided(n, flush) = n if flush, else max(n - L, 0);      n_out = decided(f_done + nf, flush) - decided(f_done, 0)
+ * the call writes frames [decided(f_done, 0), decided(f_done + nf, flush)) to columns 0 .. n_out-1 of f0 and state, each
+ * (B, n_out) with unit inner stride and row stride out_stride (elements): f0 fp32, sample_rate / period of the chosen slot or
+ * 0 in state 0, and state int32; either may be NULL (not written), not both while n_out > 0.  Nothing else is written.
+ * carry: golf_f0_viterbi_stream_state_bytes(B, K, lag) = B (192 + 40 lag) bytes, 8-byte aligned, one opaque block per row
+ * (C, the logs and presence flags of the last frame, and the backpointers and candidate periods of the last `lag` frames,
+ * because f0 of a late-decided frame comes from a call that has returned).  f_done == 0 starts an utterance and reads none
+ * of it, so nobody has to clear it; a call reads and writes only its own rows' blocks and nothing beyond that size.  nf == 0
+ * with flush and f_done > 0 is valid: it decides the last min(L, f_done) frames.
+ * One launch, one wave per row, no atomics, one fixed order: bit-reproducible and independent of the batch; every loop is
+ * bounded by nf, lag and K whatever the data holds; no allocation or synchronisation.  f_done is a launch argument.
+ * Refused before any launch: B < 1, nf < 0, f_done < 0, cand_period or cand_ap NULL with nf > 0, nf == 0 without flush,
+ * nf == 0 with f_done == 0, sample_rate <= 0, lag_ref <= 0, carry NULL, misaligned or smaller than the size above, both
+ * outputs NULL while n_out > 0, out_stride < n_out (GOLF_EINVAL); K outside 1..7, lag outside 0..1024 (1024 frames are 10 s
+ * at the recipe's hop), f_done + nf >= 2^31, B*nf >= 2^31 (GOLF_EUNSUPPORTED).  The size function answers 0 for B < 1 and
+ * for the K and lag the call refuses.
+ * ------------------------------------------------------------------------------------------- */
+size_t golf_f0_viterbi_stream_state_bytes(int B, int K, int lag);
+int golf_f0_viterbi_stream_f32(const float* cand_period, const float* cand_ap, float* f0, int* state, int64_t out_stride,
+                               void* carry, size_t carry_bytes, int B, int nf, int K, int lag, int64_t f_done, int flush,
+                               double sample_rate, double lag_ref, double unvoiced_cost, double lag_cost, double jump_cost,
+                               double switch_cost, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a-4: frame-wise LTI all-pole + windowed overlap-add — GOLF-ff end filter.
  * Replaces LTVMinimumPhaseFilter.forward, models/filters.py:131-184 (pad, unfold, lpc_synthesis ->
  * torchaudio.functional.lfilter models/lpc.py:11-16, diagonal conv_transpose1d OLA, normalise).
