@@ -1817,7 +1817,7 @@ __global__ __launch_bounds__(HARM_THREADS) void harm_kernel(
     harm_sincos(sm.Phi, rs, rc);
     float acc = 0.f;
     const float* r0 = amp ? rows + (size_t)(fa - row_lo) * H : hs;
-    const float* r1 = amp ? r0 + H : hs;
+    const float* r1 = amp ? (Fa >= 2 ? r0 + H : r0) : hs;   // a lone row has no neighbour staged: 0 * (LDS left-overs) may be NaN
     for (int h0 = 1; h0 <= H; h0 += HARM_ANCHOR) {   // blocks of 32 harmonics, fully unrolled, exact re-anchor each
         float s, c;
         harm_sincos((u64)h0 * sm.Phi, s, c);
@@ -1961,8 +1961,16 @@ static int harm_geom(int B, int Tp, int phase_hop, int amp_hop, HarmGeom* g, int
     g->total = o;
     return 0;
 }
+// harm_kernel's whole LDS request: its static arrays (toff, twsum) + hs, the staged rows and the cos / sin of initial_phase
+constexpr size_t HARM_STATIC_LDS = sizeof(u64) * (256 + 4);
+constexpr size_t HARM_LDS_LIMIT = 64 * 1024;   // what a launch may ask for without opting in; nothing shipped is near it
+static size_t harm_dyn_lds(int H, int rows, bool phi0) {
+    return sizeof(float) * (size_t)(((H + 3) & ~3) + (size_t)rows * H + (phi0 ? 2 * (size_t)H : 0));
+}
+// dyn_lds: the dynamic LDS the caller's launch will request (0: its kernel stages nothing, as harm_bwd_kernel)
 static int harm_check(const char* who, const float* phase, int B, int Tp, int phase_hop, const float* amp, int Fa,
-                      int amp_hop, const float* tscale, int Fs, int ts_hop, int H, int Tout, const HarmGeom& g) {
+                      int amp_hop, const float* tscale, int Fs, int ts_hop, int H, int Tout, const HarmGeom& g,
+                      const HarmPhase& hp, size_t dyn_lds) {
     if (!phase || B < 1 || Tp < 1 || phase_hop < 1 || H < 1 || H > 4096)
         return fail(GOLF_EINVAL, "%s: bad size (B=%d Tp=%d phase_hop=%d H=%d)", who, B, Tp, phase_hop, H);
     if ((amp && (Fa < 1 || amp_hop < 1)) || (tscale && (Fs < 1 || ts_hop < 1)))
@@ -1970,10 +1978,23 @@ static int harm_check(const char* who, const float* phase, int B, int Tp, int ph
     int expect = g.N;
     if (amp) expect = std::min(expect, amp_hop > 1 ? (Fa - 1) * amp_hop + 1 : Fa);
     if (tscale) expect = std::min(expect, ts_hop > 1 ? (Fs - 1) * ts_hop + 1 : Fs);
+    // the offset truncates like any other track (the reference's mixed-hop addition, models/synth.py:432-435); the callers
+    // have run harm_phase_check: Fo >= 1, po_hop >= 1
+    if (hp.poff) expect = (int)std::min<int64_t>(expect, (int64_t)(hp.Fo - 1) * hp.po_hop + 1);
     if (Tout != expect) return fail(GOLF_EINVAL, "%s: Tout=%d, expected %d", who, Tout, expect);
-    if (amp && (size_t)(g.nrows + 1) * H * sizeof(float) > 60 * 1024)
+    // the staging limits bind the launches that stage rows: harm_bwd_kernel reads its rows' samples from global memory, and
+    // the wrapper sends it 256-sample pseudo-frames for d/d initial_phase of a bank the forward admitted without amplitudes
+    if (amp && dyn_lds && (size_t)(g.nrows + 1) * H * sizeof(float) > 60 * 1024)
         return fail(GOLF_EUNSUPPORTED, "%s: amplitude hop %d too fine for %d harmonics (LDS staging); pass amplitudes "
                     "at a coarser hop or fold them into tscale/hscale", who, amp_hop, H);
+    if (dyn_lds && HARM_STATIC_LDS + dyn_lds > HARM_LDS_LIMIT) {
+        if (amp)
+            return fail(GOLF_EUNSUPPORTED, "%s: amplitude hop %d too fine for %d harmonics%s (LDS staging: %zu bytes, limit "
+                        "%zu); pass amplitudes at a coarser hop or fold them into tscale/hscale", who, amp_hop, H,
+                        hp.phi0 ? " with initial_phase" : "", HARM_STATIC_LDS + dyn_lds, HARM_LDS_LIMIT);
+        return fail(GOLF_EUNSUPPORTED, "%s: %d harmonics%s too many for the LDS staging (%zu bytes, limit %zu)", who, H,
+                    hp.phi0 ? " with initial_phase" : "", HARM_STATIC_LDS + dyn_lds, HARM_LDS_LIMIT);
+    }
     return GOLF_OK;
 }
 
@@ -2470,7 +2491,8 @@ static int harmonic_osc_run(const char* who, const float* phase, int64_t phase_s
     HarmGeom g;
     harm_geom(B > 0 ? B : 1, Tp > 0 ? Tp : 1, phase_hop > 0 ? phase_hop : 1, amp ? amp_hop : HARM_THREADS, &g,
               amp ? Fa : 0, H > 0 ? H : 1);
-    if (int rc = harm_check(who, phase, B, Tp, phase_hop, amp, Fa, amp_hop, tscale, Fs, ts_hop, H, Tout, g))
+    const size_t lds = harm_dyn_lds(H > 0 ? H : 1, amp ? g.nrows : 1, hp.phi0 != nullptr);
+    if (int rc = harm_check(who, phase, B, Tp, phase_hop, amp, Fa, amp_hop, tscale, Fs, ts_hop, H, Tout, g, hp, lds))
         return rc;
     if (!out || out_stride < Tout || phase_stride < Tp) return fail(GOLF_EINVAL, "%s: bad output / stride", who);
     if (!ws || ws_bytes < g.total || ((uintptr_t)ws & 255))
@@ -2479,7 +2501,6 @@ static int harmonic_osc_run(const char* who, const float* phase, int64_t phase_s
     u64* Cw = (u64*)((char*)ws + g.off_cw);
     u64* Ttot = (u64*)((char*)ws + g.off_ttot);
     if (int rc = launch_phase_tiles(phase, phase_stride, Cw, Ttot, Tp, g.P, 1, g.ntile, B, st)) return rc;
-    const size_t lds = sizeof(float) * (((H + 3) & ~3) + (size_t)(amp ? g.nrows : 1) * H + (hp.phi0 ? 2 * (size_t)H : 0));
     hipLaunchKernelGGL(harm_kernel<DERIV>, dim3((unsigned)ceil_div(Tout, HARM_THREADS), B), dim3(HARM_THREADS), lds, st,
                        phase, phase_stride, (const u64*)Cw, (const u64*)Ttot, g.ntile, Tp, g.P, amp, amp ? Fa : 1,
                        amp ? amp_hop : 1, tscale, Fs, ts_hop, hscale, H, out, out_stride, Tout, g.nrows, hp);
@@ -2496,8 +2517,9 @@ extern "C" int golf_harmonic_osc_bwd_amp_f32(const float* g_out, int64_t g_out_s
     HarmGeom g;
     harm_geom(B > 0 ? B : 1, Tp > 0 ? Tp : 1, phase_hop > 0 ? phase_hop : 1, amp_hop > 0 ? amp_hop : 1, &g, Fa,
               H > 0 ? H : 1);
+    const HarmPhase hp{phase_offset, Fo, po_hop, initial_phase};
     if (int rc = harm_check("harmonic_osc_bwd_amp", phase, B, Tp, phase_hop, g_amp, Fa, amp_hop, tscale, Fs, ts_hop, H,
-                            Tout, g))
+                            Tout, g, hp, 0))
         return rc;
     if (!g_out || !g_amp || g_out_stride < Tout) return fail(GOLF_EINVAL, "harmonic_osc_bwd_amp: bad pointer / stride");
     if (!ws || ws_bytes < g.total || ((uintptr_t)ws & 255))
@@ -2511,7 +2533,7 @@ extern "C" int golf_harmonic_osc_bwd_amp_f32(const float* g_out, int64_t g_out_s
     const int nseg = Fa > 1 ? Fa - 1 : 1;
     hipLaunchKernelGGL(harm_bwd_kernel, dim3((unsigned)nseg, B), dim3(64), 0, st, phase, phase_stride, (const u64*)Cw,
                        (const u64*)Ttot, g.ntile, Tp, g.P, Fa, amp_hop, tscale, Fs, ts_hop, hscale, H, g_out,
-                       g_out_stride, part, nseg, Tout, HarmPhase{phase_offset, Fo, po_hop, initial_phase});
+                       g_out_stride, part, nseg, Tout, hp);
     GOLF_LAUNCH_CHECK();
     const int n = B * Fa * H;
     hipLaunchKernelGGL(harm_bwd_combine_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, (const float*)part,

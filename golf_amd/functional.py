@@ -2193,8 +2193,13 @@ class _HarmonicOsc(torch.autograd.Function):
                 g_po = upsample_adjoint(g_inst.float(), ctx.po[1], ctx.po[0])
         if tscale is not None and ctx.needs_input_grad[2]:
             # out = up(tscale) * S: S is the same kernel without the per-sample scale
-            geom = (H, phase_hop, amp_hop, ts_hop, Fa, 1, Tout, has_amp)
-            S = _HarmonicOsc._run(lib, "golf_harmonic_osc_fwd_f32", phase, amp if has_amp else None, None, hscale, geom,
+            # ... and its length is the output's only while another track is as short as tscale: a tscale that alone ends
+            # the output rides along as ones (acc * 1.0f: the same bits)
+            others = [_up_len(Tp, phase_hop)] + ([_up_len(Fa, amp_hop)] if has_amp else []) \
+                + ([_up_len(*ctx.po)] if phase_offset is not None else [])
+            unit = None if min(others) == Tout else torch.ones_like(tscale)
+            geom = (H, phase_hop, amp_hop, ts_hop, Fa, 1 if unit is None else Fs, Tout, has_amp)
+            S = _HarmonicOsc._run(lib, "golf_harmonic_osc_fwd_f32", phase, amp if has_amp else None, unit, hscale, geom,
                                   phase_offset, ctx.po, initial_phase)
             g_ts = upsample_adjoint(g_out[:, :Tout] * S, ts_hop, Fs)
         return g_phase, g_amp, g_ts, None, None, None, None, None, g_po, None, g_ip
@@ -2307,8 +2312,12 @@ class _BiquadFramesOLA(torch.autograd.Function):
         B, Tx0 = ex.shape
         F, K = biquads.shape[1], biquads.shape[2]
         W = window.numel()
-        # the overlap-add of the window (the normaliser of the forward), on the output samples
-        norm = torch.nn.functional.conv_transpose1d(window.new_ones(1, 1, nfr), window.view(1, 1, W), stride=hop)
+        # the overlap-add of the window (the normaliser of the forward), on the output samples: nfr copies of the window
+        # folded hop apart.  (Not conv_transpose1d: for one (1,1,nfr) x (1,1,W) call the convolution library times every
+        # solver it has on the device first, and at nfr = 15, W = 100, hop = 24 one of them left the device with a
+        # memory-access fault; fold is a plain gather, the same bits on every call.)
+        norm = torch.nn.functional.fold(window.view(1, W, 1).expand(1, W, nfr), (1, (nfr - 1) * hop + W), (1, W),
+                                        stride=(1, hop))
         norm = norm.view(-1)[pad: pad + Ty]
         gq = _rows((gy.float() / norm).contiguous())
         g_ex = torch.zeros(B, Tx0, dtype=torch.float32, device=ex.device)

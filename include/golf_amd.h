@@ -818,12 +818,18 @@ int golf_noise_band_bwd_f32(const float* g_out, int64_t g_out_stride, const floa
  *     p = up(phase)  [cycles/sample, linear upsampling from phase_hop];   Phi = inclusive cumsum of p
  *     out[t] = sum_{h=1..H} [h*p(t) < 0.5] * amp(t,h) * sin(2 pi h Phi(t))
  *     amp(t,h) = up(A)[t,h] * up(tscale)[t] * hscale[h];  A (B,Fa,H) at amp_hop, tscale (B,Fs) at ts_hop, hscale (H):
- *     each may be NULL (= 1).  Tout = min of the upsampled lengths ((n-1)*hop+1) of phase and the given factors.
+ *     each may be NULL (= 1).  Tout = min of the upsampled lengths ((n-1)*hop+1) of phase, the given factors and
+ *     phase_offset (below): whichever track is shortest ends the output.
+ *   Limits, refused before any launch (GOLF_EUNSUPPORTED): H <= 4096; with amplitudes (256 / amp_hop + 4) * H * 4 <= 61440;
+ *   and the forward / dphase launch's whole LDS request, 2080 + 4 * (((H+3) & ~3) + rows * H + (initial_phase ? 2 H : 0))
+ *   bytes with rows = 256 / amp_hop + 3 (1 without amplitudes), <= 65536: e.g. H <= 59 at amp_hop 1, and with initial_phase
+ *   H <= 2266 at amp_hop 256 and H <= 3965 without amplitudes.  _bwd_amp stages nothing and has no such limit.
  *   The (B,T,H) tensors of the reference are never formed; the phase is exact (64-bit fixed point, as in the
  *   wavetable oscillator), sin(h theta) by a rotation recurrence re-anchored from the exact phase every 32 harmonics.
  * Backward w.r.t. A (g_amp (B,Fa,H) fully overwritten); golf_harmonic_osc_dphase_f32 serves the gradient w.r.t. the phase.
  *   Optional phase terms (ABI 3; models/synth.py:434-440): harmonic h runs at h * (Phi + up(phase_offset)) + initial_phase[b,h];
- *   phase_offset (B,Fo) cycles at hop po_hop (linear upsampling, must cover Tout samples), initial_phase (B,H) cycles;
+ *   phase_offset (B,Fo) cycles at hop po_hop (linear upsampling; a track shorter than the others ends the output, as the
+ *   reference's mixed-hop addition does; one that does not cover Tout samples is refused), initial_phase (B,H) cycles;
  *   either may be NULL.  d out / d phase_offset(t) is what golf_harmonic_osc_dphase_f32 returns.
  * ------------------------------------------------------------------------------------------- */
 /* Fa = amplitude frames (0 if amp is NULL); sized for the forward and the backward */
