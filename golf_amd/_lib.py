@@ -20,7 +20,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_f64.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
-           "stft_filter.hip", "minphase_fir.hip", "lpc_analysis.hip", "f0_yin.hip", "f0_viterbi.hip", "f0_viterbi_stream.hip")
+           "stft_filter.hip", "minphase_fir.hip", "lpc_analysis.hip", "f0_yin.hip", "f0_viterbi.hip", "f0_viterbi_stream.hip", "harm_analysis.hip")
 
 _c_f32p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -65,6 +65,8 @@ SIGNATURES = {
     "golf_f0_viterbi_stream_state_bytes": (_sz, [_int] * 3),
     "golf_f0_viterbi_stream_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _vp, _i64, _vp, _sz] + [_int] * 4 + [_i64, _int]
                                    + [_dbl] * 6 + [_vp]),
+    "golf_harmonic_analysis_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p] + [_int] * 11
+                                   + [_dbl, _dbl, _vp]),
     "golf_lti_frames_workspace_bytes": (_sz, [_int] * 6),
     "golf_lti_frames_ola_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 7
                                     + [_vp, _sz, _vp]),

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 
 __all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "f0_viterbi_stream",
-           "f0_viterbi_stream_state", "lti_frames_ola",
+           "f0_viterbi_stream_state", "harmonic_analysis", "lti_frames_ola",
            "glottal_osc",
            "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
@@ -790,6 +790,99 @@ def f0_yin(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, 
     out = _F0Yin.apply(x, float(sample_rate), hop, W, tau_min, tau_max, -(S // 2) if centred else 0, F, float(threshold),
                        float(rms_floor), bool(return_all))
     return out if return_all else out[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# harmonic-plus-noise analysis: (audio, f0) -> harmonic amplitudes, phases and noise-filter log magnitudes per frame
+# (include/golf_amd.h, csrc/harm_analysis.hip)
+# ------------------------------------------------------------------------------------------------
+HNA_MAX_WINDOW = 2048      # csrc/harm_analysis.hip HNA_MAX_L
+HNA_MAX_HARMONICS = 256    # HNA_MAX_K
+HNA_MAX_NMAG = 513         # HNA_MAX_NMAG
+
+
+class _HarmonicAnalysis(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, f0, sample_rate, hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth, eps,
+                want_phases):
+        _lib.require_device(x, f0)
+        lib = _lib.load()
+        x, f0 = _rows(x), _rows(f0)
+        (B, T), F = x.shape, f0.shape[1]
+        amp = torch.empty(B, F, K, dtype=torch.float32, device=x.device)
+        phases = torch.empty_like(amp) if want_phases else None   # not asked for: not written
+        log_mag = torch.empty(B, F, n_mag, dtype=torch.float32, device=x.device) if n_mag else None
+        rcode = lib.golf_harmonic_analysis_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), f0.stride(0), amp.data_ptr(),
+                                               _lib.ptr(phases), _lib.ptr(log_mag), B, T, F, K, n_mag, hop, periods,
+                                               min_window, max_window, unvoiced_window, smooth, sample_rate, eps,
+                                               _lib.stream_ptr())
+        _lib.check(rcode, "golf_harmonic_analysis_f32")
+        out = tuple(t for t in (amp, phases, log_mag) if t is not None)
+        ctx.mark_non_differentiable(*out)   # an analysis without a backward: inference only, like f0_yin
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return (None,) * 13
+
+
+def harmonic_analysis(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop: int, num_harmonics: int,
+                      n_mag: int = None, periods: int = 4, min_window: int = None, max_window: int = 2048,
+                      unvoiced_window: int = None, smooth: int = 0, eps: float = 1e-12, return_phases: bool = False):
+    """Harmonic-plus-noise analysis (the definition is in include/golf_amd.h): x (B, T) and its f0 track (B, F) in Hz, 0 where
+    unvoiced, frame f centred on sample ``f * hop`` -> ``amplitudes (B, F, num_harmonics)``, what ``harmonic_osc`` takes as
+    ``amp`` at hop ``hop`` with the phase ``f0 / sample_rate``; with ``n_mag`` also ``log_mag (B, F, n_mag)``, what
+    ``zero_phase_fir_filter`` takes for N(0, 1) noise; with ``return_phases`` the sine phases in cycles at the frames'
+    centres, second in the tuple: ``amplitudes``, ``(amplitudes, log_mag)``, ``(amplitudes, phases)`` or ``(amplitudes,
+    phases, log_mag)``.  A voiced frame's window is a whole number of periods, at least ``periods`` and at least about
+    ``min_window`` (default ``2 * hop``) samples, at most ``max_window`` <= 2048; an unvoiced frame's is ``unvoiced_window``
+    (default ``4 * hop``) <= 2048.  ``smooth`` averages the noise power over ``2 * smooth + 1`` bins.  Harmonics at or above
+    Nyquist are 0; x is 0 outside [0, T).  The outputs never require grad; strided rows are read in place."""
+    if x.dim() != 2:
+        raise _lib.GolfError(f"harmonic_analysis: x must be (B, T) (got {tuple(x.shape)})")
+    if f0.dim() != 2 or f0.shape[0] != x.shape[0]:
+        raise _lib.GolfError(f"harmonic_analysis: f0 must be (B, F) with the B of x (got {tuple(f0.shape)}, x {tuple(x.shape)})")
+    hop, K, periods, smooth = int(hop), int(num_harmonics), int(periods), int(smooth)
+    n_mag = 0 if n_mag is None else int(n_mag)
+    if hop < 1:
+        raise _lib.GolfError(f"harmonic_analysis: hop={hop} must be >= 1")
+    min_window = 2 * hop if min_window is None else int(min_window)
+    unvoiced_window = 4 * hop if unvoiced_window is None else int(unvoiced_window)
+    max_window = int(max_window)
+    if not sample_rate > 0:
+        raise _lib.GolfError(f"harmonic_analysis: sample_rate={sample_rate} must be positive")
+    if not 1 <= K <= HNA_MAX_HARMONICS:
+        raise _lib.GolfError(f"harmonic_analysis: num_harmonics={K} must be 1..{HNA_MAX_HARMONICS}")
+    if n_mag and not 2 <= n_mag <= HNA_MAX_NMAG:
+        raise _lib.GolfError(f"harmonic_analysis: n_mag={n_mag} must be 2..{HNA_MAX_NMAG} (or None)")
+    if periods < 2:
+        raise _lib.GolfError(f"harmonic_analysis: periods={periods} must be >= 2")
+    if not 2 <= max_window <= HNA_MAX_WINDOW or not 2 <= unvoiced_window <= HNA_MAX_WINDOW:
+        raise _lib.GolfError(f"harmonic_analysis: max_window={max_window} and unvoiced_window={unvoiced_window} must be "
+                             f"2..{HNA_MAX_WINDOW}")
+    if not 1 <= min_window <= max_window:
+        raise _lib.GolfError(f"harmonic_analysis: min_window={min_window} must be 1..max_window={max_window}")
+    if smooth < 0 or (n_mag and smooth >= n_mag):
+        raise _lib.GolfError(f"harmonic_analysis: smooth={smooth} must be 0..n_mag-1 (n_mag={n_mag})")
+    if not eps >= 0:
+        raise _lib.GolfError(f"harmonic_analysis: eps={eps} must be >= 0")
+    B, F = f0.shape
+    if F < 1:
+        raise _lib.GolfError(f"harmonic_analysis: f0 has {F} frames, must be >= 1")
+    if B * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
+        raise _lib.GolfError(f"harmonic_analysis: B*F = {B * F} frames, must be < 2^31")
+    if B == 0:
+        _lib.require_device(x.float(), f0.float())
+        out = [torch.empty(0, F, K, dtype=torch.float32, device=x.device)]
+        if return_phases:
+            out.append(out[0].clone())
+        if n_mag:
+            out.append(torch.empty(0, F, n_mag, dtype=torch.float32, device=x.device))
+    else:
+        out = _HarmonicAnalysis.apply(x, f0, float(sample_rate), hop, K, n_mag, periods, min_window, max_window,
+                                      unvoiced_window, smooth, float(eps), bool(return_phases))
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -408,6 +408,45 @@ int golf_f0_viterbi_stream_f32(const float* cand_period, const float* cand_ap, f
                                double switch_cost, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Harmonic-plus-noise analysis (additive in ABI 6): (audio, f0) -> the controls of the harmonic-plus-noise decoders, per
+ * frame on the grid of the analyses above (frame f is centred on sample f*hop): the amplitudes (and sine phases) that the
+ * harmonic oscillator bank below takes and the log magnitudes that the zero-phase noise filter takes.  It is the classical
+ * sinusoidal / harmonic-plus-noise analysis with a pitch-adaptive window and a per-frame chirp; the reference has no such
+ * code.  The float64 restatement in tests/hna_ref.py is the checker.
+ * Inputs: x (B, T) fp32, unit inner stride, row stride x_stride, 0 outside [0, T); f0 (B, F) fp32 in Hz, row stride
+ * f0_stride, f0 <= 0 (or NaN) = unvoiced; K harmonics; n_mag noise bins (0: no noise output).  Every frame constant is
+ * formed in fp64 from the fp32 inputs.  Frame f of row b:
+ *  1. window length: voiced: n_per = max(periods, ceil(min_window f0 / sr)), L = min(max_window, floor(n_per sr / f0 + 0.5));
+ *     unvoiced: L = unvoiced_window; L >= 2 in every case.
+ *  2. offsets m = -floor(L/2) + i and window w[i] = 0.5 - 0.5 cos(2 pi (i + 0.5) / L), i = 0..L-1 (a Hann window on
+ *     half-integer offsets: sum w = L/2, and the harmonics of a periodic signal are orthogonal over whole periods).
+ *  3. phase of a voiced frame in cycles: omega = f0[f] / sr;  chirp s = (f0[f+1] - f0[f-1]) / (2 hop sr) if both neighbour
+ *     frames exist and are voiced, the one-sided (f0[f+1] - f0[f]) / (hop sr) or (f0[f] - f0[f-1]) / (hop sr) if only
+ *     one is, else 0;  phi(m) = omega m + s m^2 / 2.
+ *  4. harmonics k = 1..K:  c_k = (2 / sum w) sum_i w[i] x[f hop + m] exp(-2 pi j k phi(m)),  c_k = 0 where k omega >= 0.5
+ *     (the oscillator mutes those);  amplitudes[b,f,k-1] = |c_k|;  phases[b,f,k-1] = frac(arg(c_k) / 2 pi + 1/4) cycles,
+ *     1/4 where c_k = 0: the sine phase at the frame's centre, the model being sum_k amp_k sin(2 pi (k phi(m) + phase_k)).
+ *     Unvoiced frame: amplitudes and phases are 0.
+ *  5. residual r[i] = x[f hop + m] - sum_k Re(c_k exp(2 pi j k phi(m))), x itself in an unvoiced frame;
+ *     S_b = |sum_i w[i] r[i] exp(-j pi b m / (n_mag - 1))|^2 / sum w^2, b = 0..n_mag-1: the bins of the zero-phase noise
+ *     filter, whose response is exp(log_mag); white noise of variance v gives E S_b = v.
+ *  6. S_b <- mean of S over b-smooth .. b+smooth, reflected at both ends;  log_mag[b,f,b] = 0.5 log(S_b + eps).
+ * Outputs: amplitudes (B, F, K); phases (B, F, K), may be NULL; log_mag (B, F, n_mag), may be NULL (then, and with
+ * n_mag == 0, steps 5-6 are skipped); all contiguous, written in full by one launch of one workgroup per frame, no workspace,
+ * no atomics, every sum in fp32 in a fixed order: bit-reproducible, and a row's result does not depend on its batch.
+ * k phi mod 1 is exact integer arithmetic on phi(m) mod 1 formed in fp64 and kept as a 32-bit fraction of a cycle.
+ * No call allocates or synchronises; graph-capturable.  There is no gradient.
+ * Refused before any launch, all GOLF_EINVAL: B < 1, T < 0, F < 1; x NULL with T > 0, f0 or amplitudes NULL; x_stride < T,
+ * f0_stride < F; K outside 1..256; n_mag outside {0, 2..513}; hop < 1; periods < 2; max_window outside 2..2048 (a frame
+ * must fit LDS); min_window outside 1..max_window; unvoiced_window outside 2..2048; smooth < 0 or smooth >= n_mag > 0;
+ * sample_rate <= 0; eps < 0; B*F >= 2^31.
+ * ------------------------------------------------------------------------------------------- */
+int golf_harmonic_analysis_f32(const float* x, int64_t x_stride, const float* f0, int64_t f0_stride, float* amplitudes,
+                               float* phases, float* log_mag, int B, int T, int F, int K, int n_mag, int hop, int periods,
+                               int min_window, int max_window, int unvoiced_window, int smooth, double sample_rate,
+                               double eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a-4: frame-wise LTI all-pole + windowed overlap-add — GOLF-ff end filter.
  * Replaces LTVMinimumPhaseFilter.forward, models/filters.py:131-184 (pad, unfold, lpc_synthesis ->
  * torchaudio.functional.lfilter models/lpc.py:11-16, diagonal conv_transpose1d OLA, normalise).
