@@ -38,7 +38,7 @@ def frames_open(n: int, span: int, hop: int, centred: bool) -> int:
 
 def frames_final(T: int, span: int, hop: int, centred: bool) -> int:
     """Frames of the one-shot analysis of T samples (``functional.f0_frames`` / ``lpc_analysis_frames``)."""
-    return T // hop + 1 if centred else max(T - span, 0) // hop + 1
+    return GF.lpc_analysis_frames(T, span, hop, centred)
 
 
 def frame_reach(span: int, centred: bool) -> int:

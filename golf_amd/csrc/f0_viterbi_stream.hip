@@ -2,12 +2,12 @@
 // frame decided a fixed number of frames late.  Definition in include/golf_amd.h; the float64 restatement in
 // tests/f0_stream_ref.py is the checker.
 //
-// One launch, one wave per row; lane = 8 to + from as in the one-shot kernel, everything float64.
-//   1. The forward walk is the one-shot kernel's, block by block (VS_FB frames prepared by all lanes, then one add, three
-//      DPP exchanges, one add and one ds_bpermute per frame), with the same expressions in the same order, so C[f, .] has the
-//      one-shot's bits whatever the cuts.  C[f_done - 1, .], the logs and the presence flags of frame f_done - 1 come from
-//      the carry and those of the call's last frame go back to it.  Beside the chain, not on it: the backpointers (a byte per
-//      (frame, state)) and e(f) = argmin_s C[f, s] (a byte per frame) go to two LDS rings indexed by the frame number.
+// One launch, one wave per row; the lane layout, the block preparation and the walk step are f0_path.h's, shared with the
+// one-shot kernel.  What is this kernel's own:
+//   1. The forward walk runs the shared step block by block, so C[f, .] has the one-shot's bits whatever the cuts.
+//      C[f_done - 1, .], the logs and the presence flags of frame f_done - 1 come from the carry and those of the call's
+//      last frame go back to it.  Beside the chain, not on it: the backpointers (a byte per (frame, state)) and
+//      e(f) = argmin_s C[f, s] (a byte per frame) go to two LDS rings indexed by the frame number.
 //   2. After every chunk of VS_CH frames the frames that became final are decided, 64 at a time, a lane each: lane g starts
 //      from e(h), h = min(g + lag, the last frame consumed), and follows the backpointers from h down to g + 1: at most
 //      `lag` LDS reads, whatever the data holds (the state is masked to 3 bits before it indexes).  The rings hold
@@ -22,44 +22,20 @@
 //      [192 + 8 lag, 192 + 40 lag)           candidate periods of frame f at slot f mod lag, 8 floats a frame
 // A call with f_done == 0 reads none of it.  No atomics, one fixed order: bit-reproducible, and a row does not depend on its
 // batch or on how the frames were cut into calls.
-#include "common.h"
-#include "device_common.h"
+#include "f0_path.h"
 
 namespace golf {
 
-constexpr int VS_MAX_K = 7;
 constexpr int VS_MAX_LAG = 1024;
-constexpr int VS_FB = 32;          // frames prepared per block
-constexpr int VS_CH = 1024;        // frames walked between two rounds of decisions (a multiple of VS_FB)
+constexpr int VS_CH = 1024;        // frames walked between two rounds of decisions (a multiple of PATH_FB)
 constexpr int VS_RING = 2048;      // frames the LDS rings hold (a power of two)
 constexpr int VS_HEAD = 192;       // bytes of a row's carry before its two rings
-static_assert(VS_CH % VS_FB == 0, "a chunk is whole blocks");
+static_assert(VS_CH % PATH_FB == 0, "a chunk is whole blocks");
 static_assert((VS_RING & (VS_RING - 1)) == 0 && VS_RING >= VS_MAX_LAG + VS_CH, "the rings hold the lag and a chunk");
 
 static inline size_t vs_row_bytes(int lag) { return (size_t)VS_HEAD + (size_t)40 * (size_t)lag; }
 static inline bool vs_sizes_ok(int B, int K, int lag) {
-    return B >= 1 && K >= 1 && K <= VS_MAX_K && lag >= 0 && lag <= VS_MAX_LAG;
-}
-
-template <int CTRL>
-__device__ __forceinline__ double vs_dppd(double v) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, false);
-    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-constexpr int VS_DPP_HALF_MIRROR = 0x141;   // row_half_mirror: lane i of a group of 8 reads lane 7 - i
-
-// min over the 8 lanes of a group; every lane of the group ends with it
-__device__ __forceinline__ double vs_min8(double v) {
-    v = fmin(v, vs_dppd<DPP_XOR1>(v));
-    v = fmin(v, vs_dppd<DPP_XOR2>(v));
-    return fmin(v, vs_dppd<VS_DPP_HALF_MIRROR>(v));
-}
-// the lowest lane of this lane's group of 8 whose value equals the group's min: the smaller index wins a tie
-__device__ __forceinline__ int vs_argmin8(double v, double vmin, int to) {
-    const unsigned long long m = __ballot(v == vmin);
-    return (__ffs((int)((m >> (to << 3)) & 0xff)) - 1) & 7;
+    return B >= 1 && K >= 1 && K <= PATH_MAX_K && lag >= 0 && lag <= VS_MAX_LAG;
 }
 
 __global__ __launch_bounds__(64) void f0_viterbi_stream_kernel(const float* __restrict__ cand_period,
@@ -69,10 +45,7 @@ __global__ __launch_bounds__(64) void f0_viterbi_stream_kernel(const float* __re
                                                                int f_done, int flush, double sample_rate, double log2_ref,
                                                                double u_cost, double lag_cost, double jump_cost,
                                                                double switch_cost) {
-    __shared__ double tS[VS_FB * 64];               // t(from, to) of the block's frames
-    __shared__ double lpS[(VS_FB + 1) * 8];         // log2 period; row 0 is the frame before the block
-    __shared__ double locS[VS_FB * 8];              // local cost, +inf for an absent state
-    __shared__ int prS[(VS_FB + 1) * 8];            // 1 = present
+    __shared__ PathBlock blk;
     __shared__ __attribute__((aligned(8))) unsigned char bpS[VS_RING * 8];   // backpointers of frame f at f mod VS_RING
     __shared__ unsigned char eS[VS_RING];           // e(f) at f mod VS_RING
 
@@ -95,78 +68,41 @@ __global__ __launch_bounds__(64) void f0_viterbi_stream_kernel(const float* __re
     if (f_done > 0) {
         c_from = cC[from];
         if (lane < 8) {
-            lpS[lane] = cLp[lane];
-            prS[lane] = cPr[lane] != 0;
+            blk.lp[lane] = cLp[lane];
+            blk.pr[lane] = cPr[lane] != 0;
         }
         for (int g = dec + lane; g < f_done; g += 64) ((uint2*)bpS)[g & (VS_RING - 1)] = cBp[g % Lr];
-        const int e = vs_argmin8(c_from, vs_min8(c_from), to);   // e(f_done - 1): a flush without frames ends there
+        const int e = path_argmin8(c_from, path_min8(c_from), to);   // e(f_done - 1): a flush without frames ends there
         if (lane == 0) eS[(f_done - 1) & (VS_RING - 1)] = (unsigned char)e;
     }
 
     int last_nb = 0;                                // frames of the call's last block
     for (int n0 = f_done;;) {
         const int n1 = n - n0 > VS_CH ? n0 + VS_CH : n;   // the chunk is frames [n0, n1)
-        for (int fb = n0; fb < n1; fb += VS_FB) {
-            const int nb = min(VS_FB, n1 - fb);
+        for (int fb = n0; fb < n1; fb += PATH_FB) {
+            const int nb = min(PATH_FB, n1 - fb);
             last_nb = nb;
-            if (fb > f_done && lane < 8) {   // the last frame of the block before becomes row 0 (every block but the last is full)
-                lpS[lane] = lpS[VS_FB * 8 + lane];
-                prS[lane] = prS[VS_FB * 8 + lane];
-            }
-            wave_lds_fence();
-            for (int e = lane; e < nb * 8; e += 64) {
-                const int fr = e >> 3, s = e & 7;
-                double lp = 0.0, loc = u_cost;
-                int pr = 1;
-                if (s > 0) {
-                    pr = 0, loc = INFINITY;
-                    if (s <= K) {
-                        const int64_t at = (int64_t)(fb - f_done + fr) * K + (s - 1);
-                        const float p = cp[at], a = ca[at];
-                        if (p > 0.f && a < INFINITY) {   // a < inf is false for NaN and for +inf
-                            pr = 1;
-                            lp = log2((double)p);
-                            loc = fmax((double)a, 0.0) + lag_cost * (lp - log2_ref);
-                        }
-                    }
-                }
-                lpS[(fr + 1) * 8 + s] = lp, locS[fr * 8 + s] = loc, prS[(fr + 1) * 8 + s] = pr;
-            }
-            wave_lds_fence();
-#pragma unroll 4
-            for (int fr = (fb == 0 ? 1 : 0); fr < nb; ++fr) {
-                double t = INFINITY;
-                if (prS[(fr + 1) * 8 + to] && prS[fr * 8 + from]) {
-                    if (to == 0 || from == 0)
-                        t = (to == 0 && from == 0) ? 0.0 : switch_cost;
-                    else
-                        t = jump_cost * fabs(lpS[(fr + 1) * 8 + to] - lpS[fr * 8 + from]);
-                }
-                tS[fr * 64 + lane] = t;
-            }
-            wave_lds_fence();
+            // row 0 of the call's first block came from the carry; every block but the call's last is full
+            path_prepare(blk, cp + (int64_t)(fb - f_done) * K, ca + (int64_t)(fb - f_done) * K, nb, K, fb > f_done, fb == 0,
+                         log2_ref, u_cost, lag_cost, jump_cost, switch_cost);
 
             int fr = 0;
             if (fb == 0) {   // C[0, s] = local cost; frame 0 has no predecessor: its backpointers are never followed
-                c_from = locS[from];
-                const int e = vs_argmin8(c_from, vs_min8(c_from), to);
+                c_from = blk.loc[from];
+                const int e = path_argmin8(c_from, path_min8(c_from), to);
                 if (lane < 8) bpS[lane] = 0;
                 if (lane == 0) eS[0] = (unsigned char)e;
                 fr = 1;
             }
-            double t_next = tS[min(fr, nb - 1) * 64 + lane], l_next = locS[min(fr, nb - 1) * 8 + to];
+            double t_next = blk.t[min(fr, nb - 1) * 64 + lane], l_next = blk.loc[min(fr, nb - 1) * 8 + to];
             for (; fr < nb; ++fr) {
                 const double t = t_next, l = l_next;
                 const int nx = min(fr + 1, nb - 1);   // the next frame's costs are on their way while this one reduces
-                t_next = tS[nx * 64 + lane], l_next = locS[nx * 8 + to];
-                const double v = c_from + t;
-                const double vmin = vs_min8(v);
-                const double c_to = vmin + l;
-                const int i = vs_argmin8(v, vmin, to);
+                t_next = blk.t[nx * 64 + lane], l_next = blk.loc[nx * 8 + to];
+                const int i = path_step(c_from, t, l, to, from);
                 const int slot = (fb + fr) & (VS_RING - 1);
                 if (from == 0) bpS[slot * 8 + to] = (unsigned char)i;
-                c_from = __shfl(c_to, from << 3);
-                const int e = vs_argmin8(c_from, vs_min8(c_from), to);   // beside the chain: nothing below waits for it
+                const int e = path_argmin8(c_from, path_min8(c_from), to);   // beside the chain: nothing below waits for it
                 if (lane == 0) eS[slot] = (unsigned char)e;
             }
         }
@@ -204,8 +140,8 @@ __global__ __launch_bounds__(64) void f0_viterbi_stream_kernel(const float* __re
         __threadfence();
         if (lane < 8) {   // lanes 0 .. 7 hold C[n - 1, from]
             cC[lane] = c_from;
-            cLp[lane] = lpS[last_nb * 8 + lane];
-            cPr[lane] = prS[last_nb * 8 + lane];
+            cLp[lane] = blk.lp[last_nb * 8 + lane];
+            cPr[lane] = blk.pr[last_nb * 8 + lane];
         }
         const int lo = max(n - L, f_done);   // n - L does not overflow: n >= 0, L <= 1024
         for (int g = lo + lane; g < n; g += 64) cBp[g % Lr] = ((const uint2*)bpS)[g & (VS_RING - 1)];
@@ -237,9 +173,7 @@ int golf_f0_viterbi_stream_f32(const float* cand_period, const float* cand_ap, f
         return fail(GOLF_EINVAL, "f0_viterbi_stream: null pointer (cand_period=%p cand_ap=%p)", cand_period, cand_ap);
     if (nf == 0 && !flush) return fail(GOLF_EINVAL, "f0_viterbi_stream: nf=0 frames without flush: nothing to do");
     if (nf == 0 && f_done == 0) return fail(GOLF_EINVAL, "f0_viterbi_stream: flush of an utterance of no frames (nf=0 f_done=0)");
-    if (!(sample_rate > 0.0) || !(lag_ref > 0.0))
-        return fail(GOLF_EINVAL, "f0_viterbi_stream: sample_rate=%g and lag_ref=%g must be positive", sample_rate, lag_ref);
-    if (K < 1 || K > VS_MAX_K) return fail(GOLF_EUNSUPPORTED, "f0_viterbi_stream: K=%d candidates, must be 1..%d", K, VS_MAX_K);
+    if (const int rc = path_refuse("f0_viterbi_stream", K, sample_rate, lag_ref)) return rc;
     if (lag < 0 || lag > VS_MAX_LAG) return fail(GOLF_EUNSUPPORTED, "f0_viterbi_stream: lag=%d frames, must be 0..%d", lag, VS_MAX_LAG);
     if (f_done + nf >= ((int64_t)1 << 31) || (int64_t)B * nf >= ((int64_t)1 << 31))
         return fail(GOLF_EUNSUPPORTED, "f0_viterbi_stream: f_done + nf = %lld and B*nf = %lld frames, must be < 2^31",

@@ -8,6 +8,7 @@ fp32 tensors with ``mode="fp64"``, and then runs its recursion in float64 on the
 from __future__ import annotations
 
 import dataclasses
+import functools
 import math
 
 import torch
@@ -40,6 +41,29 @@ _side_streams = {}
 # and runs with autocast off; the backward runs in the same mode.  Outside autocast a non-fp32 tensor is still an error.
 _amp_fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _amp_bwd = torch.amp.custom_bwd(device_type="cuda")
+
+
+def _amp_no_grad(fn):
+    """``_amp_fwd`` for an analysis that has no gradient, so that it needs no autograd.Function: under autocast the floating
+    tensors on the device (float64 apart) become fp32 and ``fn`` runs with autocast off; every tensor is detached, so an input
+    that requires grad is accepted and the outputs never do."""
+    def prepared(v, amp):
+        if not isinstance(v, torch.Tensor):
+            return v
+        if amp and v.is_floating_point() and v.is_cuda and v.dtype is not torch.float64:
+            v = v.float()
+        return v.detach()
+
+    @functools.wraps(fn)
+    def run(*args, **kwargs):
+        amp = torch.is_autocast_enabled("cuda")
+        args, kwargs = [prepared(v, amp) for v in args], {k: prepared(v, amp) for k, v in kwargs.items()}
+        if not amp:
+            return fn(*args, **kwargs)
+        with torch.autocast("cuda", enabled=False):
+            return fn(*args, **kwargs)
+
+    return run
 
 
 def _side_stream(device) -> "torch.cuda.Stream":
@@ -729,27 +753,43 @@ def f0_lags(sample_rate: float, f0_min: float = 60.0, f0_max: float = 1000.0, wi
     return tau_min, tau_max, 2 * tau_max if window_length is None else int(window_length)
 
 
-class _F0Yin(torch.autograd.Function):
-    @staticmethod
-    @_amp_fwd
-    def forward(ctx, x, sample_rate, hop, W, tau_min, tau_max, origin, F, threshold, rms_floor, want_all):
-        _lib.require_device(x)
-        lib = _lib.load()
-        x = _rows(x)
-        B, T = x.shape
-        f0 = torch.empty(B, F, dtype=torch.float32, device=x.device)
-        period = torch.empty_like(f0) if want_all else None   # not asked for: not written
-        ap = torch.empty_like(f0) if want_all else None
-        rcode = lib.golf_f0_yin_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), _lib.ptr(period), _lib.ptr(ap), B, T, F, hop, W,
-                                    tau_min, tau_max, origin, sample_rate, threshold, rms_floor, _lib.stream_ptr())
-        _lib.check(rcode, "golf_f0_yin_f32")
-        out = (f0, period, ap) if want_all else (f0,)
-        ctx.mark_non_differentiable(*out)   # a search over lags: no gradient reaches the waveform
-        return out
+def _f0_frame_grid(who, x, sample_rate, hop, f0_min, f0_max, window_length, centred, n_frames):
+    """What ``f0_yin`` and ``f0_candidates`` share: ``(tau_min, tau_max, W, S, origin, F)`` of x (B, T), after every refusal
+    that the two have in common."""
+    if x.dim() != 2:
+        raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
+    if hop < 1:
+        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
+    tau_min, tau_max, W = f0_lags(float(sample_rate), float(f0_min), float(f0_max), window_length)
+    if tau_min < 1 or tau_max <= tau_min:
+        raise _lib.GolfError(f"{who}: lags {tau_min}..{tau_max} (need 1 <= tau_min < tau_max: f0_max <= sample_rate, "
+                             "f0_min < f0_max)")
+    if W < 1:
+        raise _lib.GolfError(f"{who}: window_length={W} must be >= 1")
+    S = W + tau_max
+    if S > F0_MAX_FRAME:
+        raise _lib.GolfError(f"{who}: frame window_length + tau_max = {S} samples exceeds {F0_MAX_FRAME}")
+    F = f0_frames(x.shape[1], S, hop, centred) if n_frames is None else int(n_frames)
+    if F < 1:
+        raise _lib.GolfError(f"{who}: n_frames={F} must be >= 1")
+    if x.shape[0] * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
+        raise _lib.GolfError(f"{who}: B*F = {x.shape[0] * F} frames, must be < 2^31")
+    return tau_min, tau_max, W, S, -(S // 2) if centred else 0, F
 
-    @staticmethod
-    def backward(ctx, *grads):
-        return (None,) * 11
+
+@_amp_no_grad   # a search over lags: no gradient reaches the waveform
+def _f0_yin(x, sample_rate, hop, W, tau_min, tau_max, origin, F, threshold, rms_floor, want_all):
+    _lib.require_device(x)
+    lib = _lib.load()
+    x = _rows(x)
+    B, T = x.shape
+    f0 = torch.empty(B, F, dtype=torch.float32, device=x.device)
+    period = torch.empty_like(f0) if want_all else None   # not asked for: not written
+    ap = torch.empty_like(f0) if want_all else None
+    rcode = lib.golf_f0_yin_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), _lib.ptr(period), _lib.ptr(ap), B, T, F, hop, W,
+                                tau_min, tau_max, origin, sample_rate, threshold, rms_floor, _lib.stream_ptr())
+    _lib.check(rcode, "golf_f0_yin_f32")
+    return (f0, period, ap) if want_all else f0
 
 
 def f0_yin(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, f0_max: float = 1000.0,
@@ -764,32 +804,15 @@ def f0_yin(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, 
     ``f * hop`` (F = max(T - S, 0) // hop + 1); x is zero outside [0, T) and ``n_frames`` overrides F.  A frame is voiced
     if a lag falls below ``threshold`` and its RMS over the window exceeds ``rms_floor``.  The outputs never require grad;
     a waveform that does is accepted.  S <= 16384."""
-    if x.dim() != 2:
-        raise _lib.GolfError(f"f0_yin: x must be (B, T) (got {tuple(x.shape)})")
     hop = int(hop)
-    if hop < 1:
-        raise _lib.GolfError(f"f0_yin: hop={hop} must be >= 1")
-    tau_min, tau_max, W = f0_lags(float(sample_rate), float(f0_min), float(f0_max), window_length)
-    if tau_min < 1 or tau_max <= tau_min:
-        raise _lib.GolfError(f"f0_yin: lags {tau_min}..{tau_max} (need 1 <= tau_min < tau_max: f0_max <= sample_rate, "
-                             "f0_min < f0_max)")
-    if W < 1:
-        raise _lib.GolfError(f"f0_yin: window_length={W} must be >= 1")
-    S = W + tau_max
-    if S > F0_MAX_FRAME:
-        raise _lib.GolfError(f"f0_yin: frame window_length + tau_max = {S} samples exceeds {F0_MAX_FRAME}")
-    F = f0_frames(x.shape[1], S, hop, centred) if n_frames is None else int(n_frames)
-    if F < 1:
-        raise _lib.GolfError(f"f0_yin: n_frames={F} must be >= 1")
-    if x.shape[0] * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
-        raise _lib.GolfError(f"f0_yin: B*F = {x.shape[0] * F} frames, must be < 2^31")
+    tau_min, tau_max, W, S, origin, F = _f0_frame_grid("f0_yin", x, sample_rate, hop, f0_min, f0_max, window_length, centred,
+                                                       n_frames)
     if x.shape[0] == 0:
         _lib.require_device(x.float())
         z = torch.empty(0, F, dtype=torch.float32, device=x.device)
         return (z, z.clone(), z.clone()) if return_all else z
-    out = _F0Yin.apply(x, float(sample_rate), hop, W, tau_min, tau_max, -(S // 2) if centred else 0, F, float(threshold),
-                       float(rms_floor), bool(return_all))
-    return out if return_all else out[0]
+    return _f0_yin(x, float(sample_rate), hop, W, tau_min, tau_max, origin, F, float(threshold), float(rms_floor),
+                   bool(return_all))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -801,30 +824,22 @@ HNA_MAX_HARMONICS = 256    # HNA_MAX_K
 HNA_MAX_NMAG = 513         # HNA_MAX_NMAG
 
 
-class _HarmonicAnalysis(torch.autograd.Function):
-    @staticmethod
-    @_amp_fwd
-    def forward(ctx, x, f0, sample_rate, hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth, eps,
-                want_phases):
-        _lib.require_device(x, f0)
-        lib = _lib.load()
-        x, f0 = _rows(x), _rows(f0)
-        (B, T), F = x.shape, f0.shape[1]
-        amp = torch.empty(B, F, K, dtype=torch.float32, device=x.device)
-        phases = torch.empty_like(amp) if want_phases else None   # not asked for: not written
-        log_mag = torch.empty(B, F, n_mag, dtype=torch.float32, device=x.device) if n_mag else None
-        rcode = lib.golf_harmonic_analysis_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), f0.stride(0), amp.data_ptr(),
-                                               _lib.ptr(phases), _lib.ptr(log_mag), B, T, F, K, n_mag, hop, periods,
-                                               min_window, max_window, unvoiced_window, smooth, sample_rate, eps,
-                                               _lib.stream_ptr())
-        _lib.check(rcode, "golf_harmonic_analysis_f32")
-        out = tuple(t for t in (amp, phases, log_mag) if t is not None)
-        ctx.mark_non_differentiable(*out)   # an analysis without a backward: inference only, like f0_yin
-        return out
-
-    @staticmethod
-    def backward(ctx, *grads):
-        return (None,) * 13
+@_amp_no_grad   # an analysis without a backward: inference only, like f0_yin
+def _harmonic_analysis(x, f0, sample_rate, hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth, eps,
+                       want_phases):
+    _lib.require_device(x, f0)
+    lib = _lib.load()
+    x, f0 = _rows(x), _rows(f0)
+    (B, T), F = x.shape, f0.shape[1]
+    amp = torch.empty(B, F, K, dtype=torch.float32, device=x.device)
+    phases = torch.empty_like(amp) if want_phases else None   # not asked for: not written
+    log_mag = torch.empty(B, F, n_mag, dtype=torch.float32, device=x.device) if n_mag else None
+    rcode = lib.golf_harmonic_analysis_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), f0.stride(0), amp.data_ptr(),
+                                           _lib.ptr(phases), _lib.ptr(log_mag), B, T, F, K, n_mag, hop, periods,
+                                           min_window, max_window, unvoiced_window, smooth, sample_rate, eps,
+                                           _lib.stream_ptr())
+    _lib.check(rcode, "golf_harmonic_analysis_f32")
+    return tuple(t for t in (amp, phases, log_mag) if t is not None)
 
 
 def harmonic_analysis(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop: int, num_harmonics: int,
@@ -880,37 +895,30 @@ def harmonic_analysis(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop
         if n_mag:
             out.append(torch.empty(0, F, n_mag, dtype=torch.float32, device=x.device))
     else:
-        out = _HarmonicAnalysis.apply(x, f0, float(sample_rate), hop, K, n_mag, periods, min_window, max_window,
-                                      unvoiced_window, smooth, float(eps), bool(return_phases))
+        out = _harmonic_analysis(x, f0, float(sample_rate), hop, K, n_mag, periods, min_window, max_window, unvoiced_window,
+                                 smooth, float(eps), bool(return_phases))
     return out[0] if len(out) == 1 else tuple(out)
 
 
 # ------------------------------------------------------------------------------------------------
 # f0 tracking: per-frame candidate periods (csrc/f0_yin.hip) and the minimum-cost path through them (csrc/f0_viterbi.hip)
 # ------------------------------------------------------------------------------------------------
-F0_MAX_CANDIDATES = 7      # csrc/f0_yin.hip YIN_MAX_K, csrc/f0_viterbi.hip VIT_MAX_K: 8 states, the 64 lanes are their pairs
+F0_MAX_CANDIDATES = 7      # csrc/f0_yin.hip YIN_MAX_K, csrc/f0_path.h PATH_MAX_K: 8 states, the 64 lanes are their pairs
 F0_VITERBI_COSTS = dict(unvoiced_cost=0.3, lag_cost=0.02, jump_cost=0.35, switch_cost=0.14)
 
 
-class _F0Candidates(torch.autograd.Function):
-    @staticmethod
-    @_amp_fwd
-    def forward(ctx, x, hop, W, tau_min, tau_max, K, origin, F, rms_floor):
-        _lib.require_device(x)
-        lib = _lib.load()
-        x = _rows(x)
-        B, T = x.shape
-        period = torch.empty(B, F, K, dtype=torch.float32, device=x.device)
-        ap = torch.empty_like(period)
-        rcode = lib.golf_f0_candidates_f32(x.data_ptr(), x.stride(0), period.data_ptr(), ap.data_ptr(), B, T, F, hop, W,
-                                           tau_min, tau_max, K, origin, rms_floor, _lib.stream_ptr())
-        _lib.check(rcode, "golf_f0_candidates_f32")
-        ctx.mark_non_differentiable(period, ap)   # a search over lags: no gradient reaches the waveform
-        return period, ap
-
-    @staticmethod
-    def backward(ctx, *grads):
-        return (None,) * 9
+@_amp_no_grad   # a search over lags: no gradient reaches the waveform
+def _f0_candidates(x, hop, W, tau_min, tau_max, K, origin, F, rms_floor):
+    _lib.require_device(x)
+    lib = _lib.load()
+    x = _rows(x)
+    B, T = x.shape
+    period = torch.empty(B, F, K, dtype=torch.float32, device=x.device)
+    ap = torch.empty_like(period)
+    rcode = lib.golf_f0_candidates_f32(x.data_ptr(), x.stride(0), period.data_ptr(), ap.data_ptr(), B, T, F, hop, W,
+                                       tau_min, tau_max, K, origin, rms_floor, _lib.stream_ptr())
+    _lib.check(rcode, "golf_f0_candidates_f32")
+    return period, ap
 
 
 def f0_candidates(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float = 60.0, f0_max: float = 1000.0,
@@ -921,57 +929,46 @@ def f0_candidates(x: torch.Tensor, sample_rate: float, hop: int, f0_min: float =
     ``f0_yin``; the candidates are the ``n_candidates`` (1..7) local minima of d' with the smallest values, listed by
     ascending lag and refined like ``f0_yin``'s period.  A slot that is not used holds period 0 and ap +inf; a frame whose
     RMS over the window is at most ``rms_floor`` has none.  The outputs never require grad."""
-    if x.dim() != 2:
-        raise _lib.GolfError(f"f0_candidates: x must be (B, T) (got {tuple(x.shape)})")
     hop, K = int(hop), int(n_candidates)
-    if hop < 1:
-        raise _lib.GolfError(f"f0_candidates: hop={hop} must be >= 1")
+    tau_min, tau_max, W, S, origin, F = _f0_frame_grid("f0_candidates", x, sample_rate, hop, f0_min, f0_max, window_length,
+                                                       centred, n_frames)
     if not 1 <= K <= F0_MAX_CANDIDATES:
         raise _lib.GolfError(f"f0_candidates: n_candidates={K} must be 1..{F0_MAX_CANDIDATES}")
-    tau_min, tau_max, W = f0_lags(float(sample_rate), float(f0_min), float(f0_max), window_length)
-    if tau_min < 1 or tau_max <= tau_min:
-        raise _lib.GolfError(f"f0_candidates: lags {tau_min}..{tau_max} (need 1 <= tau_min < tau_max: f0_max <= sample_rate, "
-                             "f0_min < f0_max)")
-    if W < 1:
-        raise _lib.GolfError(f"f0_candidates: window_length={W} must be >= 1")
-    S = W + tau_max
-    if S > F0_MAX_FRAME:
-        raise _lib.GolfError(f"f0_candidates: frame window_length + tau_max = {S} samples exceeds {F0_MAX_FRAME}")
-    F = f0_frames(x.shape[1], S, hop, centred) if n_frames is None else int(n_frames)
-    if F < 1:
-        raise _lib.GolfError(f"f0_candidates: n_frames={F} must be >= 1")
-    if x.shape[0] * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
-        raise _lib.GolfError(f"f0_candidates: B*F = {x.shape[0] * F} frames, must be < 2^31")
     if x.shape[0] == 0:
         _lib.require_device(x.float())
         z = torch.empty(0, F, K, dtype=torch.float32, device=x.device)
         return z, z.clone()
-    return _F0Candidates.apply(x, hop, W, tau_min, tau_max, K, -(S // 2) if centred else 0, F, float(rms_floor))
+    return _f0_candidates(x, hop, W, tau_min, tau_max, K, origin, F, float(rms_floor))
 
 
-class _F0Viterbi(torch.autograd.Function):
-    @staticmethod
-    @_amp_fwd
-    def forward(ctx, cand_period, cand_ap, sample_rate, lag_ref, unvoiced_cost, lag_cost, jump_cost, switch_cost, want_state):
-        _lib.require_device(cand_period, cand_ap)
-        lib = _lib.load()
-        cand_period, cand_ap = cand_period.contiguous(), cand_ap.contiguous()
-        B, F, K = cand_period.shape
-        f0 = torch.empty(B, F, dtype=torch.float32, device=cand_period.device)
-        state = torch.empty(B, F, dtype=torch.int32, device=cand_period.device) if want_state else None
-        ws_bytes = lib.golf_f0_viterbi_workspace_bytes(B, F, K)   # the backpointers of more frames than LDS holds
-        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=cand_period.device) if ws_bytes else None
-        rcode = lib.golf_f0_viterbi_f32(cand_period.data_ptr(), cand_ap.data_ptr(), f0.data_ptr(), _lib.ptr(state),
-                                        _lib.ptr(ws), ws_bytes, B, F, K, sample_rate, lag_ref, unvoiced_cost, lag_cost,
-                                        jump_cost, switch_cost, _lib.stream_ptr())
-        _lib.check(rcode, "golf_f0_viterbi_f32")
-        out = (f0, state) if want_state else (f0,)
-        ctx.mark_non_differentiable(*out)   # an argmin over paths: no gradient reaches the candidates
-        return out
+def _f0_path_shape(who, cand_period, cand_ap, sample_rate, lag_ref):
+    """What ``f0_viterbi`` and ``f0_viterbi_stream`` share: ``(B, F, K)`` of the candidates, after every refusal that the two
+    have in common."""
+    if cand_period.dim() != 3 or cand_period.shape != cand_ap.shape:
+        raise _lib.GolfError(f"{who}: cand_period and cand_ap must both be (B, F, K) (got {tuple(cand_period.shape)} and "
+                             f"{tuple(cand_ap.shape)})")
+    if not 1 <= cand_period.shape[2] <= F0_MAX_CANDIDATES:
+        raise _lib.GolfError(f"{who}: K={cand_period.shape[2]} candidates must be 1..{F0_MAX_CANDIDATES}")
+    if not (float(sample_rate) > 0 and float(lag_ref) > 0):
+        raise _lib.GolfError(f"{who}: sample_rate={sample_rate} and lag_ref={lag_ref} must be positive")
+    return cand_period.shape
 
-    @staticmethod
-    def backward(ctx, *grads):
-        return (None,) * 9
+
+@_amp_no_grad   # an argmin over paths: no gradient reaches the candidates
+def _f0_viterbi(cand_period, cand_ap, sample_rate, lag_ref, unvoiced_cost, lag_cost, jump_cost, switch_cost, want_state):
+    _lib.require_device(cand_period, cand_ap)
+    lib = _lib.load()
+    cand_period, cand_ap = cand_period.contiguous(), cand_ap.contiguous()
+    B, F, K = cand_period.shape
+    f0 = torch.empty(B, F, dtype=torch.float32, device=cand_period.device)
+    state = torch.empty(B, F, dtype=torch.int32, device=cand_period.device) if want_state else None
+    ws_bytes = lib.golf_f0_viterbi_workspace_bytes(B, F, K)   # the backpointers of more frames than LDS holds
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=cand_period.device) if ws_bytes else None
+    rcode = lib.golf_f0_viterbi_f32(cand_period.data_ptr(), cand_ap.data_ptr(), f0.data_ptr(), _lib.ptr(state),
+                                    _lib.ptr(ws), ws_bytes, B, F, K, sample_rate, lag_ref, unvoiced_cost, lag_cost,
+                                    jump_cost, switch_cost, _lib.stream_ptr())
+    _lib.check(rcode, "golf_f0_viterbi_f32")
+    return (f0, state) if want_state else f0
 
 
 def f0_viterbi(cand_period: torch.Tensor, cand_ap: torch.Tensor, sample_rate: float, lag_ref: float,
@@ -983,25 +980,17 @@ def f0_viterbi(cand_period: torch.Tensor, cand_ap: torch.Tensor, sample_rate: fl
     and ``max(ap, 0) + lag_cost * log2(period / lag_ref)`` on a candidate; a step between two candidates costs ``jump_cost``
     per octave, one between voiced and unvoiced ``switch_cost``.  The defaults are Praat's path-finder settings (Boersma
     1993) moved to the scale of d'; they are not tuned on speech.  Float64 inside; the outputs never require grad."""
-    if cand_period.dim() != 3 or cand_period.shape != cand_ap.shape:
-        raise _lib.GolfError(f"f0_viterbi: cand_period and cand_ap must both be (B, F, K) (got {tuple(cand_period.shape)} and "
-                             f"{tuple(cand_ap.shape)})")
-    B, F, K = cand_period.shape
-    if not 1 <= K <= F0_MAX_CANDIDATES:
-        raise _lib.GolfError(f"f0_viterbi: K={K} candidates must be 1..{F0_MAX_CANDIDATES}")
+    B, F, K = _f0_path_shape("f0_viterbi", cand_period, cand_ap, sample_rate, lag_ref)
     if F < 1:
         raise _lib.GolfError(f"f0_viterbi: F={F} frames must be >= 1")
-    if not (float(sample_rate) > 0 and float(lag_ref) > 0):
-        raise _lib.GolfError(f"f0_viterbi: sample_rate={sample_rate} and lag_ref={lag_ref} must be positive")
     if B * F >= 2 ** 31:
         raise _lib.GolfError(f"f0_viterbi: B*F = {B * F} frames, must be < 2^31")
     if B == 0:
         _lib.require_device(cand_period.float(), cand_ap.float())
         z = torch.empty(0, F, dtype=torch.float32, device=cand_period.device)
         return (z, torch.empty(0, F, dtype=torch.int32, device=cand_period.device)) if return_state else z
-    out = _F0Viterbi.apply(cand_period, cand_ap, float(sample_rate), float(lag_ref), float(unvoiced_cost), float(lag_cost),
-                           float(jump_cost), float(switch_cost), bool(return_state))
-    return out if return_state else out[0]
+    return _f0_viterbi(cand_period, cand_ap, float(sample_rate), float(lag_ref), float(unvoiced_cost), float(lag_cost),
+                       float(jump_cost), float(switch_cost), bool(return_state))
 
 
 F0_STREAM_MAX_LAG = 1024   # csrc/f0_viterbi_stream.hip VS_MAX_LAG
@@ -1027,6 +1016,7 @@ def f0_viterbi_stream_state(B: int, K: int, lag: int, device) -> torch.Tensor:
     return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
 
 
+@_amp_no_grad   # as the one-shot path: under autocast fp16 / bf16 candidates become fp32
 def f0_viterbi_stream(cand_period: torch.Tensor, cand_ap: torch.Tensor, carry: torch.Tensor, f_done: int, lag: int,
                       sample_rate: float, lag_ref: float, unvoiced_cost: float = 0.3, lag_cost: float = 0.02,
                       jump_cost: float = 0.35, switch_cost: float = 0.14, flush: bool = False, return_state: bool = False):
@@ -1037,28 +1027,19 @@ def f0_viterbi_stream(cand_period: torch.Tensor, cand_ap: torch.Tensor, carry: t
     ``f0_viterbi_stream_decided``; it may be 0.  The result depends on the candidates and ``lag`` alone, not on the cuts, and
     for ``lag >= F - 1`` it is ``f0_viterbi``'s.  ``carry`` comes from ``f0_viterbi_stream_state`` and is updated in place;
     ``f_done == 0`` starts an utterance.  The outputs never require grad."""
-    if cand_period.dim() != 3 or cand_period.shape != cand_ap.shape:
-        raise _lib.GolfError(f"f0_viterbi_stream: cand_period and cand_ap must both be (B, F, K) (got "
-                             f"{tuple(cand_period.shape)} and {tuple(cand_ap.shape)})")
-    B, nf, K = cand_period.shape
+    B, nf, K = _f0_path_shape("f0_viterbi_stream", cand_period, cand_ap, sample_rate, lag_ref)
     f_done, lag, flush = int(f_done), int(lag), bool(flush)
-    if not 1 <= K <= F0_MAX_CANDIDATES:
-        raise _lib.GolfError(f"f0_viterbi_stream: K={K} candidates must be 1..{F0_MAX_CANDIDATES}")
     if not 0 <= lag <= F0_STREAM_MAX_LAG:
         raise _lib.GolfError(f"f0_viterbi_stream: lag={lag} frames must be 0..{F0_STREAM_MAX_LAG}")
     if f_done < 0:
         raise _lib.GolfError(f"f0_viterbi_stream: f_done={f_done} frames must be >= 0")
     if flush and f_done + nf < 1:
         raise _lib.GolfError("f0_viterbi_stream: F=0 frames must be >= 1 (a flush of an utterance of no frames)")
-    if not (float(sample_rate) > 0 and float(lag_ref) > 0):
-        raise _lib.GolfError(f"f0_viterbi_stream: sample_rate={sample_rate} and lag_ref={lag_ref} must be positive")
     if B * nf >= 2 ** 31 or f_done + nf >= 2 ** 31:
         raise _lib.GolfError(f"f0_viterbi_stream: B*F = {B * nf} and f_done + F = {f_done + nf} frames, must be < 2^31")
     if B < 1:
         raise _lib.GolfError(f"f0_viterbi_stream: B={B} rows must be >= 1")
     _lib.require_device(carry, dtype=torch.int64)
-    if torch.is_autocast_enabled():   # as the one-shot functions: under autocast fp16 / bf16 candidates become fp32
-        cand_period, cand_ap = cand_period.float(), cand_ap.float()
     _lib.require_device(cand_period, cand_ap)
     n_out = f0_viterbi_stream_decided(f_done + nf, lag, flush) - f0_viterbi_stream_decided(f_done, lag)
     dev = cand_period.device
@@ -1066,7 +1047,7 @@ def f0_viterbi_stream(cand_period: torch.Tensor, cand_ap: torch.Tensor, carry: t
     state = torch.empty(B, n_out, dtype=torch.int32, device=dev) if return_state else None
     if nf > 0 or n_out > 0:   # nothing to consume and nothing to decide: nothing to launch
         lib = _lib.load()
-        cand_period, cand_ap = cand_period.detach().contiguous(), cand_ap.detach().contiguous()
+        cand_period, cand_ap = cand_period.contiguous(), cand_ap.contiguous()
         rcode = lib.golf_f0_viterbi_stream_f32(cand_period.data_ptr(), cand_ap.data_ptr(), f0.data_ptr(), _lib.ptr(state),
                                                max(n_out, 1), carry.data_ptr(), carry.numel() * 8, B, nf, K, lag, f_done,
                                                int(flush), float(sample_rate), float(lag_ref), float(unvoiced_cost),

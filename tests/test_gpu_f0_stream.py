@@ -78,6 +78,31 @@ def test_a_frame_per_call_wraps_the_ring():
     assert (state.cpu().numpy() != refs[399]["state"]).sum() == (refs[65]["state"] != refs[399]["state"]).sum()
 
 
+@pytest.mark.parametrize("F,K", [(1057, 1), (1057, 7), (2113, 1)])
+def test_one_call_longer_than_a_chunk(F, K):
+    """One call of more than 1024 frames: the kernel decides between its chunks, and past 2048 frames its LDS rings wrap
+    inside the call.  1057 = 1024 + 33 ends on a block of one frame; 2113 = 2048 + 65.  Seed 0, lags 8 and 1024 (the kernel
+    takes no more), the reference for these two alone."""
+    p, a = TR.random_candidates(F, K, 0)
+    pd, ad = torch.tensor(p).cuda(), torch.tensor(a).cuda()
+    within = [500, 524] + [1024] * ((F - 1024) // 1024) + [(F - 1024) % 1024]   # no call crosses a chunk
+    assert sum(within) == F and max(within) <= 1024
+    for lag in (8, 1024):
+        ref = SR.fixed_lag(p, a, lag, SR_, REF, **TR.COSTS)
+        assert ref["margin"] >= 1e-6
+        f0d, stated = stream_path(pd, ad, lag, [F])
+        f0, state = f0d.cpu().numpy().astype(np.float64), stated.cpu().numpy()
+        voiced = state > 0
+        e_f0 = (np.abs(f0 - ref["f0"])[voiced] / ref["f0"][voiced]).max() if voiced.any() else 0.0
+        print(f"F = {F}, K = {K}, lag {lag}: margin {ref['margin']:.1e}; {int((state != ref['state']).sum())} states differ; "
+              f"f0 {e_f0:.2e}")
+        assert np.array_equal(state, ref["state"])
+        assert np.isfinite(f0).all() and np.array_equal(f0 == 0, state == 0) and e_f0 <= TOL
+        for cuts, alone in ((within, False), ([F], True)):
+            f0c, statec = stream_path(pd, ad, lag, cuts, alone)
+            assert torch.equal(f0c, f0d) and torch.equal(statec, stated), (lag, cuts, alone)
+
+
 # ---- the carry ----------------------------------------------------------------------------------------------------------------
 CARRY_SHAPE, CARRY_LAG = (130, 7), 7
 
