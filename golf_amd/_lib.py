@@ -67,6 +67,8 @@ SIGNATURES = {
                                    + [_dbl] * 6 + [_vp]),
     "golf_harmonic_analysis_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p] + [_int] * 11
                                    + [_dbl, _dbl, _vp]),
+    "golf_harmonic_analysis_stream_f32": (_int, [_c_f32p, _i64, _i64, _int, _c_f32p, _i64, _i64, _int, _c_f32p, _c_f32p,
+                                                 _c_f32p, _int, _i64, _int, _int] + [_int] * 8 + [_dbl, _dbl, _vp]),
     "golf_lti_frames_workspace_bytes": (_sz, [_int] * 6),
     "golf_lti_frames_ola_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 7
                                     + [_vp, _sz, _vp]),

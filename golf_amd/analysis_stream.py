@@ -1,5 +1,6 @@
-"""Block-by-block analysis: the streaming counterparts of ``f0.F0Analysis``, ``f0.F0Tracker`` and ``lpc.LPCAnalysis``, for a
-live waveform that feeds a decoder stream (``stream.DecoderStream`` and its siblings take exactly these tracks).
+"""Block-by-block analysis: the streaming counterparts of ``f0.F0Analysis``, ``f0.F0Tracker``, ``lpc.LPCAnalysis`` and
+``hna.HarmonicNoiseAnalysis``, for a live waveform that feeds a decoder stream (``stream.DecoderStream`` and its siblings take
+exactly these tracks).
 
 The protocol is the decoder streams': ``push(x)`` takes the next (B, n) block of the waveform, any n >= 0, and returns the
 frames that became final, in the types the module's ``forward`` returns (possibly with zero frames); ``finish()`` ends the
@@ -10,7 +11,9 @@ YIN frames and LPC frames are frame-local: a frame is final once its last sample
 ``centred=False, n_frames=`` on the buffered samples that the open frames still need -- a frame's arithmetic does not depend
 on where it sits in the row, which is why the result is exact.  Zeros stand before sample 0 and after the end, as the
 definitions say.  The tracker is not frame-local: its candidates are, and the path through them is decided ``lag`` frames
-late by golf_f0_viterbi_stream_f32 (csrc/f0_viterbi_stream.hip), whose costs are carried from push to push.
+late by golf_f0_viterbi_stream_f32 (csrc/f0_viterbi_stream.hip), whose costs are carried from push to push.  The
+harmonic-plus-noise analysis takes two inputs, the waveform and its f0 track, which arrive at different paces
+(``HarmonicNoiseStream``): its frames are frame-local too, given the f0 of the neighbouring frames.
 
 Inference only; one stream for the whole batch; ``push`` does no host-device synchronisation.
 """
@@ -22,10 +25,11 @@ from . import _lib
 from . import functional as GF
 from .audiotensor import AudioTensor
 from .f0 import F0Analysis, F0Tracker
+from .hna import HarmonicNoiseAnalysis
 from .lpc import LPCAnalysis
 
-__all__ = ["F0Stream", "F0TrackerStream", "LPCAnalysisStream", "open_analysis_stream", "frames_open", "frames_final",
-           "frame_reach"]
+__all__ = ["F0Stream", "F0TrackerStream", "LPCAnalysisStream", "HarmonicNoiseStream", "open_analysis_stream", "frames_open",
+           "frames_final", "frame_reach", "hna_frames_final", "hna_keep_from"]
 
 
 # ---- geometry: host integers only ------------------------------------------------------------------------------------------
@@ -270,9 +274,157 @@ class LPCAnalysisStream(_FrameStream):
         return tuple(AudioTensor(t, self.hop) for t in self._run(None, True))
 
 
+# ---- harmonic-plus-noise analysis: two inputs at two paces ------------------------------------------------------------------
+def hna_frames_final(pushed: int, f0_received: int, span: int, hop: int) -> int:
+    """Frames of a ``HarmonicNoiseStream``, counted from index 0, that are final after ``pushed`` samples and ``f0_received``
+    f0 frames: frame f is final once the longest window it can take (``span = max(max_window, unvoiced_window)`` samples
+    centred on ``f * hop``) lies below ``pushed`` and f0 frame ``f + 1``, the chirp's next neighbour, has come."""
+    return min(frames_open(pushed, span, hop, True), max(f0_received - 1, 0))
+
+
+def hna_keep_from(next_frame: int, span: int, hop: int):
+    """``(sample, f0 frame)`` from which a ``HarmonicNoiseStream`` whose next frame is ``next_frame`` keeps its inputs: the
+    start of that frame's longest window, and its previous neighbour."""
+    return max(next_frame * hop - span // 2, 0), max(next_frame - 1, 0)
+
+
+class HarmonicNoiseStream:
+    """``hna.HarmonicNoiseAnalysis`` block by block, for live audio and its live f0 (an ``F0Stream`` or ``F0TrackerStream``
+    on the same audio, which is ``lag`` frames late) feeding a ``stream.HarmonicPlusNoiseStream``.
+
+    ``push(x=None, f0=None)`` takes the next (B, n) block of the waveform (a tensor or an ``AudioTensor`` at hop 1) and / or the
+    next (B, k) f0 frames (a tensor or an ``AudioTensor`` at ``hop_length``); either may be absent or empty.  It returns the
+    frames that became final in the types of ``forward``: ``(amplitudes, log_mag)``, AudioTensors at ``hop_length``, or
+    ``amplitudes`` alone when ``n_mag`` is None, possibly with zero frames.  ``finish()`` ends the utterance -- F = the f0
+    frames received, T = the samples received; frames beyond T read zeros and audio beyond the last frame's window is
+    ignored, as the one-shot does for the same ``(x, f0)`` -- returns the rest and starts a new utterance.  ``push_all`` /
+    ``finish_all`` return the plain tensors of ``analyse``, with the phases.  Everything pushed out plus ``finish()`` is
+    ``torch.equal`` to the module on the concatenated ``(x, f0)``, for any cuts of either input and any interleaving.
+
+    Frame f is final once ``pushed >= f * hop + frame_reach(Lmax, True)``, ``Lmax = max(max_window, unvoiced_window)``, and f0
+    frame ``f + 1`` has come (``hna_frames_final``): the rule is the worst case over the batch and over the window lengths,
+    so ``push`` never reads the device.  The frames run through golf_harmonic_analysis_stream_f32, the one-shot kernel at a
+    position of the utterance.  Samples before ``next_frame * hop - Lmax // 2`` and f0 frames before ``next_frame - 1`` are
+    dropped (``hna_keep_from``); whichever input runs ahead is held until the other catches up.
+
+    ``latency`` is the audio side, ``frame_reach(Lmax, True)`` samples beyond a frame's own time (1024 at the defaults); with
+    the f0 source the whole figure is ``max(latency, hop_length + the f0 stream's latency)``: 240 + 2520 = 2760 samples at the
+    recipe behind ``F0TrackerStream(lag=8)``.
+
+    Inference only; one stream for the whole batch; ``push`` does no host-device synchronisation."""
+
+    def __init__(self, module: HarmonicNoiseAnalysis, batch_size: int):
+        if not isinstance(module, HarmonicNoiseAnalysis):
+            raise TypeError(f"HarmonicNoiseStream: a HarmonicNoiseAnalysis is needed (got {type(module).__name__})")
+        if int(batch_size) < 1:
+            raise ValueError(f"HarmonicNoiseStream: batch_size={batch_size}")
+        self.module, self.B, self.hop = module, int(batch_size), int(module.hop_length)
+        if self.hop < 1:
+            raise _lib.GolfError(f"HarmonicNoiseStream: hop={self.hop} must be >= 1")
+        self.span = max(int(module.max_window), int(module.unvoiced_window))   # Lmax
+        self._x = self._f0 = None   # (B, m) samples [_x0, _x0 + m) and (B, n) f0 frames [_f00, _f00 + n) of the utterance
+        self._reset()
+
+    def _reset(self) -> None:
+        self.pushed = 0        # samples of this utterance so far
+        self.f0_received = 0   # f0 frames of this utterance so far
+        self.framed = 0        # frames emitted so far
+        self._x0 = self._f00 = 0
+        self._x = None if self._x is None else self._x[:, :0]
+        self._f0 = None if self._f0 is None else self._f0[:, :0]
+
+    @property
+    def latency(self) -> int:
+        """The smallest number of samples beyond a frame's own time ``f * hop`` after which it can have been emitted: the
+        audio side.  The f0 side adds to it: the frame needs f0 frame ``f + 1`` (class docstring)."""
+        return frame_reach(self.span, True)
+
+    def _take(self, t, name: str, hop: int) -> torch.Tensor:
+        if isinstance(t, AudioTensor):
+            assert t.hop_length == hop, f"{name} must be at hop {hop} (got {t.hop_length})"
+            t = t.as_tensor()
+        if t.dim() != 2 or t.shape[0] != self.B:
+            raise ValueError(f"HarmonicNoiseStream.push: {name} of shape {tuple(t.shape)}; the stream has B={self.B}")
+        if torch.is_grad_enabled() and t.requires_grad:
+            raise NotImplementedError("HarmonicNoiseStream: an input that requires grad (streaming is inference only) is not "
+                                      "supported")
+        if torch.is_autocast_enabled() and t.is_floating_point():   # as the one-shot functions: fp16 / bf16 become fp32
+            t = t.float()
+        _lib.require_device(t)
+        return t.detach()
+
+    @staticmethod
+    def _cat(buf, t):
+        return t if buf is None or buf.shape[1] == 0 else (torch.cat([buf, t], 1) if t.shape[1] else buf)
+
+    def _device(self):
+        for t in (self._x, self._f0):
+            if t is not None:
+                return t.device
+        return torch.device("cuda")
+
+    def _frames(self, x, f0, x_t0: int, f_first: int, f0_first: int, k: int, last: bool, phases: bool):
+        """Frames ``f_first .. f_first + k - 1`` from the buffers, which start at sample ``x_t0`` and frame ``f0_first``."""
+        m = self.module
+        return GF.harmonic_analysis_stream(x, f0, x_t0, f_first, f0_first, k, last, m.sample_rate, self.hop, m.num_harmonics,
+                                           m.n_mag, m.periods, m.min_window, m.max_window, m.unvoiced_window, m.smooth, m.eps,
+                                           return_phases=phases)
+
+    def _run(self, x, f0, final: bool, phases: bool):
+        x = None if x is None else self._take(x, "x", 1)
+        f0 = None if f0 is None else self._take(f0, "f0", self.hop)
+        with torch.no_grad():
+            if x is not None:
+                self._x, self.pushed = self._cat(self._x, x), self.pushed + x.shape[1]
+            if f0 is not None:
+                self._f0, self.f0_received = self._cat(self._f0, f0), self.f0_received + f0.shape[1]
+            # finish(): one frame per f0 frame, whatever the number of samples
+            total = self.f0_received if final else hna_frames_final(self.pushed, self.f0_received, self.span, self.hop)
+            k = max(total - self.framed, 0)
+            dev = self._device()
+            xb = self._x if self._x is not None else torch.empty(self.B, 0, dtype=torch.float32, device=dev)
+            fb = self._f0 if self._f0 is not None else torch.empty(self.B, 0, dtype=torch.float32, device=dev)
+            out = self._frames(xb, fb, self._x0, self.framed, self._f00, k, final, phases)
+            self.framed += k
+            if final:
+                self._reset()
+            else:
+                x_from, f_from = hna_keep_from(self.framed, self.span, self.hop)
+                if self._x is not None and x_from > self._x0:     # hop > Lmax: at most what has come
+                    d = min(x_from - self._x0, self._x.shape[1])
+                    self._x, self._x0 = self._x[:, d:], self._x0 + d
+                if self._f0 is not None and f_from > self._f00:
+                    d = min(f_from - self._f00, self._f0.shape[1])
+                    self._f0, self._f00 = self._f0[:, d:], self._f00 + d
+            return out
+
+    def _wrap(self, out):
+        if self.module.n_mag is None:
+            return AudioTensor(out, self.hop)
+        return AudioTensor(out[0], self.hop), AudioTensor(out[1], self.hop)
+
+    def push(self, x=None, f0=None):
+        """The next block of the waveform and / or the next f0 frames -> the frames that became final, as ``forward``
+        returns them."""
+        return self._wrap(self._run(x, f0, False, False))
+
+    def finish(self):
+        """The utterance has ended: the remaining frames; the stream starts a new utterance."""
+        return self._wrap(self._run(None, None, True, False))
+
+    def push_all(self, x=None, f0=None):
+        """``push`` with the plain tensors of the module's ``analyse``: ``(amplitudes, phases[, log_mag])``."""
+        return self._run(x, f0, False, True)
+
+    def finish_all(self):
+        return self._run(None, None, True, True)
+
+
 def open_analysis_stream(module, batch_size: int, **kw):
-    """The stream of an analysis module: ``F0TrackerStream`` (``lag=``), ``F0Stream`` or ``LPCAnalysisStream``
-    (``return_rc=``)."""
+    """The stream of an analysis module: ``F0TrackerStream`` (``lag=``), ``F0Stream``, ``LPCAnalysisStream``
+    (``return_rc=``) or ``HarmonicNoiseStream``."""
+    if isinstance(module, HarmonicNoiseAnalysis):
+        return HarmonicNoiseStream(module, batch_size, **kw)
     if isinstance(module, F0Tracker):
         return F0TrackerStream(module, batch_size, **kw)
     if isinstance(module, F0Analysis):

@@ -4,7 +4,7 @@
 // One launch, one workgroup of four waves per (b, f) frame; no workspace, no atomics, nothing shared between workgroups.
 //   0. Every thread forms the frame's constants in fp64 from the fp32 inputs: the window length L, omega = f0 / sr and the
 //      chirp from the neighbouring frames' f0.
-//   1. Staging: thread i (strided by 256) loads x[f hop + m], m = i - floor(L/2), zero outside [0, T), and stores the pair
+//   1. Staging: thread i (strided by 256) loads x[f hop + m], m = i - floor(L/2), zero outside the buffer, and stores the pair
 //      (w[i] x, Phi[i]) to LDS: the windowed sample and phi(m) mod 1 formed in fp64 and kept as a Q0.32 fraction of a cycle, so
 //      that k phi mod 1 is an exact 32-bit integer product for every harmonic k.
 //   2. Projection: a work item is (segment of the window, harmonic); consecutive lanes own consecutive harmonics of one segment,
@@ -19,6 +19,12 @@
 //   5. Epilogue: S_b = |.|^2 / sum w^2, the box smoothing with reflected ends in fp64, the log.
 // Every sum runs in a fixed order: bit-reproducible, and a row does not depend on its batch.  The sums of the window are the
 // closed forms sum w = L / 2 and sum w^2 = 3 L / 8 (1 / 2 at L = 2), exact for this Hann window on half-integer offsets.
+//
+// Two entries launch the kernel.  golf_harmonic_analysis_f32 hands it the whole utterance.  golf_harmonic_analysis_stream_f32
+// (analysis_stream.HarmonicNoiseStream) hands it windows of x and f0 with their positions in the utterance and a range of
+// frames: the kernel indexes both buffers relative to those positions and asks of each neighbouring f0 frame whether it lies
+// in the window, and nothing else differs -- a frame has the same bits from either entry.  The stream entry refuses, before
+// the launch, every window from which a frame could read outside its buffers.
 #include "common.h"
 #include "device_common.h"
 
@@ -41,7 +47,10 @@ struct HnaArgs {
     float* amp;
     float* phases;
     float* log_mag;
-    int G, T, F, K, n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth;
+    // where the buffers sit in the utterance: x holds samples [x_t0, x_end), f0 frames [f0_first, f0_end), and the launch
+    // computes frames [f_first, f_first + nf) of every row.  The one-shot entry: 0, T, 0, F, 0, F.
+    int64_t x_t0, x_end, f0_first, f0_end, f_first;
+    int G, nf, K, n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth;
     double sample_rate, eps;
 };
 
@@ -63,12 +72,13 @@ __global__ __launch_bounds__(HNA_THREADS) void harm_analysis_kernel(const HnaArg
     const int tid = threadIdx.x;
     const int64_t g64 = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
     if (g64 >= p.G) return;
-    const int g = (int)g64, b = g / p.F, f = g - b * p.F, K = p.K, n_mag = p.n_mag;
-    const float* xr = p.x + (int64_t)b * p.x_stride;
-    const float* fr = p.f0 + (int64_t)b * p.f0_stride;
+    const int g = (int)g64, b = g / p.nf, K = p.K, n_mag = p.n_mag;
+    const int64_t f = p.f_first + (g - b * p.nf);   // the frame's index in the utterance
+    const float* xr = p.x + (int64_t)b * p.x_stride;                          // xr[t - x_t0]: sample t, x_t0 <= t < x_end
+    const float* fr = p.f0 + (int64_t)b * p.f0_stride + (f - p.f0_first);    // fr[0]: this frame; fr[-1], fr[1]: its neighbours
 
     // ---- 0. frame constants -------------------------------------------------------------------------------------------------
-    const float f0c = fr[f];
+    const float f0c = fr[0];
     const bool voiced = f0c > 0.f;   // false for a NaN
     const double sr = p.sample_rate;
     double omega = 0.0, chirp = 0.0;
@@ -80,7 +90,7 @@ __global__ __launch_bounds__(HNA_THREADS) void harm_analysis_kernel(const HnaArg
         const double v = floor(n_per * sr / fd + 0.5);
         L = v >= 2.0 ? (v <= (double)p.max_window ? (int)v : p.max_window) : 2;   // 2 for a NaN (f0 = +inf)
         omega = fd / sr;
-        const float fp = f > 0 ? fr[f - 1] : 0.f, fn = f + 1 < p.F ? fr[f + 1] : 0.f;
+        const float fp = f - 1 >= p.f0_first ? fr[-1] : 0.f, fn = f + 1 < p.f0_end ? fr[1] : 0.f;   // the neighbours that exist
         const double hs = (double)p.hop * sr;
         if (fp > 0.f && fn > 0.f) chirp = ((double)fn - (double)fp) / (2.0 * hs);
         else if (fn > 0.f) chirp = ((double)fn - fd) / hs;
@@ -90,10 +100,10 @@ __global__ __launch_bounds__(HNA_THREADS) void harm_analysis_kernel(const HnaArg
     const double sum_w = 0.5 * L, sum_w2 = L == 2 ? 0.5 : 0.375 * L;
 
     // ---- 1. staging ---------------------------------------------------------------------------------------------------------
-    const int64_t t0 = (int64_t)f * p.hop - half;
+    const int64_t t0 = f * p.hop - half;
     for (int i = tid; i < L; i += HNA_THREADS) {
         const int64_t t = t0 + i;
-        const float xv = (t >= 0 && t < p.T) ? xr[t] : 0.f;
+        const float xv = (t >= p.x_t0 && t < p.x_end) ? xr[t - p.x_t0] : 0.f;   // x_t0 <= max(0, t0): below it only t < 0
         unsigned Phi = 0u;
         if (voiced) {
             const double m = (double)(i - half);
@@ -239,20 +249,9 @@ __global__ __launch_bounds__(HNA_THREADS) void harm_analysis_kernel(const HnaArg
     }
 }
 
-}  // namespace golf
-
-using namespace golf;
-
-extern "C" int golf_harmonic_analysis_f32(const float* x, int64_t x_stride, const float* f0, int64_t f0_stride,
-                                          float* amplitudes, float* phases, float* log_mag, int B, int T, int F, int K,
-                                          int n_mag, int hop, int periods, int min_window, int max_window,
-                                          int unvoiced_window, int smooth, double sample_rate, double eps, void* stream) {
-    const char* who = "harmonic_analysis";
-    if (B < 1 || T < 0 || F < 1) return fail(GOLF_EINVAL, "%s: bad size (B=%d T=%d F=%d)", who, B, T, F);
-    if ((!x && T > 0) || !f0 || !amplitudes)
-        return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p amplitudes=%p)", who, x, f0, amplitudes);
-    if (x_stride < T) return fail(GOLF_EINVAL, "%s: row stride of x %lld < T=%d", who, (long long)x_stride, T);
-    if (f0_stride < F) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < F=%d", who, (long long)f0_stride, F);
+// the limits both entries share; 0 or the code of the refusal
+static int hna_check_params(const char* who, int K, int n_mag, int hop, int periods, int min_window, int max_window,
+                            int unvoiced_window, int smooth, double sample_rate, double eps) {
     if (K < 1 || K > HNA_MAX_K) return fail(GOLF_EINVAL, "%s: K=%d harmonics, must be 1..%d", who, K, HNA_MAX_K);
     if (n_mag < 0 || n_mag == 1 || n_mag > HNA_MAX_NMAG)
         return fail(GOLF_EINVAL, "%s: n_mag=%d noise bins, must be 0 (none) or 2..%d", who, n_mag, HNA_MAX_NMAG);
@@ -269,17 +268,97 @@ extern "C" int golf_harmonic_analysis_f32(const float* x, int64_t x_stride, cons
         return fail(GOLF_EINVAL, "%s: smooth=%d must be 0..n_mag-1 (n_mag=%d)", who, smooth, n_mag);
     if (!(sample_rate > 0.0)) return fail(GOLF_EINVAL, "%s: sample_rate=%g must be positive", who, sample_rate);
     if (!(eps >= 0.0)) return fail(GOLF_EINVAL, "%s: eps=%g must be >= 0", who, eps);
-    if ((int64_t)B * F >= ((int64_t)1 << 31))
-        return fail(GOLF_EINVAL, "%s: B*F = %lld frames, must be < 2^31", who, (long long)B * F);
-    HnaArgs a;
-    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride;
-    a.amp = amplitudes, a.phases = phases, a.log_mag = log_mag;
-    a.G = B * F, a.T = T, a.F = F, a.K = K, a.n_mag = n_mag, a.hop = hop, a.periods = periods, a.min_window = min_window;
-    a.max_window = max_window, a.unvoiced_window = unvoiced_window, a.smooth = smooth;
-    a.sample_rate = sample_rate, a.eps = eps;
+    return GOLF_OK;
+}
+
+static int hna_launch(const HnaArgs& a, void* stream) {
     const int gx = a.G < HNA_GRID_X ? a.G : HNA_GRID_X;
     hipLaunchKernelGGL(harm_analysis_kernel, dim3((unsigned)gx, (unsigned)ceil_div(a.G, gx)), dim3(HNA_THREADS), 0,
                        (hipStream_t)stream, a);
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }
+
+}  // namespace golf
+
+using namespace golf;
+
+extern "C" int golf_harmonic_analysis_f32(const float* x, int64_t x_stride, const float* f0, int64_t f0_stride,
+                                          float* amplitudes, float* phases, float* log_mag, int B, int T, int F, int K,
+                                          int n_mag, int hop, int periods, int min_window, int max_window,
+                                          int unvoiced_window, int smooth, double sample_rate, double eps, void* stream) {
+    const char* who = "harmonic_analysis";
+    if (B < 1 || T < 0 || F < 1) return fail(GOLF_EINVAL, "%s: bad size (B=%d T=%d F=%d)", who, B, T, F);
+    if ((!x && T > 0) || !f0 || !amplitudes)
+        return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p amplitudes=%p)", who, x, f0, amplitudes);
+    if (x_stride < T) return fail(GOLF_EINVAL, "%s: row stride of x %lld < T=%d", who, (long long)x_stride, T);
+    if (f0_stride < F) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < F=%d", who, (long long)f0_stride, F);
+    if (int rc = hna_check_params(who, K, n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth, sample_rate,
+                                  eps))
+        return rc;
+    if ((int64_t)B * F >= ((int64_t)1 << 31))
+        return fail(GOLF_EINVAL, "%s: B*F = %lld frames, must be < 2^31", who, (long long)B * F);
+    HnaArgs a;
+    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride;
+    a.amp = amplitudes, a.phases = phases, a.log_mag = log_mag;
+    a.x_t0 = 0, a.x_end = T, a.f0_first = 0, a.f0_end = F, a.f_first = 0;   // the buffers are the whole utterance
+    a.G = B * F, a.nf = F, a.K = K, a.n_mag = n_mag, a.hop = hop, a.periods = periods, a.min_window = min_window;
+    a.max_window = max_window, a.unvoiced_window = unvoiced_window, a.smooth = smooth;
+    a.sample_rate = sample_rate, a.eps = eps;
+    return hna_launch(a, stream);
+}
+
+extern "C" int golf_harmonic_analysis_stream_f32(const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* f0,
+                                                 int64_t f0_stride, int64_t f0_first, int n_f0, float* amplitudes,
+                                                 float* phases, float* log_mag, int B, int64_t f_first, int n_frames,
+                                                 int last, int K, int n_mag, int hop, int periods, int min_window,
+                                                 int max_window, int unvoiced_window, int smooth, double sample_rate,
+                                                 double eps, void* stream) {
+    const char* who = "harmonic_analysis_stream";
+    const int64_t far = (int64_t)1 << 62;   // positions stay below it, so that no sum or product here or in the kernel wraps
+    if (B < 1 || n_x < 0 || n_f0 < 1 || n_frames < 1)
+        return fail(GOLF_EINVAL, "%s: bad size (B=%d n_x=%d n_f0=%d n_frames=%d)", who, B, n_x, n_f0, n_frames);
+    if ((!x && n_x > 0) || !f0 || !amplitudes)
+        return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p amplitudes=%p)", who, x, f0, amplitudes);
+    if (x_stride < n_x) return fail(GOLF_EINVAL, "%s: row stride of x %lld < n_x=%d", who, (long long)x_stride, n_x);
+    if (f0_stride < n_f0) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < n_f0=%d", who, (long long)f0_stride, n_f0);
+    if (int rc = hna_check_params(who, K, n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth, sample_rate,
+                                  eps))
+        return rc;
+    if ((int64_t)B * n_frames >= ((int64_t)1 << 31))
+        return fail(GOLF_EINVAL, "%s: B*n_frames = %lld frames, must be < 2^31", who, (long long)B * n_frames);
+    if (x_t0 < 0 || x_t0 > far) return fail(GOLF_EINVAL, "%s: x_t0=%lld must be 0..2^62", who, (long long)x_t0);
+    if (f0_first < 0 || f0_first > far)
+        return fail(GOLF_EINVAL, "%s: f0_first=%lld must be 0..2^62", who, (long long)f0_first);
+    if (f_first < 0 || f_first > far / hop - n_frames)
+        return fail(GOLF_EINVAL, "%s: f_first=%lld must be >= 0 with (f_first + n_frames) hop <= 2^62", who,
+                    (long long)f_first);
+    const int Lmax = max_window > unvoiced_window ? max_window : unvoiced_window;   // no frame's window is longer
+    const int64_t lo = f_first * hop - Lmax / 2, f_end = f_first + n_frames;
+    const int64_t x_end = x_t0 + n_x, f0_end = f0_first + n_f0;
+    if (x_t0 > (lo > 0 ? lo : 0))
+        return fail(GOLF_EINVAL, "%s: x_t0=%lld lies above sample %lld, where the window of frame f_first=%lld may start", who,
+                    (long long)x_t0, (long long)(lo > 0 ? lo : 0), (long long)f_first);
+    if (f0_first > (f_first > 0 ? f_first - 1 : 0))
+        return fail(GOLF_EINVAL, "%s: f0_first=%lld lies above frame %lld, the neighbour before f_first=%lld", who,
+                    (long long)f0_first, (long long)(f_first > 0 ? f_first - 1 : 0), (long long)f_first);
+    if (f_end > f0_end)
+        return fail(GOLF_EINVAL, "%s: n_f0=%d: f0 ends at frame %lld, before the last computed frame %lld", who, n_f0,
+                    (long long)f0_end, (long long)(f_end - 1));
+    if (!last && (f_end - 1) * hop + (Lmax - Lmax / 2) > x_end)
+        return fail(GOLF_EINVAL, "%s: n_x=%d: x ends at sample %lld, before the window of frame %lld may end (%lld) and "
+                    "last is not set", who, n_x, (long long)x_end, (long long)(f_end - 1),
+                    (long long)((f_end - 1) * hop + (Lmax - Lmax / 2)));
+    if (!last && f_end + 1 > f0_end)
+        return fail(GOLF_EINVAL, "%s: n_f0=%d: f0 ends at frame %lld, without the neighbour after frame %lld, and last is "
+                    "not set", who, n_f0, (long long)f0_end, (long long)(f_end - 1));
+    HnaArgs a;
+    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride;
+    a.amp = amplitudes, a.phases = phases, a.log_mag = log_mag;
+    a.x_t0 = x_t0, a.x_end = x_end, a.f0_first = f0_first, a.f0_end = f0_end, a.f_first = f_first;
+    a.G = B * n_frames, a.nf = n_frames, a.K = K, a.n_mag = n_mag, a.hop = hop, a.periods = periods;
+    a.min_window = min_window, a.max_window = max_window, a.unvoiced_window = unvoiced_window, a.smooth = smooth;
+    a.sample_rate = sample_rate, a.eps = eps;
+    return hna_launch(a, stream);
+}
+

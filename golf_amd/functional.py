@@ -16,7 +16,7 @@ import torch
 from . import _lib
 
 __all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "f0_viterbi_stream",
-           "f0_viterbi_stream_state", "harmonic_analysis", "lti_frames_ola",
+           "f0_viterbi_stream_state", "harmonic_analysis", "harmonic_analysis_stream", "lti_frames_ola",
            "glottal_osc",
            "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
@@ -854,49 +854,136 @@ def harmonic_analysis(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop
     ``min_window`` (default ``2 * hop``) samples, at most ``max_window`` <= 2048; an unvoiced frame's is ``unvoiced_window``
     (default ``4 * hop``) <= 2048.  ``smooth`` averages the noise power over ``2 * smooth + 1`` bins.  Harmonics at or above
     Nyquist are 0; x is 0 outside [0, T).  The outputs never require grad; strided rows are read in place."""
-    if x.dim() != 2:
-        raise _lib.GolfError(f"harmonic_analysis: x must be (B, T) (got {tuple(x.shape)})")
-    if f0.dim() != 2 or f0.shape[0] != x.shape[0]:
-        raise _lib.GolfError(f"harmonic_analysis: f0 must be (B, F) with the B of x (got {tuple(f0.shape)}, x {tuple(x.shape)})")
-    hop, K, periods, smooth = int(hop), int(num_harmonics), int(periods), int(smooth)
-    n_mag = 0 if n_mag is None else int(n_mag)
-    if hop < 1:
-        raise _lib.GolfError(f"harmonic_analysis: hop={hop} must be >= 1")
-    min_window = 2 * hop if min_window is None else int(min_window)
-    unvoiced_window = 4 * hop if unvoiced_window is None else int(unvoiced_window)
-    max_window = int(max_window)
-    if not sample_rate > 0:
-        raise _lib.GolfError(f"harmonic_analysis: sample_rate={sample_rate} must be positive")
-    if not 1 <= K <= HNA_MAX_HARMONICS:
-        raise _lib.GolfError(f"harmonic_analysis: num_harmonics={K} must be 1..{HNA_MAX_HARMONICS}")
-    if n_mag and not 2 <= n_mag <= HNA_MAX_NMAG:
-        raise _lib.GolfError(f"harmonic_analysis: n_mag={n_mag} must be 2..{HNA_MAX_NMAG} (or None)")
-    if periods < 2:
-        raise _lib.GolfError(f"harmonic_analysis: periods={periods} must be >= 2")
-    if not 2 <= max_window <= HNA_MAX_WINDOW or not 2 <= unvoiced_window <= HNA_MAX_WINDOW:
-        raise _lib.GolfError(f"harmonic_analysis: max_window={max_window} and unvoiced_window={unvoiced_window} must be "
-                             f"2..{HNA_MAX_WINDOW}")
-    if not 1 <= min_window <= max_window:
-        raise _lib.GolfError(f"harmonic_analysis: min_window={min_window} must be 1..max_window={max_window}")
-    if smooth < 0 or (n_mag and smooth >= n_mag):
-        raise _lib.GolfError(f"harmonic_analysis: smooth={smooth} must be 0..n_mag-1 (n_mag={n_mag})")
-    if not eps >= 0:
-        raise _lib.GolfError(f"harmonic_analysis: eps={eps} must be >= 0")
+    who = "harmonic_analysis"
+    hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth = _hna_params(
+        who, x, f0, sample_rate, hop, num_harmonics, n_mag, periods, min_window, max_window, unvoiced_window, smooth, eps)
     B, F = f0.shape
     if F < 1:
         raise _lib.GolfError(f"harmonic_analysis: f0 has {F} frames, must be >= 1")
     if B * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
         raise _lib.GolfError(f"harmonic_analysis: B*F = {B * F} frames, must be < 2^31")
     if B == 0:
-        _lib.require_device(x.float(), f0.float())
-        out = [torch.empty(0, F, K, dtype=torch.float32, device=x.device)]
-        if return_phases:
-            out.append(out[0].clone())
-        if n_mag:
-            out.append(torch.empty(0, F, n_mag, dtype=torch.float32, device=x.device))
+        out = _hna_empty(x, f0, F, K, n_mag, return_phases)
     else:
         out = _harmonic_analysis(x, f0, float(sample_rate), hop, K, n_mag, periods, min_window, max_window, unvoiced_window,
                                  smooth, float(eps), bool(return_phases))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def _hna_params(who, x, f0, sample_rate, hop, num_harmonics, n_mag, periods, min_window, max_window, unvoiced_window, smooth,
+                eps):
+    """The argument checks the two entries share; the integers with their defaults filled in."""
+    if x.dim() != 2:
+        raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
+    if f0.dim() != 2 or f0.shape[0] != x.shape[0]:
+        raise _lib.GolfError(f"{who}: f0 must be (B, F) with the B of x (got {tuple(f0.shape)}, x {tuple(x.shape)})")
+    hop, K, periods, smooth = int(hop), int(num_harmonics), int(periods), int(smooth)
+    n_mag = 0 if n_mag is None else int(n_mag)
+    if hop < 1:
+        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
+    min_window = 2 * hop if min_window is None else int(min_window)
+    unvoiced_window = 4 * hop if unvoiced_window is None else int(unvoiced_window)
+    max_window = int(max_window)
+    if not sample_rate > 0:
+        raise _lib.GolfError(f"{who}: sample_rate={sample_rate} must be positive")
+    if not 1 <= K <= HNA_MAX_HARMONICS:
+        raise _lib.GolfError(f"{who}: num_harmonics={K} must be 1..{HNA_MAX_HARMONICS}")
+    if n_mag and not 2 <= n_mag <= HNA_MAX_NMAG:
+        raise _lib.GolfError(f"{who}: n_mag={n_mag} must be 2..{HNA_MAX_NMAG} (or None)")
+    if periods < 2:
+        raise _lib.GolfError(f"{who}: periods={periods} must be >= 2")
+    if not 2 <= max_window <= HNA_MAX_WINDOW or not 2 <= unvoiced_window <= HNA_MAX_WINDOW:
+        raise _lib.GolfError(f"{who}: max_window={max_window} and unvoiced_window={unvoiced_window} must be "
+                             f"2..{HNA_MAX_WINDOW}")
+    if not 1 <= min_window <= max_window:
+        raise _lib.GolfError(f"{who}: min_window={min_window} must be 1..max_window={max_window}")
+    if smooth < 0 or (n_mag and smooth >= n_mag):
+        raise _lib.GolfError(f"{who}: smooth={smooth} must be 0..n_mag-1 (n_mag={n_mag})")
+    if not eps >= 0:
+        raise _lib.GolfError(f"{who}: eps={eps} must be >= 0")
+    return hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth
+
+
+def _hna_empty(x, f0, F, K, n_mag, return_phases):
+    _lib.require_device(x.float(), f0.float())
+    out = [torch.empty(x.shape[0], F, K, dtype=torch.float32, device=x.device)]
+    if return_phases:
+        out.append(out[0].clone())
+    if n_mag:
+        out.append(torch.empty(x.shape[0], F, n_mag, dtype=torch.float32, device=x.device))
+    return out
+
+
+@_amp_no_grad
+def _harmonic_analysis_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, sample_rate, hop, K, n_mag, periods, min_window,
+                              max_window, unvoiced_window, smooth, eps, want_phases):
+    _lib.require_device(x, f0)
+    lib = _lib.load()
+    x, f0 = _rows(x), _rows(f0)
+    B = x.shape[0]
+    amp = torch.empty(B, n_frames, K, dtype=torch.float32, device=x.device)
+    phases = torch.empty_like(amp) if want_phases else None
+    log_mag = torch.empty(B, n_frames, n_mag, dtype=torch.float32, device=x.device) if n_mag else None
+    rcode = lib.golf_harmonic_analysis_stream_f32(x.data_ptr(), x.stride(0), x_t0, x.shape[1], f0.data_ptr(), f0.stride(0),
+                                                  f0_first, f0.shape[1], amp.data_ptr(), _lib.ptr(phases), _lib.ptr(log_mag),
+                                                  B, f_first, n_frames, int(last), K, n_mag, hop, periods, min_window,
+                                                  max_window, unvoiced_window, smooth, sample_rate, eps, _lib.stream_ptr())
+    _lib.check(rcode, "golf_harmonic_analysis_stream_f32")
+    return tuple(t for t in (amp, phases, log_mag) if t is not None)
+
+
+def harmonic_analysis_stream(x: torch.Tensor, f0: torch.Tensor, x_t0: int, f_first: int, f0_first: int, n_frames: int,
+                             last: bool, sample_rate: float, hop: int, num_harmonics: int, n_mag: int = None,
+                             periods: int = 4, min_window: int = None, max_window: int = 2048, unvoiced_window: int = None,
+                             smooth: int = 0, eps: float = 1e-12, return_phases: bool = False):
+    """``harmonic_analysis`` at a position of a longer utterance (golf_harmonic_analysis_stream_f32, include/golf_amd.h):
+    frames ``f_first .. f_first + n_frames - 1`` from x (B, n_x), the utterance's samples ``[x_t0, x_t0 + n_x)``, and f0
+    (B, n_f0), its frames ``[f0_first, f0_first + n_f0)``; ``last``: the utterance ends with these buffers.  The results are
+    those of ``harmonic_analysis`` with ``n_frames`` in place of F, and each frame has the bits the one-shot call gives it.
+    With ``Lmax = max(max_window, unvoiced_window)`` the buffers must hold what the frames can read: ``0 <= x_t0 <=
+    max(0, f_first * hop - Lmax // 2)``, ``0 <= f0_first <= max(f_first - 1, 0)``, ``f_first + n_frames <= f0_first + n_f0``
+    and, unless ``last``, ``(f_first + n_frames - 1) * hop + Lmax - Lmax // 2 <= x_t0 + n_x`` and ``f_first + n_frames + 1 <=
+    f0_first + n_f0``; anything else raises ``GolfError`` before a launch.  ``n_frames = 0`` or an empty batch returns empty
+    results without a launch."""
+    who = "harmonic_analysis_stream"
+    hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth = _hna_params(
+        who, x, f0, sample_rate, hop, num_harmonics, n_mag, periods, min_window, max_window, unvoiced_window, smooth, eps)
+    x_t0, f_first, f0_first, n_frames, last = int(x_t0), int(f_first), int(f0_first), int(n_frames), bool(last)
+    (B, n_x), n_f0 = x.shape, f0.shape[1]
+    far = 2 ** 62
+    if n_frames < 0:
+        raise _lib.GolfError(f"{who}: n_frames={n_frames} must be >= 0")
+    if B * n_frames >= 2 ** 31:
+        raise _lib.GolfError(f"{who}: B*n_frames = {B * n_frames} frames, must be < 2^31")
+    if not 0 <= x_t0 <= far:
+        raise _lib.GolfError(f"{who}: x_t0={x_t0} must be 0..2^62")
+    if not 0 <= f0_first <= far:
+        raise _lib.GolfError(f"{who}: f0_first={f0_first} must be 0..2^62")
+    if not 0 <= f_first <= far // hop - n_frames:
+        raise _lib.GolfError(f"{who}: f_first={f_first} must be >= 0 with (f_first + n_frames) hop <= 2^62")
+    if n_frames:
+        Lmax = max(max_window, unvoiced_window)
+        lo, f_end, x_end, f0_end = max(f_first * hop - Lmax // 2, 0), f_first + n_frames, x_t0 + n_x, f0_first + n_f0
+        if x_t0 > lo:
+            raise _lib.GolfError(f"{who}: x_t0={x_t0} lies above sample {lo}, where the window of frame f_first={f_first} may "
+                                 "start")
+        if f0_first > max(f_first - 1, 0):
+            raise _lib.GolfError(f"{who}: f0_first={f0_first} lies above frame {max(f_first - 1, 0)}, the neighbour before "
+                                 f"f_first={f_first}")
+        if f_end > f0_end:
+            raise _lib.GolfError(f"{who}: f0 ends at frame {f0_end} (n_f0={n_f0}), before the last computed frame {f_end - 1}")
+        if not last and (f_end - 1) * hop + Lmax - Lmax // 2 > x_end:
+            raise _lib.GolfError(f"{who}: x ends at sample {x_end} (n_x={n_x}), before the window of frame {f_end - 1} may end "
+                                 f"({(f_end - 1) * hop + Lmax - Lmax // 2}), and last is not set")
+        if not last and f_end + 1 > f0_end:
+            raise _lib.GolfError(f"{who}: f0 ends at frame {f0_end} (n_f0={n_f0}), without the neighbour after frame "
+                                 f"{f_end - 1}, and last is not set")
+    if B == 0 or n_frames == 0:
+        out = _hna_empty(x, f0, n_frames, K, n_mag, return_phases)
+    else:
+        out = _harmonic_analysis_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, float(sample_rate), hop, K, n_mag,
+                                        periods, min_window, max_window, unvoiced_window, smooth, float(eps),
+                                        bool(return_phases))
     return out[0] if len(out) == 1 else tuple(out)
 
 

@@ -23,7 +23,7 @@ class HarmonicNoiseAnalysis(nn.Module):
     """(waveform, f0) -> ``(amplitudes, log_mag)`` at hop ``hop_length``, or ``amplitudes`` alone when ``n_mag`` is None, on
     the device (no parameters, no buffers, no gradient).  Frame f is centred on sample ``f * hop_length``, the decoders'
     frame grid; ``f0`` is in Hz with 0 for unvoiced frames, as ``F0Analysis`` gives it.  The remaining arguments are those of
-    ``functional.harmonic_analysis``."""
+    ``functional.harmonic_analysis``.  ``analysis_stream.HarmonicNoiseStream`` is the block-by-block form."""
 
     def __init__(self, sample_rate: float, hop_length: int, num_harmonics: int, n_mag: int = None, periods: int = 4,
                  min_window: int = None, max_window: int = 2048, unvoiced_window: int = None, smooth: int = 0,

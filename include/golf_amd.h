@@ -447,6 +447,36 @@ int golf_harmonic_analysis_f32(const float* x, int64_t x_stride, const float* f0
                                double eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same analysis at a position of a longer utterance (additive in ABI 6): frames f_first .. f_first + n_frames - 1 from
+ * windows of the inputs, for the block-by-block form (analysis_stream.HarmonicNoiseStream).  Frames, samples, steps 1-6, the
+ * limits and the properties are those of golf_harmonic_analysis_f32: it is the same kernel and the same launch shape, and a
+ * frame has the one-shot call's bits.  All positions are those of the utterance, int64 (a live stream may run for hours):
+ *   x (B, n_x), row stride x_stride: samples [x_t0, x_t0 + n_x).  x_t0 >= 0: the buffer never holds the zeros before sample 0;
+ *     a sample t < 0 reads as 0, and with last != 0 so does t >= x_t0 + n_x (the utterance ends there: T = x_t0 + n_x).
+ *   f0 (B, n_f0), row stride f0_stride: frames [f0_first, f0_first + n_f0), f0_first >= 0.  In step 3 the neighbour f - 1
+ *     exists iff f - 1 >= f0_first and the neighbour f + 1 iff f + 1 < f0_first + n_f0: the one-shot's f > 0 and f + 1 < F,
+ *     given the preconditions below, with F = f0_first + n_f0 when last != 0.
+ *   amplitudes (B, n_frames, K), phases (B, n_frames, K) or NULL, log_mag (B, n_frames, n_mag) or NULL: column j is frame
+ *     f_first + j.
+ * With Lmax = max(max_window, unvoiced_window), the longest window a frame can take, refused before any launch, all
+ * GOLF_EINVAL, each naming its argument -- a mistake in the caller's bookkeeping is an error, never another chirp or a
+ * window padded with zeros:
+ *   B < 1, n_x < 0, n_f0 < 1, n_frames < 1; x NULL with n_x > 0, f0 or amplitudes NULL; x_stride < n_x, f0_stride < n_f0;
+ *   the limits of golf_harmonic_analysis_f32 on K, n_mag, hop, periods, the windows, smooth, sample_rate and eps;
+ *   B*n_frames >= 2^31; x_t0, f0_first or (f_first + n_frames) hop outside 0..2^62;
+ *   x_t0 > max(0, f_first hop - floor(Lmax/2)): a frame could read below the buffer;
+ *   f0_first > max(f_first - 1, 0) or f_first + n_frames > f0_first + n_f0: f0 does not cover the frames and the neighbour
+ *     before the first;
+ *   with last == 0: (f_first + n_frames - 1) hop + Lmax - floor(Lmax/2) > x_t0 + n_x (a window could reach beyond the buffer)
+ *     or f_first + n_frames + 1 > f0_first + n_f0 (the last frame's next neighbour has not come).
+ * ------------------------------------------------------------------------------------------- */
+int golf_harmonic_analysis_stream_f32(const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* f0,
+                                      int64_t f0_stride, int64_t f0_first, int n_f0, float* amplitudes, float* phases,
+                                      float* log_mag, int B, int64_t f_first, int n_frames, int last, int K, int n_mag,
+                                      int hop, int periods, int min_window, int max_window, int unvoiced_window, int smooth,
+                                      double sample_rate, double eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a-4: frame-wise LTI all-pole + windowed overlap-add — GOLF-ff end filter.
  * Replaces LTVMinimumPhaseFilter.forward, models/filters.py:131-184 (pad, unfold, lpc_synthesis ->
  * torchaudio.functional.lfilter models/lpc.py:11-16, diagonal conv_transpose1d OLA, normalise).
