@@ -429,7 +429,11 @@ class LTVCepFilter(LTVFilterInterface):
     response rows (cepstra -> bins 0 .. n_fft/2, complex for "min", real for "zero") stay torch autograd.  CPU tensors,
     float64 and every other geometry run stock PyTorch on rocFFT, as does an instance with ``hip_frames = False``; both paths
     return hop*(frames-1) samples.  The reference takes the transforms from torchaudio (third party); the stock path makes
-    the same torch.stft / torch.istft calls directly.  No fused design kernel (cepstrum -> response) exists."""
+    the same torch.stft / torch.istft calls directly.  No fused design kernel (cepstrum -> response) exists.
+
+    ``envelope.SpectralEnvelopeAnalysis(sample_rate, hop_length, n_fft, filter_order)`` measures ``ceps`` on a recording with
+    a known f0 track, in this filter's convention (log|H|[k] = c_0 + 2 sum_{m>=1} c_m cos(2 pi k m / n_fft)), and its
+    ``synthesise`` runs the copy-synthesis through this module."""
 
     hip_frames = True   # False: torch.stft / torch.istft on the device too
 

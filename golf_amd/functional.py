@@ -16,7 +16,7 @@ import torch
 from . import _lib
 
 __all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "f0_viterbi_stream",
-           "f0_viterbi_stream_state", "harmonic_analysis", "harmonic_analysis_stream", "lti_frames_ola",
+           "f0_viterbi_stream_state", "harmonic_analysis", "harmonic_analysis_stream", "spectral_envelope", "lti_frames_ola",
            "glottal_osc",
            "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
@@ -984,6 +984,93 @@ def harmonic_analysis_stream(x: torch.Tensor, f0: torch.Tensor, x_t0: int, f_fir
         out = _harmonic_analysis_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, float(sample_rate), hop, K, n_mag,
                                         periods, min_window, max_window, unvoiced_window, smooth, float(eps),
                                         bool(return_phases))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+ENV_MIN_NFFT, ENV_MAX_NFFT = 64, 2048   # csrc/spec_envelope.hip ENV_MIN_N, ENV_MAX_N
+ENV_VOICED_OFFSET = 0.5 * math.log(2.0)
+
+
+@_amp_no_grad   # an analysis without a backward: inference only, like harmonic_analysis
+def _spectral_envelope(x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset,
+                       want_env):
+    _lib.require_device(x, f0)
+    lib = _lib.load()
+    x, f0 = _rows(x), _rows(f0)
+    (B, T), F = x.shape, f0.shape[1]
+    log_env = torch.empty(B, F, n_fft // 2 + 1, dtype=torch.float32, device=x.device) if want_env else None
+    ceps = torch.empty(B, F, n_ceps, dtype=torch.float32, device=x.device) if n_ceps else None   # not asked for: not written
+    rcode = lib.golf_spectral_envelope_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), f0.stride(0), _lib.ptr(log_env),
+                                           _lib.ptr(ceps), B, T, F, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil,
+                                           unvoiced_f0, q1, eps, voiced_offset, _lib.stream_ptr())
+    _lib.check(rcode, "golf_spectral_envelope_f32")
+    return tuple(t for t in (log_env, ceps) if t is not None)
+
+
+def spectral_envelope_defaults(sample_rate: float, n_fft: int = 1024):
+    """``(f0_floor, f0_ceil)`` that ``spectral_envelope`` takes when they are None: the lowest f0 whose three-period window
+    fits the transform, ``3 sr / (n_fft - 3)`` (70.5 Hz at 24 kHz and 1024), and ``sr / 12``."""
+    return 3.0 * sample_rate / (n_fft - 3), sample_rate / 12.0
+
+
+def spectral_envelope(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop: int, n_fft: int = 1024,
+                      n_ceps: int = None, f0_floor: float = None, f0_ceil: float = None, unvoiced_f0: float = 500.0,
+                      q1: float = -0.15, eps: float = 1e-12, voiced_offset: float = ENV_VOICED_OFFSET,
+                      return_log_env: bool = True):
+    """Pitch-adaptive spectral-envelope analysis (the definition is in include/golf_amd.h): x (B, T) and its f0 track (B, F)
+    in Hz, 0 where unvoiced, frame f centred on sample ``f * hop`` -> ``log_env (B, F, n_fft/2 + 1)``, the natural log of the
+    magnitude envelope on bins 0 .. n_fft/2 (``exp`` of it is what ``stft_filter_frames`` takes as response rows); with
+    ``n_ceps`` also ``ceps (B, F, n_ceps)`` in ``LTVCepFilter``'s convention (``n_ceps = filter_order + 1``); with
+    ``return_log_env=False`` ``ceps`` alone: ``log_env``, ``ceps`` or ``(log_env, ceps)``.  A frame's window is three periods
+    of its f0 clamped to [``f0_floor``, ``f0_ceil``] (defaults ``spectral_envelope_defaults``), of ``unvoiced_f0`` where
+    unvoiced; ``voiced_offset`` (default ``0.5 ln 2``) is added to the log magnitude of voiced frames, which makes them
+    return log|H| of the filter an ``AdditivePulseTrain`` went through.  x is 0 outside [0, T).  The outputs never require
+    grad; strided rows are read in place."""
+    who = "spectral_envelope"
+    if x.dim() != 2:
+        raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
+    if f0.dim() != 2 or f0.shape[0] != x.shape[0]:
+        raise _lib.GolfError(f"{who}: f0 must be (B, F) with the B of x (got {tuple(f0.shape)}, x {tuple(x.shape)})")
+    hop, n_fft = int(hop), int(n_fft)
+    n_ceps = 0 if n_ceps is None else int(n_ceps)
+    if hop < 1:
+        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
+    if not sample_rate > 0:
+        raise _lib.GolfError(f"{who}: sample_rate={sample_rate} must be positive")
+    if not ENV_MIN_NFFT <= n_fft <= ENV_MAX_NFFT or n_fft & (n_fft - 1):
+        raise _lib.GolfError(f"{who}: n_fft={n_fft} must be a power of two in [{ENV_MIN_NFFT}, {ENV_MAX_NFFT}]")
+    nb = n_fft // 2 + 1
+    if not 0 <= n_ceps <= nb:
+        raise _lib.GolfError(f"{who}: n_ceps={n_ceps} must be 1..{nb} (or None)")
+    if not n_ceps and not return_log_env:
+        raise _lib.GolfError(f"{who}: nothing to return: n_ceps is None and return_log_env is False")
+    lo, hi = spectral_envelope_defaults(float(sample_rate), n_fft)
+    f0_floor, f0_ceil = lo if f0_floor is None else float(f0_floor), hi if f0_ceil is None else float(f0_ceil)
+    if not f0_floor > 0 or not f0_floor <= f0_ceil:
+        raise _lib.GolfError(f"{who}: f0_floor={f0_floor} must be positive and <= f0_ceil={f0_ceil}")
+    if not f0_ceil <= sample_rate / 4:
+        raise _lib.GolfError(f"{who}: f0_ceil={f0_ceil} must be <= sample_rate/4 = {sample_rate / 4}")
+    if not f0_floor <= unvoiced_f0 <= f0_ceil:
+        raise _lib.GolfError(f"{who}: unvoiced_f0={unvoiced_f0} must lie in [f0_floor, f0_ceil] = [{f0_floor}, {f0_ceil}]")
+    if math.floor(1.5 * sample_rate / f0_floor + 0.5) > n_fft // 2 - 1:
+        raise _lib.GolfError(f"{who}: f0_floor={f0_floor}: the longest window, 2*"
+                             f"{math.floor(1.5 * sample_rate / f0_floor + 0.5)} + 1 samples, must fit n_fft={n_fft}")
+    if not eps > 0:
+        raise _lib.GolfError(f"{who}: eps={eps} must be positive")
+    if q1 != q1 or voiced_offset != voiced_offset:
+        raise _lib.GolfError(f"{who}: q1={q1} and voiced_offset={voiced_offset} must be numbers")
+    B, F = f0.shape
+    if F < 1:
+        raise _lib.GolfError(f"{who}: f0 has {F} frames, must be >= 1")
+    if B * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
+        raise _lib.GolfError(f"{who}: B*F = {B * F} frames, must be < 2^31")
+    if B == 0:
+        _lib.require_device(x.float(), f0.float())
+        out = [torch.empty(0, F, w, dtype=torch.float32, device=x.device)
+               for w, want in ((nb, return_log_env), (n_ceps, n_ceps)) if want]
+    else:
+        out = _spectral_envelope(x, f0, float(sample_rate), hop, n_fft, n_ceps, f0_floor, f0_ceil, float(unvoiced_f0),
+                                 float(q1), float(eps), float(voiced_offset), bool(return_log_env))
     return out[0] if len(out) == 1 else tuple(out)
 
 

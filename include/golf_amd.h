@@ -477,6 +477,49 @@ int golf_harmonic_analysis_stream_f32(const float* x, int64_t x_stride, int64_t 
                                       double sample_rate, double eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Spectral-envelope analysis (additive in ABI 6): (audio, f0) -> the control of the cepstral harmonic filter (LTVCepFilter:
+ * ceps) and the response rows of the STFT-domain frame filter (exp(log_env)), per frame on the grid of the analyses above
+ * (frame f is centred on sample f*hop).  It is a pitch-adaptive envelope estimator of the CheapTrick kind: an f0-sized
+ * window, a power spectrum, smoothing over 2 f0 / 3 and cepstral liftering; the reference has no such code.  The float64
+ * restatement in tests/env_ref.py is the checker.
+ * Inputs: x (B, T) fp32, unit inner stride, row stride x_stride, 0 outside [0, T); f0 (B, F) fp32 in Hz, row stride
+ * f0_stride, f0 <= 0 (or NaN) = unvoiced; n = n_fft, a power of two in [64, 2048], nb = n/2 + 1 bins; 0 <= n_ceps <= nb.
+ * Every frame constant is formed in fp64 from the fp32 inputs.  Frame f of row b:
+ *  1. effective f0: fe = min(max(f0, f0_floor), f0_ceil) if voiced, else unvoiced_f0.
+ *  2. window: hw = floor(1.5 sr / fe + 0.5), offsets m = -hw..hw, w(m) = 0.5 + 0.5 cos(2 pi m fe / (3 sr)), a Hann window
+ *     three periods wide;  xw(m) = w(m) x[f hop + m];  the DC the window sees is removed: xw <- xw - w (sum xw / sum w).
+ *  3. power spectrum: P[k] = |sum_m xw(m) exp(-2 pi j k m / n)|^2 / sum w^2, k = 0..n/2; white noise of variance v gives
+ *     E P = v, the unit of golf_harmonic_analysis_f32's S_b.
+ *  4. DC correction: r0 = fe n / sr bins;  for each k < r0, with u = r0 - k, the linear interpolation of P (as step 3 left
+ *     it) at the bin coordinate u, between floor(u) and min(floor(u) + 1, n/2), is added to P[k].
+ *  5. smoothing over 2 fe / 3: P is extended evenly about bin 0 and about bin n/2 and read as piecewise constant on the
+ *     cells [k - 1/2, k + 1/2);  Ps[k] is its mean over [k - r, k + r], r = r0 / 3, a cell partly inside counting by its
+ *     covered fraction.
+ *  6. L[k] = log(Ps[k] + eps);  c[q], q = 0..n/2, is the inverse real DFT of the even extension of L.
+ *  7. lifter: c'[q] = c[q] sinc(fe q / sr) ((1 - 2 q1) + 2 q1 cos(2 pi fe q / sr)), sinc(t) = sin(pi t) / (pi t), 1 at q = 0.
+ *  8. log_env[b,f,k] = 0.5 Re DFT(even extension of c')[k] + off, the natural log of the magnitude envelope;
+ *     ceps[b,f,m] = 0.5 c'[m] + (m == 0) off, m < n_ceps, in LTVCepFilter's convention log|H|[k] = c_0 + 2 sum_{m>=1} c_m
+ *     cos(2 pi k m / n): with n_ceps = nb its response is exp(log_env) up to rounding, a smaller n_ceps truncates further;
+ *     off = voiced_offset on voiced frames, 0 on unvoiced ones.  (The estimate is in white-noise units, and a pulse train
+ *     whose harmonics have the amplitude sqrt(2 f0 / sr) has half the power density of unit white noise: voiced_offset =
+ *     0.5 ln 2 makes a voiced frame return log|H| of the filter the pulse train went through.)
+ * Outputs: log_env (B, F, nb) and ceps (B, F, n_ceps), contiguous, either may be NULL, not both; written in full by one
+ * launch of one workgroup per frame, no workspace, no atomics, every sum in fp32 in a fixed order: bit-reproducible, and a
+ * row's result does not depend on its batch.  The three transforms are fp32 FFTs in LDS; step 5 sums each bin's cells
+ * directly (no difference of running sums); eps is rounded to fp32.  No call allocates or synchronises; graph-capturable.
+ * There is no gradient.  The window is at least three periods wide and must fit n, so r0 >= 3 and r >= 1 bin always.
+ * Refused before any launch, GOLF_EINVAL, each naming its argument: B < 1, T < 0, F < 1; f0 NULL, x NULL with T > 0; both
+ * outputs NULL, ceps with n_ceps == 0; x_stride < T, f0_stride < F; hop < 1; sample_rate <= 0; eps <= 0; n_ceps outside
+ * 0..nb; f0_floor <= 0, f0_floor > f0_ceil, f0_ceil > sr/4; unvoiced_f0 outside [f0_floor, f0_ceil]; q1 or voiced_offset
+ * NaN; floor(1.5 sr / f0_floor + 0.5) > n/2 - 1 (the longest window must fit the transform); B*F >= 2^31.  n_fft not a power
+ * of two or outside [64, 2048]: GOLF_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+int golf_spectral_envelope_f32(const float* x, int64_t x_stride, const float* f0, int64_t f0_stride, float* log_env,
+                               float* ceps, int B, int T, int F, int n_fft, int n_ceps, int hop, double sample_rate,
+                               double f0_floor, double f0_ceil, double unvoiced_f0, double q1, double eps,
+                               double voiced_offset, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a-4: frame-wise LTI all-pole + windowed overlap-add — GOLF-ff end filter.
  * Replaces LTVMinimumPhaseFilter.forward, models/filters.py:131-184 (pad, unfold, lpc_synthesis ->
  * torchaudio.functional.lfilter models/lpc.py:11-16, diagonal conv_transpose1d OLA, normalise).
