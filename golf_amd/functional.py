@@ -16,7 +16,8 @@ import torch
 from . import _lib
 
 __all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "f0_viterbi_stream",
-           "f0_viterbi_stream_state", "harmonic_analysis", "harmonic_analysis_stream", "spectral_envelope", "lti_frames_ola",
+           "f0_viterbi_stream_state", "harmonic_analysis", "harmonic_analysis_stream", "spectral_envelope", "glottal_plan", "glottal_match", "GlottalPlan",
+           "lti_frames_ola",
            "glottal_osc",
            "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
@@ -1072,6 +1073,109 @@ def spectral_envelope(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop
         out = _spectral_envelope(x, f0, float(sample_rate), hop, n_fft, n_ceps, f0_floor, f0_ceil, float(unvoiced_f0),
                                  float(q1), float(eps), float(voiced_offset), bool(return_log_env))
     return out[0] if len(out) == 1 else tuple(out)
+
+
+# ------------------------------------------------------------------------------------------------
+# glottal-source analysis: a residual's harmonics against the glottal-flow wavetable (csrc/glottal_match.hip)
+# ------------------------------------------------------------------------------------------------
+GLOTTAL_MAX_HARMONICS, GLOTTAL_MAX_ROWS = 256, 1024   # csrc/glottal_match.hip GM_MAX_H, GM_MAX_K
+GLOTTAL_MIN_NPHI, GLOTTAL_MAX_NPHI = 8, 4096          # GM_MIN_NPHI, GM_MAX_NPHI
+
+
+@dataclasses.dataclass(frozen=True)
+class GlottalPlan:
+    """What ``glottal_match`` needs of a table (K, L), built once per table by ``glottal_plan``: ``spectrum`` (K, H, 2),
+    ``norms`` (K, H) and ``cross`` (K - 1, H), fp32 and contiguous (include/golf_amd.h golf_glottal_match_f32)."""
+    spectrum: torch.Tensor
+    norms: torch.Tensor
+    cross: torch.Tensor
+
+
+def glottal_plan(table: torch.Tensor, num_harmonics: int) -> GlottalPlan:
+    """The plan of a wavetable (K, L) for ``num_harmonics`` harmonics, in stock torch on the table's device (a CPU table
+    gives a CPU plan): S[k,h] = 2 rfft(table[k])[h] / L for h = 1..H, zero for h > L/2, transformed in float64 and stored in
+    fp32; the prefix sums N[k,h] = sum_{i<=h} |S[k,i]|^2 and X[k,h] = sum_{i<=h} Re(S[k,i] conj(S[k+1,i])) of the stored S,
+    summed in float64 and stored in fp32.  Never requires grad."""
+    who = "glottal_plan"
+    H = int(num_harmonics)
+    if table.dim() != 2:
+        raise _lib.GolfError(f"{who}: the table must be (K, L) (got {tuple(table.shape)})")
+    K, L = table.shape
+    if not 2 <= K <= GLOTTAL_MAX_ROWS:
+        raise _lib.GolfError(f"{who}: the table has {K} rows, must be 2..{GLOTTAL_MAX_ROWS}")
+    if L < 2:
+        raise _lib.GolfError(f"{who}: the table has {L} points per row, must be >= 2")
+    if not 1 <= H <= GLOTTAL_MAX_HARMONICS:
+        raise _lib.GolfError(f"{who}: num_harmonics={H} must be 1..{GLOTTAL_MAX_HARMONICS}")
+    with torch.no_grad():
+        spec = torch.fft.rfft(table.detach().double(), dim=1)[:, 1:H + 1] * (2.0 / L)   # bins 1 .. min(H, L/2)
+        S = torch.zeros(K, H, 2, dtype=torch.float32, device=table.device)
+        S[:, :spec.shape[1]] = torch.view_as_real(spec).float()
+        Sd = S.double()
+        N = (Sd * Sd).sum(-1).cumsum(1).float()
+        X = (Sd[:-1] * Sd[1:]).sum(-1).cumsum(1).float()
+    return GlottalPlan(S.contiguous(), N.contiguous(), X.contiguous())
+
+
+@_amp_no_grad   # a search: no gradient reaches the harmonics
+def _glottal_match(amplitudes, phases, f0, S, N, X, sample_rate, n_phi):
+    _lib.require_device(amplitudes, phases, f0, S, N, X)
+    lib = _lib.load()
+    amplitudes, phases, f0 = amplitudes.contiguous(), phases.contiguous(), _rows(f0)
+    B, F, H = amplitudes.shape
+    w, theta, rho = (torch.empty(B, F, dtype=torch.float32, device=f0.device) for _ in range(3))
+    rcode = lib.golf_glottal_match_f32(amplitudes.data_ptr(), phases.data_ptr(), f0.data_ptr(), f0.stride(0), S.data_ptr(),
+                                       N.data_ptr(), X.data_ptr(), w.data_ptr(), theta.data_ptr(), rho.data_ptr(), B, F, H,
+                                       S.shape[0], n_phi, sample_rate, _lib.stream_ptr())
+    _lib.check(rcode, "golf_glottal_match_f32")
+    return w, theta, rho
+
+
+def glottal_match(amplitudes: torch.Tensor, phases: torch.Tensor, f0: torch.Tensor, plan: GlottalPlan, sample_rate: float,
+                  n_phi: int = 256):
+    """Match of a residual's harmonics against a glottal-flow wavetable (the definition is in include/golf_amd.h):
+    ``amplitudes``, ``phases`` (B, F, H) as ``harmonic_analysis(e, f0, ..., return_phases=True)`` gives them for the residual
+    ``e``, its f0 track (B, F) in Hz, 0 where unvoiced, and the table's ``glottal_plan`` for the same H -> ``(w, theta,
+    rho)``, (B, F) each: ``w`` in [0, 1] is the position on the table's rows, what ``glottal_osc`` takes as ``wsel`` (NaN in
+    an unvoiced frame, a frame without a harmonic below Nyquist and an all-zero frame), ``theta`` in [0, 1) the table phase
+    at the frame's centre and ``rho`` in [-1, 1] the normalised correlation of the frame with the chosen pulse (both 0 where
+    ``w`` is NaN).  ``n_phi`` phase shifts are searched, a power of two in [8, 4096].  The outputs never require grad;
+    strided ``f0`` rows are read in place."""
+    who = "glottal_match"
+    if not isinstance(plan, GlottalPlan):
+        raise _lib.GolfError(f"{who}: plan must be a GlottalPlan (glottal_plan(table, num_harmonics))")
+    if amplitudes.dim() != 3 or phases.shape != amplitudes.shape:
+        raise _lib.GolfError(f"{who}: amplitudes and phases must be (B, F, H) alike (got {tuple(amplitudes.shape)}, "
+                             f"{tuple(phases.shape)})")
+    B, F, H = amplitudes.shape
+    if f0.dim() != 2 or tuple(f0.shape) != (B, F):
+        raise _lib.GolfError(f"{who}: f0 must be (B, F) = {(B, F)} (got {tuple(f0.shape)})")
+    S, N, X = plan.spectrum, plan.norms, plan.cross
+    K = S.shape[0]
+    if S.dim() != 3 or S.shape[2] != 2 or tuple(N.shape) != (K, S.shape[1]) or tuple(X.shape) != (K - 1, S.shape[1]):
+        raise _lib.GolfError(f"{who}: the plan's shapes do not go together (spectrum {tuple(S.shape)}, norms "
+                             f"{tuple(N.shape)}, cross {tuple(X.shape)})")
+    if not all(t.is_contiguous() for t in (S, N, X)):
+        raise _lib.GolfError(f"{who}: the plan's tensors must be contiguous")
+    if S.shape[1] != H:
+        raise _lib.GolfError(f"{who}: the plan was built for {S.shape[1]} harmonics, the analysis has {H}")
+    n_phi = int(n_phi)
+    if not 1 <= H <= GLOTTAL_MAX_HARMONICS:
+        raise _lib.GolfError(f"{who}: H={H} harmonics, must be 1..{GLOTTAL_MAX_HARMONICS}")
+    if not 2 <= K <= GLOTTAL_MAX_ROWS:
+        raise _lib.GolfError(f"{who}: the plan has {K} rows, must be 2..{GLOTTAL_MAX_ROWS}")
+    if not GLOTTAL_MIN_NPHI <= n_phi <= GLOTTAL_MAX_NPHI or n_phi & (n_phi - 1):
+        raise _lib.GolfError(f"{who}: n_phi={n_phi} must be a power of two in [{GLOTTAL_MIN_NPHI}, {GLOTTAL_MAX_NPHI}]")
+    if not sample_rate > 0:
+        raise _lib.GolfError(f"{who}: sample_rate={sample_rate} must be positive")
+    if F < 1:
+        raise _lib.GolfError(f"{who}: f0 has {F} frames, must be >= 1")
+    if B * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
+        raise _lib.GolfError(f"{who}: B*F = {B * F} frames, must be < 2^31")
+    if B == 0:
+        _lib.require_device(amplitudes.float(), phases.float(), f0.float(), S, N, X)
+        return tuple(torch.empty(0, F, dtype=torch.float32, device=f0.device) for _ in range(3))
+    return _glottal_match(amplitudes, phases, f0, S, N, X, float(sample_rate), n_phi)
 
 
 # ------------------------------------------------------------------------------------------------

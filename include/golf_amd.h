@@ -520,6 +520,54 @@ int golf_spectral_envelope_f32(const float* x, int64_t x_stride, const float* f0
                                double voiced_offset, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Glottal-source analysis (additive in ABI 6): (the harmonics of a residual, f0) -> the control of the glottal-flow wavetable
+ * (IndexedGlottalFlowTable: table_select_weight), per frame on the grid of the analyses above.  The residual is the audio
+ * through golf_ltv_inverse_f32, divided by the gain; its harmonics are what golf_harmonic_analysis_f32 writes.  Each frame's
+ * harmonics are matched against every table row at every one of n_phi phase shifts, and the best row and shift are refined;
+ * the reference has no such code.  The float64 restatement in tests/glottal_ref.py is the checker.
+ * Inputs: amplitudes, phases (B, F, H) fp32, contiguous, exactly as golf_harmonic_analysis_f32 writes them (sine phases in
+ * cycles): c_h = amp_h exp(2 pi j (phase_h - 1/4)), h = 1..H;  f0 (B, F) fp32 in Hz, row stride f0_stride, f0 <= 0 (or NaN)
+ * = unvoiced.  The plan of a table (K, L), built once per table (functional.glottal_plan), contiguous fp32:
+ *   spectrum (K, H, 2): S[k,h] = 2 rfft(table[k])[h] / L (re, im), h = 1..H; entries with h > L/2 are zero;
+ *   norms (K, H):     N[k,h] = sum_{i<=h} |S[k,i]|^2;
+ *   cross (K-1, H):   X[k,h] = sum_{i<=h} Re(S[k,i] conj(S[k+1,i])), both summed in float64 over the fp32 S and rounded once.
+ * Every frame constant is formed in fp64 from the fp32 inputs.  Frame f of row b:
+ *  1. Hf = the number of h in 1..H with h (double)f0 / sr < 0.5, the harmonics golf_harmonic_analysis_f32 does not mute (the
+ *     same expression: the two kernels agree on it bit for bit);  E2 = sum_{h<=Hf} amp_h^2.
+ *  2. unvoiced, Hf = 0 or E2 = 0 (or NaN):  w = NaN, theta = 0, rho = 0, and nothing else is computed.
+ *  3. C[k,j] = sum_{h<=Hf} Re(c_h conj(S[k,h]) exp(-2 pi j h j / n_phi)), k = 0..K-1, j = 0..n_phi-1; the argument h j mod
+ *     n_phi is exact integer arithmetic.  rho[k,j] = C[k,j] / sqrt(N[k,Hf] E2); a row with N[k,Hf] = 0 scores 0.
+ *  4. (k*, j*) = argmax rho, the smaller k, then the smaller j, on exact ties.
+ *  5. phase: a parabola through rho[k*, j*-1], rho[k*, j*], rho[k*, j*+1], columns modulo n_phi;  d = its vertex, in
+ *     [-1/2, 1/2], 0 when the curvature is 0;  theta = frac((j* + d) / n_phi), in [0, 1).
+ *  6. row, at column j*, for each existing pair (k0, k0+1), k0 = k*-1 then k0 = k*: with c0 = C[k0,j*], c1 = C[k0+1,j*],
+ *     n00 = N[k0,Hf], n11 = N[k0+1,Hf], n01 = X[k0,Hf], the blend (1-p) row_k0 + p row_{k0+1} scores
+ *     ((1-p) c0 + p c1) / sqrt(((1-p)^2 n00 + 2 p (1-p) n01 + p^2 n11) E2) (0 when the bracket is not positive), largest at
+ *     p = u / (u + v), u = c1 n00 - c0 n01, v = c0 n11 - c1 n01, clipped to [0, 1], p = 0 when u + v = 0.  The better pair
+ *     is taken (the first on a tie), and (rho[k*,j*], k*) is kept unless a pair beats it strictly:
+ *     w = (k0 + p) / (K - 1), rho = that score.
+ * w is the inverse of the oscillator's row-pair interpolation (blend_tables), theta the oscillator's wrapped table phase at
+ * the frame's centre, rho in [-1, 1] a voicing / fit confidence (the normalised correlation of the frame's harmonics with
+ * the chosen pulse).
+ * Outputs: w, theta, rho (B, F) each, contiguous; each may be NULL, not all three; written in full by one launch of one
+ * workgroup per frame.  The K x n_phi scores never reach memory: a lane keeps 16 of them in registers and the argmax is
+ * reduced inside the workgroup.  The search of steps 3-4 has fp32 operands (c_h and exp(.) rounded to fp32, D = c_h conj(S)
+ * formed in fp32) and fp32 accumulation with fmaf in ascending h.  Neighbouring rows differ by 1e-4 .. 1e-3 in rho, so two
+ * neighbouring cells can tie within fp32 rounding, and steps 5-6 are discontinuous in (k*, j*); so the 5 x 5 scores around the
+ * fp32 winner are formed again in fp64 from the fp32 inputs (c_h unrounded), (k*, j*) is taken among the inner 3 x 3 by the
+ * rule of step 4, and steps 5-6 run in fp64 on those scores.  A frame then differs from a float64 computation of the whole
+ * definition by the rounding of its three outputs, unless two cells that are not neighbours tie within fp32 rounding.
+ * No workspace, no atomics, every sum in a fixed order: bit-reproducible, and a row's result does not depend on its batch.
+ * No call allocates or synchronises; graph-capturable.  There is no gradient.
+ * Refused before any launch, GOLF_EINVAL, each naming its argument: B < 1, F < 1; H outside 1..256; K outside 2..1024; any
+ * input or plan pointer NULL; all three outputs NULL; f0_stride < F; sample_rate <= 0; B*F >= 2^31.  n_phi not a power of
+ * two or outside [8, 4096]: GOLF_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+int golf_glottal_match_f32(const float* amplitudes, const float* phases, const float* f0, int64_t f0_stride,
+                           const float* spectrum, const float* norms, const float* cross, float* w, float* theta, float* rho,
+                           int B, int F, int H, int K, int n_phi, double sample_rate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a-4: frame-wise LTI all-pole + windowed overlap-add — GOLF-ff end filter.
  * Replaces LTVMinimumPhaseFilter.forward, models/filters.py:131-184 (pad, unfold, lpc_synthesis ->
  * torchaudio.functional.lfilter models/lpc.py:11-16, diagonal conv_transpose1d OLA, normalise).
