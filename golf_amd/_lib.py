@@ -20,7 +20,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_f64.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
-           "stft_filter.hip", "minphase_fir.hip", "lpc_analysis.hip", "f0_yin.hip", "f0_viterbi.hip", "f0_viterbi_stream.hip", "harm_analysis.hip", "spec_envelope.hip", "glottal_match.hip")
+           "stft_filter.hip", "minphase_fir.hip", "lpc_analysis.hip", "f0_yin.hip", "f0_viterbi.hip", "f0_viterbi_stream.hip", "harm_analysis.hip", "spec_envelope.hip", "glottal_match.hip", "lpc_residual.hip")
 
 _c_f32p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -70,6 +70,11 @@ SIGNATURES = {
     "golf_harmonic_analysis_stream_f32": (_int, [_c_f32p, _i64, _i64, _int, _c_f32p, _i64, _i64, _int, _c_f32p, _c_f32p,
                                                  _c_f32p, _int, _i64, _int, _int] + [_int] * 8 + [_dbl, _dbl, _vp]),
     "golf_spectral_envelope_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _c_f32p] + [_int] * 6 + [_dbl] * 7 + [_vp]),
+    "golf_spectral_envelope_stream_f32": (_int, [_c_f32p, _i64, _i64, _int, _c_f32p, _i64, _i64, _int, _c_f32p, _c_f32p, _int,
+                                                 _i64, _int, _int, _int, _int, _int] + [_dbl] * 7 + [_vp]),
+    "golf_ltv_residual_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 5 + [_vp]),
+    "golf_ltv_residual_stream_f32": (_int, [_c_f32p, _i64, _i64, _int, _c_f32p, _c_f32p, _i64, _int, _c_f32p, _i64, _int, _i64,
+                                            _int, _int, _int, _int, _vp]),
     "golf_glottal_match_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _i64] + [_c_f32p] * 6 + [_int] * 5 + [_dbl, _vp]),
     "golf_lti_frames_workspace_bytes": (_sz, [_int] * 6),
     "golf_lti_frames_ola_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64] + [_int] * 7

@@ -1,5 +1,6 @@
-"""Block-by-block analysis: the streaming counterparts of ``f0.F0Analysis``, ``f0.F0Tracker``, ``lpc.LPCAnalysis`` and
-``hna.HarmonicNoiseAnalysis``, for a live waveform that feeds a decoder stream (``stream.DecoderStream`` and its siblings take
+"""Block-by-block analysis: the streaming counterparts of ``f0.F0Analysis``, ``f0.F0Tracker``, ``lpc.LPCAnalysis``,
+``hna.HarmonicNoiseAnalysis``, ``envelope.SpectralEnvelopeAnalysis`` and ``glottal.GlottalSourceAnalysis`` (with its residual,
+``functional.ltv_residual``), for a live waveform that feeds a decoder stream (``stream.DecoderStream`` and its siblings take
 exactly these tracks).
 
 The protocol is the decoder streams': ``push(x)`` takes the next (B, n) block of the waveform, any n >= 0, and returns the
@@ -13,7 +14,9 @@ on where it sits in the row, which is why the result is exact.  Zeros stand befo
 definitions say.  The tracker is not frame-local: its candidates are, and the path through them is decided ``lag`` frames
 late by golf_f0_viterbi_stream_f32 (csrc/f0_viterbi_stream.hip), whose costs are carried from push to push.  The
 harmonic-plus-noise analysis takes two inputs, the waveform and its f0 track, which arrive at different paces
-(``HarmonicNoiseStream``): its frames are frame-local too, given the f0 of the neighbouring frames.
+(``HarmonicNoiseStream``): its frames are frame-local too, given the f0 of the neighbouring frames.  So are the frames of the
+spectral-envelope analysis (``SpectralEnvelopeStream``) and of the glottal-source analysis (``GlottalSourceStream``), and the
+samples of the residual it reads (``ResidualStream``): each runs its one-shot kernel at a position of the utterance.
 
 Inference only; one stream for the whole batch; ``push`` does no host-device synchronisation.
 """
@@ -24,12 +27,16 @@ import torch
 from . import _lib
 from . import functional as GF
 from .audiotensor import AudioTensor
+from .envelope import SpectralEnvelopeAnalysis
 from .f0 import F0Analysis, F0Tracker
+from .glottal import GlottalSourceAnalysis
 from .hna import HarmonicNoiseAnalysis
 from .lpc import LPCAnalysis
 
-__all__ = ["F0Stream", "F0TrackerStream", "LPCAnalysisStream", "HarmonicNoiseStream", "open_analysis_stream", "frames_open",
-           "frames_final", "frame_reach", "hna_frames_final", "hna_keep_from"]
+__all__ = ["F0Stream", "F0TrackerStream", "LPCAnalysisStream", "HarmonicNoiseStream", "SpectralEnvelopeStream",
+           "GlottalSourceStream", "ResidualStream", "open_analysis_stream", "frames_open", "frames_final", "frame_reach",
+           "hna_frames_final", "hna_keep_from", "env_frames_final", "env_keep_from", "res_samples_final", "res_samples_finish",
+           "res_keep_from"]
 
 
 # ---- geometry: host integers only ------------------------------------------------------------------------------------------
@@ -288,7 +295,102 @@ def hna_keep_from(next_frame: int, span: int, hop: int):
     return max(next_frame * hop - span // 2, 0), max(next_frame - 1, 0)
 
 
-class HarmonicNoiseStream:
+def _check_block(who: str, B: int, t, name: str, hop: int, ndim: int = 2) -> torch.Tensor:
+    """The checks every pushed block passes before its device is looked at: the hop of an AudioTensor, the shape, no
+    gradient; under autocast fp16 / bf16 become fp32."""
+    if isinstance(t, AudioTensor):
+        assert t.hop_length == hop, f"{name} must be at hop {hop} (got {t.hop_length})"
+        t = t.as_tensor()
+    if t.dim() != ndim or t.shape[0] != B:
+        raise ValueError(f"{who}.push: {name} of shape {tuple(t.shape)}; the stream has B={B}")
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise NotImplementedError(f"{who}: an input that requires grad (streaming is inference only) is not supported")
+    if torch.is_autocast_enabled() and t.is_floating_point():   # as the one-shot functions: fp16 / bf16 become fp32
+        t = t.float()
+    return t.detach()
+
+
+def _take_block(who: str, B: int, t, name: str, hop: int, ndim: int = 2) -> torch.Tensor:
+    t = _check_block(who, B, t, name, hop, ndim)
+    _lib.require_device(t)
+    return t
+
+
+def _cat(buf, t):
+    """``buf`` with the block ``t`` appended along dimension 1; no copy when either is empty."""
+    return t if buf is None or buf.shape[1] == 0 else (torch.cat([buf, t], 1) if t.shape[1] else buf)
+
+
+class _AudioF0Stream:
+    """The protocol and the two buffers of the streams that take a waveform and a frame-rate f0 track at two paces.  A
+    subclass names its module type, sets ``span`` and implements ``_total(final)``, the frames final so far; ``_keep()``, the
+    ``(sample, f0 frame)`` from which the open frames still read; and ``_frames(x, f0, x_t0, f_first, f0_first, k, last,
+    full)``, frames ``f_first .. f_first + k - 1`` from the buffers, which start at sample ``x_t0`` and frame ``f0_first``."""
+
+    _module_type = None
+    _audio = "x"   # the name of the waveform argument in messages
+
+    def __init__(self, module, batch_size: int):
+        if not isinstance(module, self._module_type):
+            a = self._module_type.__name__
+            raise TypeError(f"{self._who}: a{'n' if a[0] in 'AEIOU' else ''} {a} is needed (got {type(module).__name__})")
+        if int(batch_size) < 1:
+            raise ValueError(f"{self._who}: batch_size={batch_size}")
+        self.module, self.B, self.hop = module, int(batch_size), int(module.hop_length)
+        if self.hop < 1:
+            raise _lib.GolfError(f"{self._who}: hop={self.hop} must be >= 1")
+        self._x = self._f0 = None   # (B, m) samples [_x0, _x0 + m) and (B, n) f0 frames [_f00, _f00 + n) of the utterance
+        self._reset()
+
+    @property
+    def _who(self) -> str:
+        return type(self).__name__
+
+    def _reset(self) -> None:
+        self.pushed = 0        # samples of this utterance so far
+        self.f0_received = 0   # f0 frames of this utterance so far
+        self.framed = 0        # frames emitted so far
+        self._x0 = self._f00 = 0
+        self._x = None if self._x is None else self._x[:, :0]
+        self._f0 = None if self._f0 is None else self._f0[:, :0]
+
+    def _take(self, t, name: str, hop: int) -> torch.Tensor:
+        return _take_block(self._who, self.B, t, name, hop)
+
+    def _device(self):
+        for t in (self._x, self._f0):
+            if t is not None:
+                return t.device
+        return torch.device("cuda")
+
+    def _run(self, x, f0, final: bool, full: bool):
+        x = None if x is None else self._take(x, self._audio, 1)
+        f0 = None if f0 is None else self._take(f0, "f0", self.hop)
+        with torch.no_grad():
+            if x is not None:
+                self._x, self.pushed = _cat(self._x, x), self.pushed + x.shape[1]
+            if f0 is not None:
+                self._f0, self.f0_received = _cat(self._f0, f0), self.f0_received + f0.shape[1]
+            k = max(self._total(final) - self.framed, 0)
+            dev = self._device()
+            xb = self._x if self._x is not None else torch.empty(self.B, 0, dtype=torch.float32, device=dev)
+            fb = self._f0 if self._f0 is not None else torch.empty(self.B, 0, dtype=torch.float32, device=dev)
+            out = self._frames(xb, fb, self._x0, self.framed, self._f00, k, final, full)
+            self.framed += k
+            if final:
+                self._reset()
+            else:
+                x_from, f_from = self._keep()
+                if self._x is not None and x_from > self._x0:     # hop > span: at most what has come
+                    d = min(x_from - self._x0, self._x.shape[1])
+                    self._x, self._x0 = self._x[:, d:], self._x0 + d
+                if self._f0 is not None and f_from > self._f00:
+                    d = min(f_from - self._f00, self._f0.shape[1])
+                    self._f0, self._f00 = self._f0[:, d:], self._f00 + d
+            return out
+
+
+class HarmonicNoiseStream(_AudioF0Stream):
     """``hna.HarmonicNoiseAnalysis`` block by block, for live audio and its live f0 (an ``F0Stream`` or ``F0TrackerStream``
     on the same audio, which is ``lag`` frames late) feeding a ``stream.HarmonicPlusNoiseStream``.
 
@@ -313,25 +415,11 @@ class HarmonicNoiseStream:
 
     Inference only; one stream for the whole batch; ``push`` does no host-device synchronisation."""
 
-    def __init__(self, module: HarmonicNoiseAnalysis, batch_size: int):
-        if not isinstance(module, HarmonicNoiseAnalysis):
-            raise TypeError(f"HarmonicNoiseStream: a HarmonicNoiseAnalysis is needed (got {type(module).__name__})")
-        if int(batch_size) < 1:
-            raise ValueError(f"HarmonicNoiseStream: batch_size={batch_size}")
-        self.module, self.B, self.hop = module, int(batch_size), int(module.hop_length)
-        if self.hop < 1:
-            raise _lib.GolfError(f"HarmonicNoiseStream: hop={self.hop} must be >= 1")
-        self.span = max(int(module.max_window), int(module.unvoiced_window))   # Lmax
-        self._x = self._f0 = None   # (B, m) samples [_x0, _x0 + m) and (B, n) f0 frames [_f00, _f00 + n) of the utterance
-        self._reset()
+    _module_type = HarmonicNoiseAnalysis
 
-    def _reset(self) -> None:
-        self.pushed = 0        # samples of this utterance so far
-        self.f0_received = 0   # f0 frames of this utterance so far
-        self.framed = 0        # frames emitted so far
-        self._x0 = self._f00 = 0
-        self._x = None if self._x is None else self._x[:, :0]
-        self._f0 = None if self._f0 is None else self._f0[:, :0]
+    def __init__(self, module: HarmonicNoiseAnalysis, batch_size: int):
+        super().__init__(module, batch_size)
+        self.span = max(int(module.max_window), int(module.unvoiced_window))   # Lmax
 
     @property
     def latency(self) -> int:
@@ -339,29 +427,12 @@ class HarmonicNoiseStream:
         audio side.  The f0 side adds to it: the frame needs f0 frame ``f + 1`` (class docstring)."""
         return frame_reach(self.span, True)
 
-    def _take(self, t, name: str, hop: int) -> torch.Tensor:
-        if isinstance(t, AudioTensor):
-            assert t.hop_length == hop, f"{name} must be at hop {hop} (got {t.hop_length})"
-            t = t.as_tensor()
-        if t.dim() != 2 or t.shape[0] != self.B:
-            raise ValueError(f"HarmonicNoiseStream.push: {name} of shape {tuple(t.shape)}; the stream has B={self.B}")
-        if torch.is_grad_enabled() and t.requires_grad:
-            raise NotImplementedError("HarmonicNoiseStream: an input that requires grad (streaming is inference only) is not "
-                                      "supported")
-        if torch.is_autocast_enabled() and t.is_floating_point():   # as the one-shot functions: fp16 / bf16 become fp32
-            t = t.float()
-        _lib.require_device(t)
-        return t.detach()
+    def _total(self, final: bool) -> int:
+        # finish(): one frame per f0 frame, whatever the number of samples
+        return self.f0_received if final else hna_frames_final(self.pushed, self.f0_received, self.span, self.hop)
 
-    @staticmethod
-    def _cat(buf, t):
-        return t if buf is None or buf.shape[1] == 0 else (torch.cat([buf, t], 1) if t.shape[1] else buf)
-
-    def _device(self):
-        for t in (self._x, self._f0):
-            if t is not None:
-                return t.device
-        return torch.device("cuda")
+    def _keep(self):
+        return hna_keep_from(self.framed, self.span, self.hop)
 
     def _frames(self, x, f0, x_t0: int, f_first: int, f0_first: int, k: int, last: bool, phases: bool):
         """Frames ``f_first .. f_first + k - 1`` from the buffers, which start at sample ``x_t0`` and frame ``f0_first``."""
@@ -369,34 +440,6 @@ class HarmonicNoiseStream:
         return GF.harmonic_analysis_stream(x, f0, x_t0, f_first, f0_first, k, last, m.sample_rate, self.hop, m.num_harmonics,
                                            m.n_mag, m.periods, m.min_window, m.max_window, m.unvoiced_window, m.smooth, m.eps,
                                            return_phases=phases)
-
-    def _run(self, x, f0, final: bool, phases: bool):
-        x = None if x is None else self._take(x, "x", 1)
-        f0 = None if f0 is None else self._take(f0, "f0", self.hop)
-        with torch.no_grad():
-            if x is not None:
-                self._x, self.pushed = self._cat(self._x, x), self.pushed + x.shape[1]
-            if f0 is not None:
-                self._f0, self.f0_received = self._cat(self._f0, f0), self.f0_received + f0.shape[1]
-            # finish(): one frame per f0 frame, whatever the number of samples
-            total = self.f0_received if final else hna_frames_final(self.pushed, self.f0_received, self.span, self.hop)
-            k = max(total - self.framed, 0)
-            dev = self._device()
-            xb = self._x if self._x is not None else torch.empty(self.B, 0, dtype=torch.float32, device=dev)
-            fb = self._f0 if self._f0 is not None else torch.empty(self.B, 0, dtype=torch.float32, device=dev)
-            out = self._frames(xb, fb, self._x0, self.framed, self._f00, k, final, phases)
-            self.framed += k
-            if final:
-                self._reset()
-            else:
-                x_from, f_from = hna_keep_from(self.framed, self.span, self.hop)
-                if self._x is not None and x_from > self._x0:     # hop > Lmax: at most what has come
-                    d = min(x_from - self._x0, self._x.shape[1])
-                    self._x, self._x0 = self._x[:, d:], self._x0 + d
-                if self._f0 is not None and f_from > self._f00:
-                    d = min(f_from - self._f00, self._f0.shape[1])
-                    self._f0, self._f00 = self._f0[:, d:], self._f00 + d
-            return out
 
     def _wrap(self, out):
         if self.module.n_mag is None:
@@ -420,9 +463,294 @@ class HarmonicNoiseStream:
         return self._run(None, None, True, True)
 
 
+# ---- spectral-envelope analysis: a frame reads its own f0 and the samples within hwmax of its centre ------------------------
+def env_frames_final(pushed: int, f0_received: int, hwmax: int, hop: int) -> int:
+    """Frames of a ``SpectralEnvelopeStream``, counted from index 0, that are final after ``pushed`` samples and
+    ``f0_received`` f0 frames: frame f is final once the longest window it can take (``hwmax`` samples either side of
+    ``f * hop``) lies below ``pushed``, that is ``f * hop + hwmax + 1 <= pushed``, and its own f0 frame has come."""
+    room = pushed - hwmax - 1
+    return min(room // hop + 1 if room >= 0 else 0, f0_received)
+
+
+def env_keep_from(next_frame: int, hwmax: int, hop: int):
+    """``(sample, f0 frame)`` from which a ``SpectralEnvelopeStream`` whose next frame is ``next_frame`` keeps its inputs."""
+    return max(next_frame * hop - hwmax, 0), next_frame
+
+
+class SpectralEnvelopeStream(_AudioF0Stream):
+    """``envelope.SpectralEnvelopeAnalysis`` block by block, for live audio and its live f0 (an ``F0Stream`` or
+    ``F0TrackerStream`` on the same audio) feeding the NHV decoder's stream (``stream.HarmonicPlusNoiseStream`` takes ``ceps``
+    as the harmonic filter's control).
+
+    ``push(x=None, f0=None)`` takes the next (B, n) block of the waveform and / or the next (B, k) f0 frames, as
+    ``HarmonicNoiseStream`` does, and returns the frames that became final as ``forward`` returns them: ``ceps``, an
+    AudioTensor at ``hop_length`` (``log_env`` when ``filter_order`` is None), possibly with zero frames.  ``finish()`` ends
+    the utterance -- one frame per f0 frame received, T = the samples received -- returns the rest and starts a new utterance.
+    ``push_all`` / ``finish_all`` return the plain ``(log_env, ceps)`` of ``analyse``.  Everything pushed out plus
+    ``finish()`` is ``torch.equal`` to the module on the concatenated ``(x, f0)``, for any cuts and any interleaving.
+
+    Frame f is final once ``pushed >= f * hop + hwmax + 1``, ``hwmax = floor(1.5 sr / f0_floor + 0.5)`` the half window of
+    the lowest f0, and f0 frame f has come (``env_frames_final``): the worst case over the batch, so ``push`` never reads the
+    device.  The frames run through golf_spectral_envelope_stream_f32, the one-shot kernel at a position of the utterance.
+    Samples before ``next_frame * hop - hwmax`` and f0 frames before ``next_frame`` are dropped (``env_keep_from``).
+
+    ``latency = hwmax + 1`` samples beyond a frame's own time (512 at 24 kHz and n_fft 1024); behind an f0 stream the whole
+    figure is ``max(latency, the f0 stream's latency)``.
+
+    Inference only; one stream for the whole batch; ``push`` does no host-device synchronisation."""
+
+    _module_type = SpectralEnvelopeAnalysis
+
+    def __init__(self, module: SpectralEnvelopeAnalysis, batch_size: int):
+        super().__init__(module, batch_size)
+        self.hwmax = GF.spectral_envelope_hwmax(module.sample_rate, module.n_fft, module.f0_floor)
+        self.span = 2 * self.hwmax + 1   # the longest window
+
+    @property
+    def latency(self) -> int:
+        """The smallest number of samples beyond a frame's own time ``f * hop`` after which it can have been emitted."""
+        return self.hwmax + 1
+
+    def _total(self, final: bool) -> int:
+        return self.f0_received if final else env_frames_final(self.pushed, self.f0_received, self.hwmax, self.hop)
+
+    def _keep(self):
+        return env_keep_from(self.framed, self.hwmax, self.hop)
+
+    def _frames(self, x, f0, x_t0: int, f_first: int, f0_first: int, k: int, last: bool, full: bool):
+        """``full``: ``(log_env, ceps)`` as ``analyse``; else what ``forward`` returns, one tensor."""
+        m = self.module
+        order = m.filter_order
+        n_ceps = (m.n_fft // 2 + 1 if order is None else order + 1) if full else (None if order is None else order + 1)
+        return GF.spectral_envelope_stream(x, f0, x_t0, f_first, f0_first, k, last, m.sample_rate, self.hop, m.n_fft, n_ceps,
+                                           m.f0_floor, m.f0_ceil, m.unvoiced_f0, m.q1, m.eps, m.voiced_offset,
+                                           return_log_env=full or order is None)
+
+    def push(self, x=None, f0=None) -> AudioTensor:
+        """The next block of the waveform and / or the next f0 frames -> the frames that became final, as ``forward``
+        returns them."""
+        return AudioTensor(self._run(x, f0, False, False), self.hop)
+
+    def finish(self) -> AudioTensor:
+        """The utterance has ended: the remaining frames; the stream starts a new utterance."""
+        return AudioTensor(self._run(None, None, True, False), self.hop)
+
+    def push_all(self, x=None, f0=None):
+        """``push`` with the plain tensors of the module's ``analyse``: ``(log_env, ceps)``."""
+        return self._run(x, f0, False, True)
+
+    def finish_all(self):
+        return self._run(None, None, True, True)
+
+
+# ---- glottal-source analysis: the harmonic analysis of the residual, then the match against the table ------------------------
+class GlottalSourceStream(_AudioF0Stream):
+    """``glottal.GlottalSourceAnalysis`` block by block, for a live residual (a ``ResidualStream``) and its live f0.
+
+    ``push(e=None, f0=None)`` takes the next (B, n) block of the residual and / or the next (B, k) f0 frames and returns
+    ``w``, the ``table_select_weight`` of the frames that became final, an AudioTensor at ``hop_length``, possibly with zero
+    frames; ``finish()`` ends the utterance (one frame per f0 frame received) and starts a new one; ``push_all`` /
+    ``finish_all`` return the plain ``(w, theta, rho)`` of ``analyse``.  Everything pushed out plus ``finish()`` is
+    ``torch.equal`` to ``analyse`` on the concatenated ``(e, f0)``, for any cuts and any interleaving.
+
+    The bookkeeping is ``HarmonicNoiseStream``'s (``hna_frames_final``, ``hna_keep_from``) with the window arguments that
+    ``analyse`` passes to ``functional.harmonic_analysis``: no noise bins, phases on, ``unvoiced_window = 4 hop``.  The frames
+    that became final go through ``functional.harmonic_analysis_stream`` and then ``functional.glottal_match`` with the f0
+    values of exactly those frames; a frame without an estimate takes ``unvoiced_weight``.  A push that completes no frame
+    launches nothing.  ``latency`` is the audio side, as ``HarmonicNoiseStream.latency``; the frame also needs f0 frame
+    ``f + 1``.
+
+    Inference only; one stream for the whole batch; ``push`` does no host-device synchronisation."""
+
+    _module_type = GlottalSourceAnalysis
+    _audio = "e"
+
+    def __init__(self, module: GlottalSourceAnalysis, batch_size: int):
+        super().__init__(module, batch_size)
+        self.unvoiced_window = 4 * self.hop   # what harmonic_analysis takes when analyse leaves it out
+        self.span = max(int(module.max_window), self.unvoiced_window)
+
+    @property
+    def latency(self) -> int:
+        """The smallest number of samples beyond a frame's own time ``f * hop`` after which it can have been emitted: the
+        residual's side.  The frame also needs f0 frame ``f + 1``."""
+        return frame_reach(self.span, True)
+
+    def _total(self, final: bool) -> int:
+        return self.f0_received if final else hna_frames_final(self.pushed, self.f0_received, self.span, self.hop)
+
+    def _keep(self):
+        return hna_keep_from(self.framed, self.span, self.hop)
+
+    def _frames(self, e, f0, x_t0: int, f_first: int, f0_first: int, k: int, last: bool, full: bool):
+        m = self.module
+        if k == 0:
+            z = torch.empty(self.B, 0, dtype=torch.float32, device=self._device())
+            return z, z.clone(), z.clone()
+        amp, ph = GF.harmonic_analysis_stream(e, f0, x_t0, f_first, f0_first, k, last, m.sample_rate, self.hop,
+                                              m.num_harmonics, None, m.periods, m.min_window, m.max_window,
+                                              self.unvoiced_window, return_phases=True)
+        own = f0[:, f_first - f0_first:f_first - f0_first + k]
+        w, theta, rho = GF.glottal_match(amp, ph, own, m.plan(), m.sample_rate, m.n_phi)
+        return torch.nan_to_num_(w, nan=float(m.unvoiced_weight)), theta, rho
+
+    def push(self, e=None, f0=None) -> AudioTensor:
+        """The next block of the residual and / or the next f0 frames -> ``w`` of the frames that became final."""
+        return AudioTensor(self._run(e, f0, False, True)[0], self.hop)
+
+    def finish(self) -> AudioTensor:
+        """The utterance has ended: the remaining frames; the stream starts a new utterance."""
+        return AudioTensor(self._run(None, None, True, True)[0], self.hop)
+
+    def push_all(self, e=None, f0=None):
+        """``push`` with the plain tensors of the module's ``analyse``: ``(w, theta, rho)``."""
+        return self._run(e, f0, False, True)
+
+    def finish_all(self):
+        return self._run(None, None, True, True)
+
+
+# ---- the residual: samples out, from samples and frame-rate filter parameters ------------------------------------------------
+def res_samples_final(pushed: int, frames_received: int, hop: int) -> int:
+    """Samples of a ``ResidualStream``, counted from 0, that are final after ``pushed`` samples and ``frames_received``
+    frames of ``(gain, a)``: sample t is final once it has come and so has frame ``t // hop + 1``, the far end of its
+    interpolation.  (The last sample of an utterance, which the clamp ``f <= F - 2`` serves, is known only at ``finish()``.)"""
+    return min(pushed, max(frames_received - 1, 0) * hop)
+
+
+def res_samples_finish(pushed: int, frames_received: int, hop: int) -> int:
+    """Samples of the whole utterance: ``min(T, (F - 1) hop + 1)``, 0 without a frame."""
+    return min(pushed, (frames_received - 1) * hop + 1) if frames_received >= 1 else 0
+
+
+def res_keep_from(emitted: int, frames_received: int, order: int, hop: int):
+    """``(sample, frame)`` from which a ``ResidualStream`` that has emitted ``emitted`` samples keeps its inputs: the first
+    tap of the next sample, and that sample's frame ``emitted // hop`` -- but never above frame ``frames_received - 2``,
+    which the next sample reads through the clamp if the utterance ends with the frames received so far."""
+    return max(emitted - order, 0), max(min(emitted // hop, frames_received - 2), 0)
+
+
+class ResidualStream:
+    """``functional.ltv_residual`` (``GlottalSourceAnalysis.residual_fused``) block by block: live audio and the live
+    ``(gain, a)`` of an ``LPCAnalysisStream`` on the same audio -> the excitation estimate that a ``GlottalSourceStream``
+    reads.
+
+    ``push(x=None, gain=None, a=None)`` takes the next (B, n) block of the waveform and / or the next frames ``gain`` (B, k)
+    and ``a`` (B, k, lpc_order), which come together (tensors, or AudioTensors at ``hop_length``), and returns ``e`` (B, m),
+    the samples that became final, possibly none.  ``finish()`` ends the utterance -- F = the frames received, T = the samples
+    received, ``T' = min(T, (F - 1) hop + 1)`` samples in all, none when F = 0 -- returns the rest and starts a new utterance.
+    ``push_all`` / ``finish_all`` are the same calls (the result is a plain tensor either way).  Everything pushed out plus
+    ``finish()`` is ``torch.equal`` to ``functional.ltv_residual`` on the concatenated inputs, for any cuts and any
+    interleaving.
+
+    Sample t is final once it has come and so has frame ``t // hop + 1`` (``res_samples_final``); sample ``(F - 1) hop``, which
+    the one-shot interpolates through the clamp ``f <= F - 2``, comes out at ``finish()`` only.  The samples run through
+    golf_ltv_residual_stream_f32, the one-shot kernel at a position of the utterance.  Samples before ``emitted - lpc_order``
+    and frames before ``min(emitted // hop, frames received - 2)`` are dropped (``res_keep_from``); whichever input runs
+    ahead is held until the other catches up.
+
+    ``latency``: sample t needs frame ``t // hop + 1``, whose own time is at most ``hop`` samples after t; with frames that
+    arrive d samples after their own time, ``e[t]`` can have been emitted ``hop + d`` samples after t.  ``latency`` is the
+    stream's own part, ``hop``; behind a centred ``LPCAnalysisStream`` d is half its window, 240 + 480 = 720 samples at the
+    recipe (hop 240, window 960).
+
+    Inference only; one stream for the whole batch; ``push`` does no host-device synchronisation."""
+
+    def __init__(self, hop_length: int, lpc_order: int, batch_size: int):
+        if int(batch_size) < 1:
+            raise ValueError(f"ResidualStream: batch_size={batch_size}")
+        self.hop, self.order, self.B = int(hop_length), int(lpc_order), int(batch_size)
+        if self.hop < 1:
+            raise _lib.GolfError(f"ResidualStream: hop={self.hop} must be >= 1")
+        if not 1 <= self.order <= GF.RES_MAX_ORDER:
+            raise _lib.GolfError(f"ResidualStream: lpc_order={self.order} must be 1..{GF.RES_MAX_ORDER}")
+        self._x = self._g = self._a = None   # samples [_x0, ...) and frames [_fr0, ...) of the utterance
+        self._reset()
+
+    def _reset(self) -> None:
+        self.pushed = 0            # samples of this utterance so far
+        self.frames_received = 0   # frames of (gain, a) of this utterance so far
+        self.emitted = 0           # samples emitted so far
+        self._x0 = self._fr0 = 0
+        self._x = None if self._x is None else self._x[:, :0]
+        self._g = None if self._g is None else self._g[:, :0]
+        self._a = None if self._a is None else self._a[:, :0]
+
+    @property
+    def latency(self) -> int:
+        """The stream's own part of the delay of ``e[t]`` behind sample t: ``hop`` samples, to the own time of frame
+        ``t // hop + 1``; the delay d of the frames behind their own time adds to it (class docstring)."""
+        return self.hop
+
+    def _device(self):
+        for t in (self._x, self._g):
+            if t is not None:
+                return t.device
+        return torch.device("cuda")
+
+    def _require_device(self, *tensors) -> None:
+        _lib.require_device(*tensors)
+
+    def _samples(self, x, gain, a, x_t0: int, fr_first: int, t_first: int, n: int, last: bool):
+        """Samples ``t_first .. t_first + n - 1`` from the buffers, which start at sample ``x_t0`` and frame ``fr_first``."""
+        if n == 0:
+            return torch.empty(self.B, 0, dtype=torch.float32, device=self._device())
+        return GF.ltv_residual_stream(x, gain, a, x_t0, fr_first, t_first, n, last, self.hop)
+
+    def _run(self, x, gain, a, final: bool):
+        if (gain is None) != (a is None):
+            raise ValueError("ResidualStream.push: gain and a come together")
+        who = "ResidualStream"
+        x = None if x is None else _check_block(who, self.B, x, "x", 1)
+        if gain is not None:
+            gain, a = _check_block(who, self.B, gain, "gain", self.hop), _check_block(who, self.B, a, "a", self.hop, 3)
+            if a.shape[1] != gain.shape[1] or a.shape[2] != self.order:
+                raise ValueError(f"ResidualStream.push: a of shape {tuple(a.shape)} beside gain {tuple(gain.shape)}; the "
+                                 f"stream has lpc_order={self.order}")
+        self._require_device(x, gain, a)
+        with torch.no_grad():
+            if x is not None:
+                self._x, self.pushed = _cat(self._x, x), self.pushed + x.shape[1]
+            if gain is not None:
+                self._g, self._a = _cat(self._g, gain), _cat(self._a, a)
+                self.frames_received += gain.shape[1]
+            total = res_samples_finish(self.pushed, self.frames_received, self.hop) if final else \
+                res_samples_final(self.pushed, self.frames_received, self.hop)
+            n = max(total - self.emitted, 0)
+            out = self._samples(self._x, self._g, self._a, self._x0, self._fr0, self.emitted, n, final)
+            self.emitted += n
+            if final:
+                self._reset()
+            else:
+                x_from, f_from = res_keep_from(self.emitted, self.frames_received, self.order, self.hop)
+                if self._x is not None and x_from > self._x0:
+                    d = min(x_from - self._x0, self._x.shape[1])
+                    self._x, self._x0 = self._x[:, d:], self._x0 + d
+                if self._g is not None and f_from > self._fr0:
+                    d = min(f_from - self._fr0, self._g.shape[1])
+                    self._g, self._a, self._fr0 = self._g[:, d:], self._a[:, d:], self._fr0 + d
+            return out
+
+    def push(self, x=None, gain=None, a=None) -> torch.Tensor:
+        """The next block of the waveform and / or the next frames of ``(gain, a)`` -> the samples of ``e`` that became
+        final."""
+        return self._run(x, gain, a, False)
+
+    def finish(self) -> torch.Tensor:
+        """The utterance has ended: the remaining samples; the stream starts a new utterance."""
+        return self._run(None, None, None, True)
+
+    push_all, finish_all = push, finish
+
+
 def open_analysis_stream(module, batch_size: int, **kw):
     """The stream of an analysis module: ``F0TrackerStream`` (``lag=``), ``F0Stream``, ``LPCAnalysisStream``
-    (``return_rc=``) or ``HarmonicNoiseStream``."""
+    (``return_rc=``), ``HarmonicNoiseStream``, ``SpectralEnvelopeStream`` or ``GlottalSourceStream``.  (``ResidualStream``
+    has no module: it is opened with the hop and the order.)"""
+    if isinstance(module, SpectralEnvelopeAnalysis):
+        return SpectralEnvelopeStream(module, batch_size, **kw)
+    if isinstance(module, GlottalSourceAnalysis):
+        return GlottalSourceStream(module, batch_size, **kw)
     if isinstance(module, HarmonicNoiseAnalysis):
         return HarmonicNoiseStream(module, batch_size, **kw)
     if isinstance(module, F0Tracker):

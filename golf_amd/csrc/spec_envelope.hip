@@ -17,7 +17,8 @@
 //      between them whole -- never a difference of running sums.
 //   5. log, transform, lifter (sinc and cosine arguments reduced in fp64), ceps out, transform, log_env out.
 // Every sum runs in a fixed order: bit-reproducible, and a row does not depend on its batch.  The kernel is a function of
-// utterance positions (t = f hop + m in int64), so a block-by-block twin needs only the position of its buffer.
+// utterance positions (t = f hop + m in int64), so the block-by-block twin (golf_spectral_envelope_stream_f32) is this kernel
+// with the positions of its buffers: samples [x_t0, x_end), f0 frames from f0_first, output column j = frame f_first + j.
 #include "common.h"
 
 namespace golf {
@@ -34,8 +35,10 @@ struct EnvArgs {
     int64_t f0_stride;
     float* log_env;
     float* ceps;
-    int64_t T;
-    int G, F, n, log2n, n_ceps, hop;
+    int64_t x_t0, x_end;    // the buffer holds samples [x_t0, x_end); a sample outside it reads 0 (the entries say which may)
+    int64_t f0_first;       // column 0 of the f0 buffer is frame f0_first
+    int64_t f_first;        // column 0 of the outputs is frame f_first
+    int G, F, n, log2n, n_ceps, hop;   // F: frames of this launch
     double sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, voiced_offset;
     float eps;
 };
@@ -74,12 +77,13 @@ __global__ __launch_bounds__(ENV_THREADS) void spec_envelope_kernel(const EnvArg
     const int tid = threadIdx.x;
     const int64_t g64 = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
     if (g64 >= p.G) return;
-    const int g = (int)g64, b = g / p.F, f = g - b * p.F;
+    const int g = (int)g64, b = g / p.F;
+    const int64_t f = p.f_first + (g - b * p.F);
     const int n = p.n, nh = n >> 1, log2n = p.log2n;
     const float* xr = p.x + (int64_t)b * p.x_stride;
 
     // ---- 0. frame constants -------------------------------------------------------------------------------------------------
-    const float f0v = p.f0[(int64_t)b * p.f0_stride + f];
+    const float f0v = p.f0[(int64_t)b * p.f0_stride + (f - p.f0_first)];
     const bool voiced = f0v > 0.f;   // false for a NaN
     const double sr = p.sample_rate;
     const double fe = voiced ? fmin(fmax((double)f0v, p.f0_floor), p.f0_ceil) : p.unvoiced_f0;
@@ -95,11 +99,11 @@ __global__ __launch_bounds__(ENV_THREADS) void spec_envelope_kernel(const EnvArg
         tw[j] = make_float2(c, -s);
     }
     const int L = 2 * hw + 1;
-    const int64_t t0 = (int64_t)f * p.hop - hw;
+    const int64_t t0 = f * p.hop - hw;
     float sw = 0.f, sw2 = 0.f, sxw = 0.f;
     for (int i = tid; i < L; i += ENV_THREADS) {
         const int64_t t = t0 + i;
-        const float xv = (t >= 0 && t < p.T) ? xr[t] : 0.f;
+        const float xv = (t >= p.x_t0 && t < p.x_end) ? xr[t - p.x_t0] : 0.f;
         const double arg = (double)(i - hw) * fe / (3.0 * sr);   // cycles, within about [-1/2, 1/2]
         const float ch = cospif((float)arg);
         const float w = ch * ch;   // 0.5 + 0.5 cos(2 pi arg) = cos^2(pi arg): no cancellation where the window is small
@@ -189,21 +193,9 @@ __global__ __launch_bounds__(ENV_THREADS) void spec_envelope_kernel(const EnvArg
     for (int k = tid; k <= nh; k += ENV_THREADS) p.log_env[(int64_t)g * (nh + 1) + k] = fmaf(0.5f, E[k].x, off);
 }
 
-}  // namespace golf
-
-using namespace golf;
-
-extern "C" int golf_spectral_envelope_f32(const float* x, int64_t x_stride, const float* f0, int64_t f0_stride,
-                                          float* log_env, float* ceps, int B, int T, int F, int n_fft, int n_ceps, int hop,
-                                          double sample_rate, double f0_floor, double f0_ceil, double unvoiced_f0, double q1,
-                                          double eps, double voiced_offset, void* stream) {
-    const char* who = "spectral_envelope";
-    if (B < 1 || T < 0 || F < 1) return fail(GOLF_EINVAL, "%s: bad size (B=%d T=%d F=%d)", who, B, T, F);
-    if ((!x && T > 0) || !f0) return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p)", who, x, f0);
-    if (!log_env && !ceps) return fail(GOLF_EINVAL, "%s: null pointer: log_env and ceps are both NULL", who);
-    if (ceps && n_ceps == 0) return fail(GOLF_EINVAL, "%s: n_ceps=0 with a ceps output", who);
-    if (x_stride < T) return fail(GOLF_EINVAL, "%s: row stride of x %lld < T=%d", who, (long long)x_stride, T);
-    if (f0_stride < F) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < F=%d", who, (long long)f0_stride, F);
+// the limits both entries share, after their own checks of sizes, pointers and strides; 0 or the code of the refusal
+static int env_check_params(const char* who, int n_fft, int n_ceps, int hop, double sample_rate, double f0_floor,
+                            double f0_ceil, double unvoiced_f0, double q1, double eps, double voiced_offset) {
     if (n_fft < ENV_MIN_N || n_fft > ENV_MAX_N || (n_fft & (n_fft - 1)))
         return fail(GOLF_EUNSUPPORTED, "%s: n_fft=%d must be a power of two in [%d, %d]", who, n_fft, ENV_MIN_N, ENV_MAX_N);
     const int nb = n_fft / 2 + 1;
@@ -224,11 +216,12 @@ extern "C" int golf_spectral_envelope_f32(const float* x, int64_t x_stride, cons
     if (!(hw_max <= (double)(n_fft / 2 - 1)))
         return fail(GOLF_EINVAL, "%s: f0_floor=%g: the longest window, 2*%.0f + 1 samples, must fit n_fft=%d (half width <= %d)",
                     who, f0_floor, hw_max, n_fft, n_fft / 2 - 1);
-    if ((int64_t)B * F >= ((int64_t)1 << 31))
-        return fail(GOLF_EINVAL, "%s: B*F = %lld frames, must be < 2^31", who, (long long)B * F);
-    EnvArgs a;
-    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride, a.log_env = log_env, a.ceps = ceps;
-    a.T = T, a.G = B * F, a.F = F, a.n = n_fft, a.log2n = __builtin_ctz((unsigned)n_fft), a.n_ceps = n_ceps, a.hop = hop;
+    return GOLF_OK;
+}
+
+static int env_launch(EnvArgs& a, int B, int n_frames, int n_fft, int n_ceps, int hop, double sample_rate, double f0_floor,
+                      double f0_ceil, double unvoiced_f0, double q1, double eps, double voiced_offset, void* stream) {
+    a.G = B * n_frames, a.F = n_frames, a.n = n_fft, a.log2n = __builtin_ctz((unsigned)n_fft), a.n_ceps = n_ceps, a.hop = hop;
     a.sample_rate = sample_rate, a.f0_floor = f0_floor, a.f0_ceil = f0_ceil, a.unvoiced_f0 = unvoiced_f0, a.q1 = q1;
     a.voiced_offset = voiced_offset, a.eps = (float)eps;
     const int gx = a.G < ENV_GRID_X ? a.G : ENV_GRID_X;
@@ -237,3 +230,76 @@ extern "C" int golf_spectral_envelope_f32(const float* x, int64_t x_stride, cons
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }
+
+}  // namespace golf
+
+using namespace golf;
+
+extern "C" int golf_spectral_envelope_f32(const float* x, int64_t x_stride, const float* f0, int64_t f0_stride,
+                                          float* log_env, float* ceps, int B, int T, int F, int n_fft, int n_ceps, int hop,
+                                          double sample_rate, double f0_floor, double f0_ceil, double unvoiced_f0, double q1,
+                                          double eps, double voiced_offset, void* stream) {
+    const char* who = "spectral_envelope";
+    if (B < 1 || T < 0 || F < 1) return fail(GOLF_EINVAL, "%s: bad size (B=%d T=%d F=%d)", who, B, T, F);
+    if ((!x && T > 0) || !f0) return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p)", who, x, f0);
+    if (!log_env && !ceps) return fail(GOLF_EINVAL, "%s: null pointer: log_env and ceps are both NULL", who);
+    if (ceps && n_ceps == 0) return fail(GOLF_EINVAL, "%s: n_ceps=0 with a ceps output", who);
+    if (x_stride < T) return fail(GOLF_EINVAL, "%s: row stride of x %lld < T=%d", who, (long long)x_stride, T);
+    if (f0_stride < F) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < F=%d", who, (long long)f0_stride, F);
+    if (int rc = env_check_params(who, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset))
+        return rc;
+    if ((int64_t)B * F >= ((int64_t)1 << 31))
+        return fail(GOLF_EINVAL, "%s: B*F = %lld frames, must be < 2^31", who, (long long)B * F);
+    EnvArgs a;
+    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride, a.log_env = log_env, a.ceps = ceps;
+    a.x_t0 = 0, a.x_end = T, a.f0_first = 0, a.f_first = 0;   // the buffers are the whole utterance
+    return env_launch(a, B, F, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset, stream);
+}
+
+extern "C" int golf_spectral_envelope_stream_f32(const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* f0,
+                                                 int64_t f0_stride, int64_t f0_first, int n_f0, float* log_env, float* ceps,
+                                                 int B, int64_t f_first, int n_frames, int last, int n_fft, int n_ceps, int hop,
+                                                 double sample_rate, double f0_floor, double f0_ceil, double unvoiced_f0,
+                                                 double q1, double eps, double voiced_offset, void* stream) {
+    const char* who = "spectral_envelope_stream";
+    const int64_t far = (int64_t)1 << 62;   // positions stay below it, so that no sum or product here or in the kernel wraps
+    if (B < 1 || n_x < 0 || n_f0 < 1 || n_frames < 1)
+        return fail(GOLF_EINVAL, "%s: bad size (B=%d n_x=%d n_f0=%d n_frames=%d)", who, B, n_x, n_f0, n_frames);
+    if ((!x && n_x > 0) || !f0) return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p)", who, x, f0);
+    if (!log_env && !ceps) return fail(GOLF_EINVAL, "%s: null pointer: log_env and ceps are both NULL", who);
+    if (ceps && n_ceps == 0) return fail(GOLF_EINVAL, "%s: n_ceps=0 with a ceps output", who);
+    if (x_stride < n_x) return fail(GOLF_EINVAL, "%s: row stride of x %lld < n_x=%d", who, (long long)x_stride, n_x);
+    if (f0_stride < n_f0) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < n_f0=%d", who, (long long)f0_stride, n_f0);
+    if (int rc = env_check_params(who, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset))
+        return rc;
+    if ((int64_t)B * n_frames >= ((int64_t)1 << 31))
+        return fail(GOLF_EINVAL, "%s: B*n_frames = %lld frames, must be < 2^31", who, (long long)B * n_frames);
+    if (x_t0 < 0 || x_t0 > far) return fail(GOLF_EINVAL, "%s: x_t0=%lld must be 0..2^62", who, (long long)x_t0);
+    if (f0_first < 0 || f0_first > far)
+        return fail(GOLF_EINVAL, "%s: f0_first=%lld must be 0..2^62", who, (long long)f0_first);
+    if (f_first < 0 || f_first > far / hop - n_frames)
+        return fail(GOLF_EINVAL, "%s: f_first=%lld must be >= 0 with (f_first + n_frames) hop <= 2^62", who,
+                    (long long)f_first);
+    const int64_t hwmax = (int64_t)floor(1.5 * sample_rate / f0_floor + 0.5);   // <= n_fft/2 - 1: no frame's half window is longer
+    const int64_t lo = f_first * hop - hwmax > 0 ? f_first * hop - hwmax : 0, f_end = f_first + n_frames;
+    const int64_t x_end = x_t0 + n_x, f0_end = f0_first + n_f0;
+    if (x_t0 > lo)
+        return fail(GOLF_EINVAL, "%s: x_t0=%lld lies above sample %lld, where the window of frame f_first=%lld may start", who,
+                    (long long)x_t0, (long long)lo, (long long)f_first);
+    if (f0_first > f_first)
+        return fail(GOLF_EINVAL, "%s: f0_first=%lld lies above the first computed frame f_first=%lld", who, (long long)f0_first,
+                    (long long)f_first);
+    if (f_end > f0_end)
+        return fail(GOLF_EINVAL, "%s: n_f0=%d: f0 ends at frame %lld, before the last computed frame %lld", who, n_f0,
+                    (long long)f0_end, (long long)(f_end - 1));
+    if (!last && (f_end - 1) * hop + hwmax + 1 > x_end)
+        return fail(GOLF_EINVAL, "%s: n_x=%d: x ends at sample %lld, before the window of frame %lld may end (%lld) and "
+                    "last is not set", who, n_x, (long long)x_end, (long long)(f_end - 1),
+                    (long long)((f_end - 1) * hop + hwmax + 1));
+    EnvArgs a;
+    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride, a.log_env = log_env, a.ceps = ceps;
+    a.x_t0 = x_t0, a.x_end = x_end, a.f0_first = f0_first, a.f_first = f_first;
+    return env_launch(a, B, n_frames, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset,
+                      stream);
+}
+

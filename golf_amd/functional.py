@@ -16,7 +16,7 @@ import torch
 from . import _lib
 
 __all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "f0_viterbi_stream",
-           "f0_viterbi_stream_state", "harmonic_analysis", "harmonic_analysis_stream", "spectral_envelope", "glottal_plan", "glottal_match", "GlottalPlan",
+           "f0_viterbi_stream_state", "harmonic_analysis", "harmonic_analysis_stream", "spectral_envelope", "spectral_envelope_stream", "ltv_residual", "ltv_residual_stream", "glottal_plan", "glottal_match", "GlottalPlan",
            "lti_frames_ola",
            "glottal_osc",
            "ss_output_length", "ss_has_f64", "ff_output_length", "osc_lengths", "PreparedTransitions", "ss_status",
@@ -650,6 +650,116 @@ def ltv_inverse(y: torch.Tensor, a: torch.Tensor, hop: int) -> torch.Tensor:
     return _LTVInverse.apply(y, a, hop)
 
 
+RES_MAX_ORDER = 64   # csrc/lpc_residual.hip RES_MAX_M
+
+
+@_amp_no_grad   # an analysis without a backward (ltv_inverse has one): inference only, like harmonic_analysis
+def _ltv_residual_stream(x, gain, a, x_t0, fr_first, t_first, n_out, last, hop, one_shot):
+    _lib.require_device(x, gain, a)
+    lib = _lib.load()
+    x, gain, a = _rows(x), gain.contiguous(), a.contiguous()
+    B, M = x.shape[0], a.shape[2]
+    e = torch.empty(B, n_out, dtype=torch.float32, device=x.device)
+    if one_shot:
+        rc = lib.golf_ltv_residual_f32(x.data_ptr(), x.stride(0), gain.data_ptr(), a.data_ptr(), e.data_ptr(), e.stride(0), B,
+                                       x.shape[1], a.shape[1], M, hop, _lib.stream_ptr())
+        _lib.check(rc, "golf_ltv_residual_f32")
+    else:
+        rc = lib.golf_ltv_residual_stream_f32(x.data_ptr(), x.stride(0), x_t0, x.shape[1], gain.data_ptr(), a.data_ptr(),
+                                              fr_first, a.shape[1], e.data_ptr(), e.stride(0), B, t_first, n_out, int(last),
+                                              M, hop, _lib.stream_ptr())
+        _lib.check(rc, "golf_ltv_residual_stream_f32")
+    return e
+
+
+def _residual_shapes(who, x, gain, a, hop):
+    if x.dim() != 2:
+        raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
+    if gain.dim() != 2 or gain.shape[0] != x.shape[0]:
+        raise _lib.GolfError(f"{who}: gain must be (B, F) with the B of x (got {tuple(gain.shape)}, x {tuple(x.shape)})")
+    if a.dim() != 3 or a.shape[:2] != gain.shape:
+        raise _lib.GolfError(f"{who}: a must be (B, F, M) with the (B, F) of gain (got {tuple(a.shape)}, gain "
+                             f"{tuple(gain.shape)})")
+    hop, M = int(hop), a.shape[2]
+    if hop < 1:
+        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
+    if not 1 <= M <= RES_MAX_ORDER:
+        raise _lib.GolfError(f"{who}: M={M} (the last dimension of a) must be 1..{RES_MAX_ORDER}")
+    return hop, M
+
+
+def _residual_empty(x, gain, a, n_out):
+    _lib.require_device(x.float(), gain.float(), a.float())
+    return torch.empty(x.shape[0], n_out, dtype=torch.float32, device=x.device)
+
+
+def ltv_residual(x: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: int) -> torch.Tensor:
+    """The decoder's excitation estimate in one launch (golf_ltv_residual_f32, the definition is in include/golf_amd.h):
+    x (B, T), ``gain`` (B, F) and ``a`` (B, F, M) as ``lpc_analysis`` gives them -> ``e (B, T')``, ``T' = min(T, (F - 1) hop +
+    1)``: ``ltv_inverse(x, a, hop)``, bit for bit, divided by the gain interpolated as ``fmaf(w, gain[f+1] - gain[f],
+    gain[f])`` with ``w = (t - f hop) / hop``, one correctly rounded division each.  Every sample is a function of its
+    position alone, which is what ``ltv_residual_stream`` is exact against; it differs from ``ltv_inverse(x, a, hop) /
+    linear_upsample(gain, hop)`` only in how the gain is interpolated.  No gradient: the output never requires grad;
+    strided rows of x are read in place.  An empty batch or an empty x returns an empty result without a launch."""
+    who = "ltv_residual"
+    hop, M = _residual_shapes(who, x, gain, a, hop)
+    (B, T), F = x.shape, gain.shape[1]
+    if F < 1:
+        raise _lib.GolfError(f"{who}: gain has {F} frames, must be >= 1")
+    n_out = ss_output_length(T, F, hop)
+    if B == 0 or n_out == 0:
+        return _residual_empty(x, gain, a, n_out)
+    return _ltv_residual_stream(x, gain, a, 0, 0, 0, n_out, True, hop, True)
+
+
+def ltv_residual_stream(x: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, x_t0: int, fr_first: int, t_first: int,
+                        n_out: int, last: bool, hop: int) -> torch.Tensor:
+    """``ltv_residual`` at a position of a longer utterance (golf_ltv_residual_stream_f32, include/golf_amd.h): samples
+    ``t_first .. t_first + n_out - 1`` from x (B, n_x), the utterance's samples ``[x_t0, x_t0 + n_x)``, and ``gain`` (B, n_fr),
+    ``a`` (B, n_fr, M), its frames ``[fr_first, fr_first + n_fr)``; ``last``: the utterance ends with these frames (F =
+    ``fr_first + n_fr``).  Each sample has the bits the one-shot call gives it.  The buffers must hold what the samples read:
+    ``0 <= x_t0 <= max(0, t_first - M)``, ``x_t0 + n_x >= t_first + n_out``, ``fr_first <=`` the frame of ``t_first`` and,
+    unless ``last``, ``(t_first + n_out - 1) // hop + 1 < fr_first + n_fr``; with ``last``, ``t_first + n_out <= (F - 1) hop +
+    1``; anything else raises ``GolfError`` before a launch.  ``n_out = 0`` or an empty batch returns an empty result without
+    a launch."""
+    who = "ltv_residual_stream"
+    hop, M = _residual_shapes(who, x, gain, a, hop)
+    x_t0, fr_first, t_first, n_out, last = int(x_t0), int(fr_first), int(t_first), int(n_out), bool(last)
+    (B, n_x), n_fr = x.shape, gain.shape[1]
+    far = 2 ** 62
+    if n_out < 0:
+        raise _lib.GolfError(f"{who}: n_out={n_out} must be >= 0")
+    if not 0 <= x_t0 <= far:
+        raise _lib.GolfError(f"{who}: x_t0={x_t0} must be 0..2^62")
+    if not 0 <= t_first <= far:
+        raise _lib.GolfError(f"{who}: t_first={t_first} must be 0..2^62")
+    if not 0 <= fr_first <= far // hop - n_fr:
+        raise _lib.GolfError(f"{who}: fr_first={fr_first} must be >= 0 with (fr_first + n_fr) hop <= 2^62")
+    if n_out:
+        t_end, x_end, fr_end = t_first + n_out, x_t0 + n_x, fr_first + n_fr
+        if n_fr < 1:
+            raise _lib.GolfError(f"{who}: n_fr={n_fr} frames, must be >= 1")
+        if x_t0 > max(t_first - M, 0):
+            raise _lib.GolfError(f"{who}: x_t0={x_t0} lies above sample {max(t_first - M, 0)}, the first tap of sample "
+                                 f"t_first={t_first}")
+        if x_end < t_end:
+            raise _lib.GolfError(f"{who}: x ends at sample {x_end} (n_x={n_x}), before the last computed sample {t_end - 1}")
+        f_lo = t_first // hop
+        if last:
+            if t_end > (fr_end - 1) * hop + 1:
+                raise _lib.GolfError(f"{who}: n_out={n_out}: the samples end at {t_end}, beyond (F - 1) hop + 1 = "
+                                     f"{(fr_end - 1) * hop + 1} of the F={fr_end} frames the utterance ends with")
+            f_lo = min(f_lo, max(fr_end - 2, 0))
+        elif (t_end - 1) // hop + 1 >= fr_end:
+            raise _lib.GolfError(f"{who}: the frames end at {fr_end} (n_fr={n_fr}), without frame {(t_end - 1) // hop + 1} "
+                                 f"after the last sample {t_end - 1}, and last is not set")
+        if fr_first > f_lo:
+            raise _lib.GolfError(f"{who}: fr_first={fr_first} lies above frame {f_lo} of the first sample t_first={t_first}")
+    if B == 0 or n_out == 0:
+        return _residual_empty(x, gain, a, n_out)
+    return _ltv_residual_stream(x, gain, a, x_t0, fr_first, t_first, n_out, last, hop, False)
+
+
 # ------------------------------------------------------------------------------------------------
 # LPC analysis: audio -> (gain, a, rc) per frame (include/golf_amd.h, csrc/lpc_analysis.hip)
 # ------------------------------------------------------------------------------------------------
@@ -1014,20 +1124,9 @@ def spectral_envelope_defaults(sample_rate: float, n_fft: int = 1024):
     return 3.0 * sample_rate / (n_fft - 3), sample_rate / 12.0
 
 
-def spectral_envelope(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop: int, n_fft: int = 1024,
-                      n_ceps: int = None, f0_floor: float = None, f0_ceil: float = None, unvoiced_f0: float = 500.0,
-                      q1: float = -0.15, eps: float = 1e-12, voiced_offset: float = ENV_VOICED_OFFSET,
-                      return_log_env: bool = True):
-    """Pitch-adaptive spectral-envelope analysis (the definition is in include/golf_amd.h): x (B, T) and its f0 track (B, F)
-    in Hz, 0 where unvoiced, frame f centred on sample ``f * hop`` -> ``log_env (B, F, n_fft/2 + 1)``, the natural log of the
-    magnitude envelope on bins 0 .. n_fft/2 (``exp`` of it is what ``stft_filter_frames`` takes as response rows); with
-    ``n_ceps`` also ``ceps (B, F, n_ceps)`` in ``LTVCepFilter``'s convention (``n_ceps = filter_order + 1``); with
-    ``return_log_env=False`` ``ceps`` alone: ``log_env``, ``ceps`` or ``(log_env, ceps)``.  A frame's window is three periods
-    of its f0 clamped to [``f0_floor``, ``f0_ceil``] (defaults ``spectral_envelope_defaults``), of ``unvoiced_f0`` where
-    unvoiced; ``voiced_offset`` (default ``0.5 ln 2``) is added to the log magnitude of voiced frames, which makes them
-    return log|H| of the filter an ``AdditivePulseTrain`` went through.  x is 0 outside [0, T).  The outputs never require
-    grad; strided rows are read in place."""
-    who = "spectral_envelope"
+def _env_params(who, x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset,
+                return_log_env):
+    """The argument checks the two entries share; the numbers with their defaults filled in."""
     if x.dim() != 2:
         raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
     if f0.dim() != 2 or f0.shape[0] != x.shape[0]:
@@ -1060,6 +1159,25 @@ def spectral_envelope(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop
         raise _lib.GolfError(f"{who}: eps={eps} must be positive")
     if q1 != q1 or voiced_offset != voiced_offset:
         raise _lib.GolfError(f"{who}: q1={q1} and voiced_offset={voiced_offset} must be numbers")
+    return hop, n_fft, n_ceps, nb, f0_floor, f0_ceil
+
+
+def spectral_envelope(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop: int, n_fft: int = 1024,
+                      n_ceps: int = None, f0_floor: float = None, f0_ceil: float = None, unvoiced_f0: float = 500.0,
+                      q1: float = -0.15, eps: float = 1e-12, voiced_offset: float = ENV_VOICED_OFFSET,
+                      return_log_env: bool = True):
+    """Pitch-adaptive spectral-envelope analysis (the definition is in include/golf_amd.h): x (B, T) and its f0 track (B, F)
+    in Hz, 0 where unvoiced, frame f centred on sample ``f * hop`` -> ``log_env (B, F, n_fft/2 + 1)``, the natural log of the
+    magnitude envelope on bins 0 .. n_fft/2 (``exp`` of it is what ``stft_filter_frames`` takes as response rows); with
+    ``n_ceps`` also ``ceps (B, F, n_ceps)`` in ``LTVCepFilter``'s convention (``n_ceps = filter_order + 1``); with
+    ``return_log_env=False`` ``ceps`` alone: ``log_env``, ``ceps`` or ``(log_env, ceps)``.  A frame's window is three periods
+    of its f0 clamped to [``f0_floor``, ``f0_ceil``] (defaults ``spectral_envelope_defaults``), of ``unvoiced_f0`` where
+    unvoiced; ``voiced_offset`` (default ``0.5 ln 2``) is added to the log magnitude of voiced frames, which makes them
+    return log|H| of the filter an ``AdditivePulseTrain`` went through.  x is 0 outside [0, T).  The outputs never require
+    grad; strided rows are read in place."""
+    who = "spectral_envelope"
+    hop, n_fft, n_ceps, nb, f0_floor, f0_ceil = _env_params(who, x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil,
+                                                             unvoiced_f0, q1, eps, voiced_offset, return_log_env)
     B, F = f0.shape
     if F < 1:
         raise _lib.GolfError(f"{who}: f0 has {F} frames, must be >= 1")
@@ -1072,6 +1190,81 @@ def spectral_envelope(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop
     else:
         out = _spectral_envelope(x, f0, float(sample_rate), hop, n_fft, n_ceps, f0_floor, f0_ceil, float(unvoiced_f0),
                                  float(q1), float(eps), float(voiced_offset), bool(return_log_env))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def spectral_envelope_hwmax(sample_rate: float, n_fft: int = 1024, f0_floor: float = None) -> int:
+    """The longest half window a frame of ``spectral_envelope`` can take, ``floor(1.5 sr / f0_floor + 0.5)`` samples."""
+    lo = spectral_envelope_defaults(float(sample_rate), int(n_fft))[0] if f0_floor is None else float(f0_floor)
+    return math.floor(1.5 * float(sample_rate) / lo + 0.5)
+
+
+@_amp_no_grad
+def _spectral_envelope_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, sample_rate, hop, n_fft, n_ceps, f0_floor,
+                              f0_ceil, unvoiced_f0, q1, eps, voiced_offset, want_env):
+    _lib.require_device(x, f0)
+    lib = _lib.load()
+    x, f0 = _rows(x), _rows(f0)
+    B = x.shape[0]
+    log_env = torch.empty(B, n_frames, n_fft // 2 + 1, dtype=torch.float32, device=x.device) if want_env else None
+    ceps = torch.empty(B, n_frames, n_ceps, dtype=torch.float32, device=x.device) if n_ceps else None
+    rcode = lib.golf_spectral_envelope_stream_f32(x.data_ptr(), x.stride(0), x_t0, x.shape[1], f0.data_ptr(), f0.stride(0),
+                                                  f0_first, f0.shape[1], _lib.ptr(log_env), _lib.ptr(ceps), B, f_first,
+                                                  n_frames, int(last), n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil,
+                                                  unvoiced_f0, q1, eps, voiced_offset, _lib.stream_ptr())
+    _lib.check(rcode, "golf_spectral_envelope_stream_f32")
+    return tuple(t for t in (log_env, ceps) if t is not None)
+
+
+def spectral_envelope_stream(x: torch.Tensor, f0: torch.Tensor, x_t0: int, f_first: int, f0_first: int, n_frames: int,
+                             last: bool, sample_rate: float, hop: int, n_fft: int = 1024, n_ceps: int = None,
+                             f0_floor: float = None, f0_ceil: float = None, unvoiced_f0: float = 500.0, q1: float = -0.15,
+                             eps: float = 1e-12, voiced_offset: float = ENV_VOICED_OFFSET, return_log_env: bool = True):
+    """``spectral_envelope`` at a position of a longer utterance (golf_spectral_envelope_stream_f32, include/golf_amd.h):
+    frames ``f_first .. f_first + n_frames - 1`` from x (B, n_x), the utterance's samples ``[x_t0, x_t0 + n_x)``, and f0
+    (B, n_f0), its frames ``[f0_first, f0_first + n_f0)``; ``last``: the utterance ends with the x buffer.  The results are
+    those of ``spectral_envelope`` with ``n_frames`` in place of F, and each frame has the bits the one-shot call gives it.
+    With ``hwmax = spectral_envelope_hwmax(sample_rate, n_fft, f0_floor)`` the buffers must hold what the frames can read:
+    ``0 <= x_t0 <= max(0, f_first * hop - hwmax)``, ``f0_first <= f_first``, ``f_first + n_frames <= f0_first + n_f0`` and,
+    unless ``last``, ``(f_first + n_frames - 1) * hop + hwmax + 1 <= x_t0 + n_x``; anything else raises ``GolfError`` before a
+    launch.  ``n_frames = 0`` or an empty batch returns empty results without a launch."""
+    who = "spectral_envelope_stream"
+    hop, n_fft, n_ceps, nb, f0_floor, f0_ceil = _env_params(who, x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil,
+                                                             unvoiced_f0, q1, eps, voiced_offset, return_log_env)
+    x_t0, f_first, f0_first, n_frames, last = int(x_t0), int(f_first), int(f0_first), int(n_frames), bool(last)
+    (B, n_x), n_f0 = x.shape, f0.shape[1]
+    far = 2 ** 62
+    if n_frames < 0:
+        raise _lib.GolfError(f"{who}: n_frames={n_frames} must be >= 0")
+    if B * n_frames >= 2 ** 31:
+        raise _lib.GolfError(f"{who}: B*n_frames = {B * n_frames} frames, must be < 2^31")
+    if not 0 <= x_t0 <= far:
+        raise _lib.GolfError(f"{who}: x_t0={x_t0} must be 0..2^62")
+    if not 0 <= f0_first <= far:
+        raise _lib.GolfError(f"{who}: f0_first={f0_first} must be 0..2^62")
+    if not 0 <= f_first <= far // hop - n_frames:
+        raise _lib.GolfError(f"{who}: f_first={f_first} must be >= 0 with (f_first + n_frames) hop <= 2^62")
+    if n_frames:
+        hwmax = math.floor(1.5 * float(sample_rate) / f0_floor + 0.5)
+        lo, f_end, x_end, f0_end = max(f_first * hop - hwmax, 0), f_first + n_frames, x_t0 + n_x, f0_first + n_f0
+        if x_t0 > lo:
+            raise _lib.GolfError(f"{who}: x_t0={x_t0} lies above sample {lo}, where the window of frame f_first={f_first} may "
+                                 "start")
+        if f0_first > f_first:
+            raise _lib.GolfError(f"{who}: f0_first={f0_first} lies above the first computed frame f_first={f_first}")
+        if f_end > f0_end:
+            raise _lib.GolfError(f"{who}: f0 ends at frame {f0_end} (n_f0={n_f0}), before the last computed frame {f_end - 1}")
+        if not last and (f_end - 1) * hop + hwmax + 1 > x_end:
+            raise _lib.GolfError(f"{who}: x ends at sample {x_end} (n_x={n_x}), before the window of frame {f_end - 1} may end "
+                                 f"({(f_end - 1) * hop + hwmax + 1}), and last is not set")
+    if B == 0 or n_frames == 0:
+        _lib.require_device(x.float(), f0.float())
+        out = [torch.empty(B, n_frames, w, dtype=torch.float32, device=x.device)
+               for w, want in ((nb, return_log_env), (n_ceps, n_ceps)) if want]
+    else:
+        out = _spectral_envelope_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, float(sample_rate), hop, n_fft, n_ceps,
+                                        f0_floor, f0_ceil, float(unvoiced_f0), float(q1), float(eps), float(voiced_offset),
+                                        bool(return_log_env))
     return out[0] if len(out) == 1 else tuple(out)
 
 

@@ -77,6 +77,16 @@ class GlottalSourceAnalysis(nn.Module):
         e = GF.ltv_inverse(x, a, self.hop_length)
         return e / GF.linear_upsample(gain, self.hop_length)[:, :e.shape[1]]
 
+    def residual_fused(self, x, gain, a) -> torch.Tensor:
+        """``residual`` in one launch (``functional.ltv_residual``, golf_ltv_residual_f32): the same inverse filter, bit for
+        bit, divided by the gain interpolated as ``fmaf(w, gain[f+1] - gain[f], gain[f])``, ``w = (t - f hop) / hop``.  It
+        differs from ``residual`` only in how the gain is interpolated (there torch forms the weight as ``fl(1 / hop) t``,
+        whose error grows with t); every sample is a function of its position alone, so this is the definition that
+        ``analysis_stream.ResidualStream`` is exact against.  No gradient."""
+        x = self._plain(x, 1, "the waveform")
+        gain, a = self._plain(gain, self.hop_length, "gain"), self._plain(a, self.hop_length, "a")
+        return GF.ltv_residual(x, gain, a, self.hop_length)
+
     def analyse(self, e, f0):
         """Plain tensors ``(w, theta, rho)``, (B, F) each: the table position with ``unvoiced_weight`` where there is no
         estimate, the table phase at the frame's centre in cycles and the fit in [-1, 1] (0 where there is no estimate)."""

@@ -520,6 +520,80 @@ int golf_spectral_envelope_f32(const float* x, int64_t x_stride, const float* f0
                                double voiced_offset, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same analysis at a position of a longer utterance (additive in ABI 6): frames f_first .. f_first + n_frames - 1 from
+ * windows of the inputs, for the block-by-block form (analysis_stream.SpectralEnvelopeStream).  Frames, steps 1-8, the limits
+ * and the properties are those of golf_spectral_envelope_f32: it is the same kernel and the same launch shape, and a frame
+ * has the one-shot call's bits.  All positions are those of the utterance, int64:
+ *   x (B, n_x), row stride x_stride: samples [x_t0, x_t0 + n_x), x_t0 >= 0.  A sample t < 0 reads as 0, and with last != 0 so
+ *     does t >= x_t0 + n_x (the utterance ends there: T = x_t0 + n_x).
+ *   f0 (B, n_f0), row stride f0_stride: frames [f0_first, f0_first + n_f0).  A frame reads its own f0 only, no neighbour's.
+ *   log_env (B, n_frames, nb), ceps (B, n_frames, n_ceps), either may be NULL, not both: column j is frame f_first + j.
+ * A frame reads the samples f hop - hw .. f hop + hw, hw <= hwmax = floor(1.5 sr / f0_floor + 0.5), the half window of the
+ * lowest f0.  Refused before any launch, all GOLF_EINVAL, each naming its argument -- a mistake in the caller's bookkeeping is
+ * an error, never a window padded with zeros:
+ *   B < 1, n_x < 0, n_f0 < 1, n_frames < 1; x NULL with n_x > 0, f0 NULL; both outputs NULL, ceps with n_ceps == 0;
+ *   x_stride < n_x, f0_stride < n_f0; the limits of golf_spectral_envelope_f32 on n_fft (GOLF_EUNSUPPORTED), n_ceps, hop,
+ *   sample_rate, eps, f0_floor, f0_ceil, unvoiced_f0, q1 and voiced_offset; B*n_frames >= 2^31;
+ *   x_t0, f0_first or (f_first + n_frames) hop outside 0..2^62;
+ *   x_t0 > max(0, f_first hop - hwmax): a frame could read below the buffer;
+ *   f0_first > f_first or f_first + n_frames > f0_first + n_f0: f0 does not cover the frames;
+ *   with last == 0: (f_first + n_frames - 1) hop + hwmax + 1 > x_t0 + n_x (a window could reach beyond the buffer).
+ * ------------------------------------------------------------------------------------------- */
+int golf_spectral_envelope_stream_f32(const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* f0,
+                                      int64_t f0_stride, int64_t f0_first, int n_f0, float* log_env, float* ceps, int B,
+                                      int64_t f_first, int n_frames, int last, int n_fft, int n_ceps, int hop,
+                                      double sample_rate, double f0_floor, double f0_ceil, double unvoiced_f0, double q1,
+                                      double eps, double voiced_offset, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The residual, fused (additive in ABI 6; csrc/lpc_residual.hip): (audio, gain, a) -> the decoder's excitation estimate, the
+ * audio through the inverse of its all-pole filter divided by the interpolated gain, in one launch.  It is the input of the
+ * glottal-source analysis below, and the definition its block-by-block form is exact against: every quantity of sample t is
+ * a function of t and of the two frames around it, never of a running product.  The float64 restatement in
+ * tests/residual_ref.py is the checker.
+ * Inputs: x (B, T) fp32, unit inner stride, row stride x_stride; gain (B, F) and a (B, F, M) fp32, contiguous, as
+ * golf_lpc_analysis_fwd_f32 writes them; 1 <= M <= 64, hop >= 1.  T' = min(T, (F - 1) hop + 1).  For t < T':
+ *   f = min(floor(t / hop), F - 2), or 0 when F == 1;
+ *   w = (float)(t - f hop) / (float)hop, one correctly rounded fp32 division of two exact integers;
+ *   A[t,i] = fmaf(w, a[f+1,i] - a[f,i], a[f,i]), i < M  (a[f,i] itself when F == 1);
+ *   G[t]   = fmaf(w, gain[f+1] - gain[f], gain[f])      (gain[f] itself when F == 1);
+ *   num[t] = x[t] + sum_{i < M, t-1-i >= 0} A[t,i] x[t-1-i], accumulated in fp32 with fmaf in ascending i from x[t]: the
+ *            bits of golf_ltv_inverse_f32;
+ *   e[t]   = num[t] / G[t], one correctly rounded fp32 division (no reciprocal approximation).  A zero gain gives what
+ *            IEEE 754 gives (inf or NaN); golf_lpc_analysis_fwd_f32 never returns 0.
+ * Output: e (B, T'), row stride e_stride, written in full by one launch of one workgroup per (row, tile of 256 samples); the
+ * tile's samples and the M before them are staged in LDS.  No workspace, no atomics, a fixed order: bit-reproducible, and a
+ * row's result does not depend on its batch.  No call allocates or synchronises; graph-capturable.  There is no gradient
+ * (golf_ltv_inverse_f32 has one).
+ * Refused before any launch, GOLF_EINVAL, each naming its argument: B < 1, T < 1, F < 1; any pointer NULL; M outside 1..64;
+ * hop < 1; x_stride < T, e_stride < T'; B * ceil(T' / 256) >= 2^31.
+ * ------------------------------------------------------------------------------------------- */
+int golf_ltv_residual_f32(const float* x, int64_t x_stride, const float* gain, const float* a, float* e, int64_t e_stride,
+                          int B, int T, int F, int M, int hop, void* stream);
+
+/* The same kernel at a position of a longer utterance (additive in ABI 6), for the block-by-block form
+ * (analysis_stream.ResidualStream): samples t_first .. t_first + n_out - 1, each with the one-shot call's bits.  All
+ * positions are those of the utterance, int64:
+ *   x (B, n_x), row stride x_stride: samples [x_t0, x_t0 + n_x); a sample t < 0 reads as 0 (and is never a tap);
+ *   gain (B, n_fr) and a (B, n_fr, M), contiguous: frames [fr_first, fr_first + n_fr);
+ *   e (B, n_out), row stride e_stride: column j is sample t_first + j.
+ * With last == 0 the utterance goes on: f = floor(t / hop) without a clamp, and frame f + 1 must be in the buffer.  With
+ * last != 0 the utterance has F = fr_first + n_fr frames: the clamp f <= F - 2 applies (f = 0 when F == 1) and no sample
+ * at or beyond (F - 1) hop + 1 exists.
+ * Refused before any launch, all GOLF_EINVAL, each naming its argument -- a mistake in the caller's bookkeeping is an error,
+ * never another interpolation:
+ *   B < 1, n_x < 1, n_fr < 1, n_out < 1; any pointer NULL; M outside 1..64; hop < 1; x_stride < n_x, e_stride < n_out;
+ *   x_t0, t_first or (fr_first + n_fr) hop outside 0..2^62; B * ceil(n_out / 256) >= 2^31;
+ *   x_t0 > max(0, t_first - M): a tap could read below the buffer;
+ *   x_t0 + n_x < t_first + n_out: x does not cover the samples;
+ *   with last == 0: floor((t_first + n_out - 1) / hop) + 1 >= fr_first + n_fr (the next frame of the last sample has not come);
+ *   with last != 0: t_first + n_out > (F - 1) hop + 1;
+ *   fr_first > the frame f of sample t_first (as defined above, with the clamp when last != 0): its frame is missing. */
+int golf_ltv_residual_stream_f32(const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* gain, const float* a,
+                                 int64_t fr_first, int n_fr, float* e, int64_t e_stride, int B, int64_t t_first, int n_out,
+                                 int last, int M, int hop, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Glottal-source analysis (additive in ABI 6): (the harmonics of a residual, f0) -> the control of the glottal-flow wavetable
  * (IndexedGlottalFlowTable: table_select_weight), per frame on the grid of the analyses above.  The residual is the audio
  * through golf_ltv_inverse_f32, divided by the gain; its harmonics are what golf_harmonic_analysis_f32 writes.  Each frame's
