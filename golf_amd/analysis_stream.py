@@ -32,6 +32,7 @@ from .f0 import F0Analysis, F0Tracker
 from .glottal import GlottalSourceAnalysis
 from .hna import HarmonicNoiseAnalysis
 from .lpc import LPCAnalysis
+from .stream import _Track
 
 __all__ = ["F0Stream", "F0TrackerStream", "LPCAnalysisStream", "HarmonicNoiseStream", "SpectralEnvelopeStream",
            "GlottalSourceStream", "ResidualStream", "open_analysis_stream", "frames_open", "frames_final", "frame_reach",
@@ -57,92 +58,136 @@ def frame_reach(span: int, centred: bool) -> int:
     return span - span // 2 if centred else span
 
 
-class _FrameStream:
-    """The protocol and the sample buffer the three streams share.  A subclass names its frame (``span``, ``hop``,
-    ``centred``) and implements ``_frames(x, k)``: the one-shot call for the first k frames of x with ``centred=False``."""
+class _Stream:
+    """What every analysis stream shares: the constructor's checks, the check of a pushed block, one ``stream._Track`` per
+    input -- a buffer along dimension 1 that knows where in the utterance it starts -- and the run loop over them.  A
+    subclass implements ``_total(final)``, the units (frames or samples) of the utterance that are final so far;
+    ``_keep()``, for each track the position from which the open units still read; and ``_compute(n, final, *how)``, the
+    next n units from the tracks."""
 
-    def __init__(self, module, batch_size: int, span: int):
+    def __init__(self, batch_size: int, hop: int, n_tracks: int):
         if int(batch_size) < 1:
             raise ValueError(f"{self._who}: batch_size={batch_size}")
-        self.module, self.B = module, int(batch_size)
-        self.span, self.hop, self.centred = int(span), int(module.hop_length), bool(module.centred)
+        self.B, self.hop = int(batch_size), int(hop)
         if self.hop < 1:
             raise _lib.GolfError(f"{self._who}: hop={self.hop} must be >= 1")
-        self._origin = -(self.span // 2) if self.centred else 0
-        self._buf = None     # (B, m) fp32: samples [_buf0, _buf0 + m) with zeros before sample 0
+        self._tracks = tuple(_Track() for _ in range(n_tracks))
         self._reset()
 
     @property
     def _who(self) -> str:
         return type(self).__name__
 
+    @property
+    def pushed(self) -> int:
+        """Samples of this utterance so far."""
+        return self._tracks[0].end
+
     def _reset(self) -> None:
-        self.pushed = 0      # samples of this utterance so far
-        self.framed = 0      # frames handed to the kernels so far
-        self._buf0 = self._origin
-        if self._buf is not None:
-            self._buf = self._buf.new_zeros(self.B, -self._origin)
+        self._done = 0   # units of this utterance computed so far
+        for tr in self._tracks:
+            tr.start = 0
+            if tr.data is not None:
+                tr.data = tr.data[:, :0]
+
+    def _device(self):
+        for tr in self._tracks:
+            if tr.data is not None:
+                return tr.data.device
+        return torch.device("cuda")
+
+    def _check_block(self, t, name: str, hop: int, ndim: int = 2) -> torch.Tensor:
+        """The checks every pushed block passes before its device is looked at: the hop of an AudioTensor, the shape, no
+        gradient; under autocast fp16 / bf16 become fp32."""
+        if isinstance(t, AudioTensor):
+            assert t.hop_length == hop, f"{name} must be at hop {hop} (got {t.hop_length})"
+            t = t.as_tensor()
+        if t.dim() != ndim or t.shape[0] != self.B:
+            raise ValueError(f"{self._who}.push: {name} of shape {tuple(t.shape)}; the stream has B={self.B}")
+        if torch.is_grad_enabled() and t.requires_grad:
+            raise NotImplementedError(f"{self._who}: an input that requires grad (streaming is inference only) is not supported")
+        if torch.is_autocast_enabled() and t.is_floating_point():   # as the one-shot functions: fp16 / bf16 become fp32
+            t = t.float()
+        return t.detach()
+
+    def _take(self, t, name: str, hop: int) -> torch.Tensor:
+        t = self._check_block(t, name, hop)
+        _lib.require_device(t)
+        return t
+
+    def _advance(self, blocks, final: bool, *how):
+        """The run loop: each block (or None) goes to the end of its track; the units that became final are computed; then
+        the utterance is over, or every track drops what no open unit reads (at most what has come).  Nothing here can
+        require grad: ``_check_block`` has detached the blocks, and the kernels' wrappers detach what they take."""
+        for tr, t in zip(self._tracks, blocks):
+            if t is not None:
+                tr.append(t, True)   # fresh: the block is the caller's to give, an emptied track takes it as it is
+        n = max(self._total(final) - self._done, 0)
+        out = self._compute(n, final, *how)
+        self._done += n
+        if final:
+            self._reset()
+        else:
+            for tr, lo in zip(self._tracks, self._keep()):
+                tr.drop_before(lo)
+        return out
+
+
+class _FrameStream(_Stream):
+    """The protocol and the sample track the three one-input streams share.  A subclass names its frame (``span``, ``hop``,
+    ``centred``) and implements ``_frames(x, k)``, the one-shot call for the first k frames of x with ``centred=False``, and
+    ``_emit(k, out, final)``, what the push returns.  The track starts with the zeros before sample 0."""
+
+    def __init__(self, module, batch_size: int, span: int):
+        self.module, self.span, self.centred = module, int(span), bool(module.centred)
+        self._origin = -(self.span // 2) if self.centred else 0
+        super().__init__(batch_size, module.hop_length, 1)
+
+    framed = property(lambda self: self._done, doc="Frames handed to the kernels so far.")
+
+    def _reset(self) -> None:
+        super()._reset()
+        tr = self._tracks[0]
+        tr.start = self._origin
+        if tr.data is not None:
+            tr.data = tr.data.new_zeros(self.B, -self._origin)
+
+    @property
+    def pushed(self) -> int:
+        return max(self._tracks[0].end, 0)   # (the zeros before sample 0 are there from the first push on)
 
     @property
     def latency(self) -> int:
         """The smallest number of samples beyond a frame's own time ``f * hop`` after which it has been emitted."""
         return frame_reach(self.span, self.centred)
 
-    def _take(self, x) -> torch.Tensor:
-        if isinstance(x, AudioTensor):
-            assert x.hop_length == 1, f"the waveform must be at hop 1 (got {x.hop_length})"
-            x = x.as_tensor()
-        if x.dim() != 2 or x.shape[0] != self.B:
-            raise ValueError(f"{self._who}.push: x of shape {tuple(x.shape)}; the stream has B={self.B}")
-        if torch.is_grad_enabled() and x.requires_grad:
-            raise NotImplementedError(f"{self._who}: an input that requires grad (streaming is inference only) is not supported")
-        if torch.is_autocast_enabled() and x.is_floating_point():   # as the one-shot functions: fp16 / bf16 become fp32
-            x = x.float()
-        _lib.require_device(x)
-        return x.detach()
+    def _total(self, final: bool) -> int:
+        return (frames_final if final else frames_open)(self._tracks[0].end, self.span, self.hop, self.centred)
 
-    def _append(self, x: torch.Tensor) -> None:
-        if self._buf is None:
-            self._buf = x.new_zeros(self.B, -self._origin)
-        keep = x[:, min(max(self._buf0 - self.pushed, 0), x.shape[1]):]   # hop > span: samples between frames are dropped
-        if keep.shape[1]:
-            self._buf = torch.cat([self._buf, keep], 1) if self._buf.shape[1] else keep
-        self.pushed += x.shape[1]
+    def _keep(self):
+        return (self._origin + self._done * self.hop,)   # the start of the next frame
 
-    def _advance(self, final: bool):
-        """The frames that became final, through the one-shot kernels; the samples no open frame needs are dropped."""
-        total = frames_final(self.pushed, self.span, self.hop, self.centred) if final else \
-            frames_open(self.pushed, self.span, self.hop, self.centred)
-        k = total - self.framed
+    def _compute(self, k: int, final: bool):
+        """The frames that became final, through the one-shot kernels."""
         out = None
         if k > 0:
-            start = self._origin + self.framed * self.hop   # >= _buf0: nothing before it was kept
-            x = self._buf[:, max(start - self._buf0, 0):] if start < self._buf0 + self._buf.shape[1] else None
-            if x is None or x.shape[1] == 0:
-                x = self._buf.new_zeros(self.B, 1)          # the frames read only the zeros after the end
+            tr = self._tracks[0]   # it starts at the next frame, or ends before it: then only the zeros after the end are read
+            x = tr.data if self._origin + self._done * self.hop < tr.end else tr.data.new_zeros(self.B, 1)
             out = self._frames(x, k)
-            self.framed = total
-        nxt = self._origin + self.framed * self.hop
-        if nxt > self._buf0:
-            self._buf = self._buf[:, min(nxt - self._buf0, self._buf.shape[1]):]
-            self._buf0 = nxt
-        return k, out
-
-    def _device(self):
-        return self._buf.device if self._buf is not None else torch.device("cuda")
+        return self._emit(k, out, final)
 
     def _run(self, x, final: bool):
+        tr = self._tracks[0]
         if x is not None:
-            x = self._take(x)
-        with torch.no_grad():
-            if x is not None:
-                self._append(x)
-            elif self._buf is None:
-                self._buf = torch.zeros(self.B, -self._origin, device=self._device())
-            out = self._emit(*self._advance(final), final)
-            if final:
-                self._reset()
-            return out
+            x = self._take(x, "x", 1)
+        if tr.data is None:
+            tr.data = torch.zeros(self.B, -self._origin, device=self._device()) if x is None else \
+                x.new_zeros(self.B, -self._origin)
+        if x is not None:   # hop > span: the next frame may start beyond what has come, and the samples before it are dropped
+            skip = min(max(self._origin + self._done * self.hop - tr.end, 0), x.shape[1])
+            tr.start += skip   # (the track is empty then)
+            x = x[:, skip:]
+        return self._advance((x,), final)
 
 
 class _F0Base(_FrameStream):
@@ -238,7 +283,7 @@ class F0TrackerStream(_F0Base):
         else:
             period = torch.empty(self.B, 0, m.n_candidates, dtype=torch.float32, device=dev)
             ap = period
-        return GF.f0_viterbi_stream(period, ap, self._carry, self.framed - k, self.lag, m.sample_rate, float(m.tau_min),
+        return GF.f0_viterbi_stream(period, ap, self._carry, self.framed, self.lag, m.sample_rate, float(m.tau_min),
                                     m.unvoiced_cost, m.lag_cost, m.jump_cost, m.switch_cost, flush=final, return_state=True)
 
 
@@ -295,35 +340,9 @@ def hna_keep_from(next_frame: int, span: int, hop: int):
     return max(next_frame * hop - span // 2, 0), max(next_frame - 1, 0)
 
 
-def _check_block(who: str, B: int, t, name: str, hop: int, ndim: int = 2) -> torch.Tensor:
-    """The checks every pushed block passes before its device is looked at: the hop of an AudioTensor, the shape, no
-    gradient; under autocast fp16 / bf16 become fp32."""
-    if isinstance(t, AudioTensor):
-        assert t.hop_length == hop, f"{name} must be at hop {hop} (got {t.hop_length})"
-        t = t.as_tensor()
-    if t.dim() != ndim or t.shape[0] != B:
-        raise ValueError(f"{who}.push: {name} of shape {tuple(t.shape)}; the stream has B={B}")
-    if torch.is_grad_enabled() and t.requires_grad:
-        raise NotImplementedError(f"{who}: an input that requires grad (streaming is inference only) is not supported")
-    if torch.is_autocast_enabled() and t.is_floating_point():   # as the one-shot functions: fp16 / bf16 become fp32
-        t = t.float()
-    return t.detach()
-
-
-def _take_block(who: str, B: int, t, name: str, hop: int, ndim: int = 2) -> torch.Tensor:
-    t = _check_block(who, B, t, name, hop, ndim)
-    _lib.require_device(t)
-    return t
-
-
-def _cat(buf, t):
-    """``buf`` with the block ``t`` appended along dimension 1; no copy when either is empty."""
-    return t if buf is None or buf.shape[1] == 0 else (torch.cat([buf, t], 1) if t.shape[1] else buf)
-
-
-class _AudioF0Stream:
-    """The protocol and the two buffers of the streams that take a waveform and a frame-rate f0 track at two paces.  A
-    subclass names its module type, sets ``span`` and implements ``_total(final)``, the frames final so far; ``_keep()``, the
+class _AudioF0Stream(_Stream):
+    """The protocol of the streams that take a waveform and a frame-rate f0 track at two paces, one track each.  A subclass
+    names its module type, sets ``span`` and implements ``_total(final)``, the frames final so far; ``_keep()``, the
     ``(sample, f0 frame)`` from which the open frames still read; and ``_frames(x, f0, x_t0, f_first, f0_first, k, last,
     full)``, frames ``f_first .. f_first + k - 1`` from the buffers, which start at sample ``x_t0`` and frame ``f0_first``."""
 
@@ -334,60 +353,22 @@ class _AudioF0Stream:
         if not isinstance(module, self._module_type):
             a = self._module_type.__name__
             raise TypeError(f"{self._who}: a{'n' if a[0] in 'AEIOU' else ''} {a} is needed (got {type(module).__name__})")
-        if int(batch_size) < 1:
-            raise ValueError(f"{self._who}: batch_size={batch_size}")
-        self.module, self.B, self.hop = module, int(batch_size), int(module.hop_length)
-        if self.hop < 1:
-            raise _lib.GolfError(f"{self._who}: hop={self.hop} must be >= 1")
-        self._x = self._f0 = None   # (B, m) samples [_x0, _x0 + m) and (B, n) f0 frames [_f00, _f00 + n) of the utterance
-        self._reset()
+        self.module = module
+        super().__init__(batch_size, module.hop_length, 2)
 
-    @property
-    def _who(self) -> str:
-        return type(self).__name__
+    f0_received = property(lambda self: self._tracks[1].end, doc="f0 frames of this utterance so far.")
+    framed = property(lambda self: self._done, doc="Frames emitted so far.")
 
-    def _reset(self) -> None:
-        self.pushed = 0        # samples of this utterance so far
-        self.f0_received = 0   # f0 frames of this utterance so far
-        self.framed = 0        # frames emitted so far
-        self._x0 = self._f00 = 0
-        self._x = None if self._x is None else self._x[:, :0]
-        self._f0 = None if self._f0 is None else self._f0[:, :0]
-
-    def _take(self, t, name: str, hop: int) -> torch.Tensor:
-        return _take_block(self._who, self.B, t, name, hop)
-
-    def _device(self):
-        for t in (self._x, self._f0):
-            if t is not None:
-                return t.device
-        return torch.device("cuda")
+    def _compute(self, k: int, final: bool, full: bool):
+        x, f0 = self._tracks
+        xb = x.data if x.data is not None else torch.empty(self.B, 0, dtype=torch.float32, device=self._device())
+        fb = f0.data if f0.data is not None else torch.empty(self.B, 0, dtype=torch.float32, device=self._device())
+        return self._frames(xb, fb, x.start, self._done, f0.start, k, final, full)
 
     def _run(self, x, f0, final: bool, full: bool):
         x = None if x is None else self._take(x, self._audio, 1)
         f0 = None if f0 is None else self._take(f0, "f0", self.hop)
-        with torch.no_grad():
-            if x is not None:
-                self._x, self.pushed = _cat(self._x, x), self.pushed + x.shape[1]
-            if f0 is not None:
-                self._f0, self.f0_received = _cat(self._f0, f0), self.f0_received + f0.shape[1]
-            k = max(self._total(final) - self.framed, 0)
-            dev = self._device()
-            xb = self._x if self._x is not None else torch.empty(self.B, 0, dtype=torch.float32, device=dev)
-            fb = self._f0 if self._f0 is not None else torch.empty(self.B, 0, dtype=torch.float32, device=dev)
-            out = self._frames(xb, fb, self._x0, self.framed, self._f00, k, final, full)
-            self.framed += k
-            if final:
-                self._reset()
-            else:
-                x_from, f_from = self._keep()
-                if self._x is not None and x_from > self._x0:     # hop > span: at most what has come
-                    d = min(x_from - self._x0, self._x.shape[1])
-                    self._x, self._x0 = self._x[:, d:], self._x0 + d
-                if self._f0 is not None and f_from > self._f00:
-                    d = min(f_from - self._f00, self._f0.shape[1])
-                    self._f0, self._f00 = self._f0[:, d:], self._f00 + d
-            return out
+        return self._advance((x, f0), final, full)
 
 
 class HarmonicNoiseStream(_AudioF0Stream):
@@ -429,10 +410,11 @@ class HarmonicNoiseStream(_AudioF0Stream):
 
     def _total(self, final: bool) -> int:
         # finish(): one frame per f0 frame, whatever the number of samples
-        return self.f0_received if final else hna_frames_final(self.pushed, self.f0_received, self.span, self.hop)
+        x, f0 = self._tracks
+        return f0.end if final else hna_frames_final(x.end, f0.end, self.span, self.hop)
 
     def _keep(self):
-        return hna_keep_from(self.framed, self.span, self.hop)
+        return hna_keep_from(self._done, self.span, self.hop)
 
     def _frames(self, x, f0, x_t0: int, f_first: int, f0_first: int, k: int, last: bool, phases: bool):
         """Frames ``f_first .. f_first + k - 1`` from the buffers, which start at sample ``x_t0`` and frame ``f0_first``."""
@@ -512,10 +494,11 @@ class SpectralEnvelopeStream(_AudioF0Stream):
         return self.hwmax + 1
 
     def _total(self, final: bool) -> int:
-        return self.f0_received if final else env_frames_final(self.pushed, self.f0_received, self.hwmax, self.hop)
+        x, f0 = self._tracks
+        return f0.end if final else env_frames_final(x.end, f0.end, self.hwmax, self.hop)
 
     def _keep(self):
-        return env_keep_from(self.framed, self.hwmax, self.hop)
+        return env_keep_from(self._done, self.hwmax, self.hop)
 
     def _frames(self, x, f0, x_t0: int, f_first: int, f0_first: int, k: int, last: bool, full: bool):
         """``full``: ``(log_env, ceps)`` as ``analyse``; else what ``forward`` returns, one tensor."""
@@ -554,9 +537,10 @@ class GlottalSourceStream(_AudioF0Stream):
     ``torch.equal`` to ``analyse`` on the concatenated ``(e, f0)``, for any cuts and any interleaving.
 
     The bookkeeping is ``HarmonicNoiseStream``'s (``hna_frames_final``, ``hna_keep_from``) with the window arguments that
-    ``analyse`` passes to ``functional.harmonic_analysis``: no noise bins, phases on, ``unvoiced_window = 4 hop``.  The frames
-    that became final go through ``functional.harmonic_analysis_stream`` and then ``functional.glottal_match`` with the f0
-    values of exactly those frames; a frame without an estimate takes ``unvoiced_weight``.  A push that completes no frame
+    ``analyse`` passes to ``functional.harmonic_analysis``: no noise bins, phases on, the module's ``unvoiced_window`` (4 hop).
+    The frames that became final go through ``functional.harmonic_analysis_stream`` and then the module's ``match``, which
+    is how ``analyse`` ends too: ``functional.glottal_match`` with the f0 values of exactly those frames, and
+    ``unvoiced_weight`` for a frame without an estimate.  A push that completes no frame
     launches nothing.  ``latency`` is the audio side, as ``HarmonicNoiseStream.latency``; the frame also needs f0 frame
     ``f + 1``.
 
@@ -567,7 +551,7 @@ class GlottalSourceStream(_AudioF0Stream):
 
     def __init__(self, module: GlottalSourceAnalysis, batch_size: int):
         super().__init__(module, batch_size)
-        self.unvoiced_window = 4 * self.hop   # what harmonic_analysis takes when analyse leaves it out
+        self.unvoiced_window = module.unvoiced_window
         self.span = max(int(module.max_window), self.unvoiced_window)
 
     @property
@@ -577,10 +561,11 @@ class GlottalSourceStream(_AudioF0Stream):
         return frame_reach(self.span, True)
 
     def _total(self, final: bool) -> int:
-        return self.f0_received if final else hna_frames_final(self.pushed, self.f0_received, self.span, self.hop)
+        x, f0 = self._tracks
+        return f0.end if final else hna_frames_final(x.end, f0.end, self.span, self.hop)
 
     def _keep(self):
-        return hna_keep_from(self.framed, self.span, self.hop)
+        return hna_keep_from(self._done, self.span, self.hop)
 
     def _frames(self, e, f0, x_t0: int, f_first: int, f0_first: int, k: int, last: bool, full: bool):
         m = self.module
@@ -590,9 +575,7 @@ class GlottalSourceStream(_AudioF0Stream):
         amp, ph = GF.harmonic_analysis_stream(e, f0, x_t0, f_first, f0_first, k, last, m.sample_rate, self.hop,
                                               m.num_harmonics, None, m.periods, m.min_window, m.max_window,
                                               self.unvoiced_window, return_phases=True)
-        own = f0[:, f_first - f0_first:f_first - f0_first + k]
-        w, theta, rho = GF.glottal_match(amp, ph, own, m.plan(), m.sample_rate, m.n_phi)
-        return torch.nan_to_num_(w, nan=float(m.unvoiced_weight)), theta, rho
+        return m.match(amp, ph, f0[:, f_first - f0_first:f_first - f0_first + k])
 
     def push(self, e=None, f0=None) -> AudioTensor:
         """The next block of the residual and / or the next f0 frames -> ``w`` of the frames that became final."""
@@ -630,7 +613,7 @@ def res_keep_from(emitted: int, frames_received: int, order: int, hop: int):
     return max(emitted - order, 0), max(min(emitted // hop, frames_received - 2), 0)
 
 
-class ResidualStream:
+class ResidualStream(_Stream):
     """``functional.ltv_residual`` (``GlottalSourceAnalysis.residual_fused``) block by block: live audio and the live
     ``(gain, a)`` of an ``LPCAnalysisStream`` on the same audio -> the excitation estimate that a ``GlottalSourceStream``
     reads.
@@ -657,36 +640,19 @@ class ResidualStream:
     Inference only; one stream for the whole batch; ``push`` does no host-device synchronisation."""
 
     def __init__(self, hop_length: int, lpc_order: int, batch_size: int):
-        if int(batch_size) < 1:
-            raise ValueError(f"ResidualStream: batch_size={batch_size}")
-        self.hop, self.order, self.B = int(hop_length), int(lpc_order), int(batch_size)
-        if self.hop < 1:
-            raise _lib.GolfError(f"ResidualStream: hop={self.hop} must be >= 1")
+        super().__init__(batch_size, hop_length, 3)   # the tracks: x, and gain and a, which move together
+        self.order = int(lpc_order)
         if not 1 <= self.order <= GF.RES_MAX_ORDER:
-            raise _lib.GolfError(f"ResidualStream: lpc_order={self.order} must be 1..{GF.RES_MAX_ORDER}")
-        self._x = self._g = self._a = None   # samples [_x0, ...) and frames [_fr0, ...) of the utterance
-        self._reset()
+            raise _lib.GolfError(f"{self._who}: lpc_order={self.order} must be 1..{GF.RES_MAX_ORDER}")
 
-    def _reset(self) -> None:
-        self.pushed = 0            # samples of this utterance so far
-        self.frames_received = 0   # frames of (gain, a) of this utterance so far
-        self.emitted = 0           # samples emitted so far
-        self._x0 = self._fr0 = 0
-        self._x = None if self._x is None else self._x[:, :0]
-        self._g = None if self._g is None else self._g[:, :0]
-        self._a = None if self._a is None else self._a[:, :0]
+    frames_received = property(lambda self: self._tracks[1].end, doc="Frames of (gain, a) of this utterance so far.")
+    emitted = property(lambda self: self._done, doc="Samples emitted so far.")
 
     @property
     def latency(self) -> int:
         """The stream's own part of the delay of ``e[t]`` behind sample t: ``hop`` samples, to the own time of frame
         ``t // hop + 1``; the delay d of the frames behind their own time adds to it (class docstring)."""
         return self.hop
-
-    def _device(self):
-        for t in (self._x, self._g):
-            if t is not None:
-                return t.device
-        return torch.device("cuda")
 
     def _require_device(self, *tensors) -> None:
         _lib.require_device(*tensors)
@@ -697,39 +663,28 @@ class ResidualStream:
             return torch.empty(self.B, 0, dtype=torch.float32, device=self._device())
         return GF.ltv_residual_stream(x, gain, a, x_t0, fr_first, t_first, n, last, self.hop)
 
+    def _total(self, final: bool) -> int:
+        return (res_samples_finish if final else res_samples_final)(self._tracks[0].end, self._tracks[1].end, self.hop)
+
+    def _keep(self):
+        x_from, f_from = res_keep_from(self._done, self._tracks[1].end, self.order, self.hop)
+        return x_from, f_from, f_from
+
+    def _compute(self, n: int, final: bool):
+        x, gain, a = self._tracks
+        return self._samples(x.data, gain.data, a.data, x.start, gain.start, self._done, n, final)
+
     def _run(self, x, gain, a, final: bool):
         if (gain is None) != (a is None):
-            raise ValueError("ResidualStream.push: gain and a come together")
-        who = "ResidualStream"
-        x = None if x is None else _check_block(who, self.B, x, "x", 1)
+            raise ValueError(f"{self._who}.push: gain and a come together")
+        x = None if x is None else self._check_block(x, "x", 1)   # every block is checked before any device is looked at
         if gain is not None:
-            gain, a = _check_block(who, self.B, gain, "gain", self.hop), _check_block(who, self.B, a, "a", self.hop, 3)
+            gain, a = self._check_block(gain, "gain", self.hop), self._check_block(a, "a", self.hop, 3)
             if a.shape[1] != gain.shape[1] or a.shape[2] != self.order:
-                raise ValueError(f"ResidualStream.push: a of shape {tuple(a.shape)} beside gain {tuple(gain.shape)}; the "
+                raise ValueError(f"{self._who}.push: a of shape {tuple(a.shape)} beside gain {tuple(gain.shape)}; the "
                                  f"stream has lpc_order={self.order}")
         self._require_device(x, gain, a)
-        with torch.no_grad():
-            if x is not None:
-                self._x, self.pushed = _cat(self._x, x), self.pushed + x.shape[1]
-            if gain is not None:
-                self._g, self._a = _cat(self._g, gain), _cat(self._a, a)
-                self.frames_received += gain.shape[1]
-            total = res_samples_finish(self.pushed, self.frames_received, self.hop) if final else \
-                res_samples_final(self.pushed, self.frames_received, self.hop)
-            n = max(total - self.emitted, 0)
-            out = self._samples(self._x, self._g, self._a, self._x0, self._fr0, self.emitted, n, final)
-            self.emitted += n
-            if final:
-                self._reset()
-            else:
-                x_from, f_from = res_keep_from(self.emitted, self.frames_received, self.order, self.hop)
-                if self._x is not None and x_from > self._x0:
-                    d = min(x_from - self._x0, self._x.shape[1])
-                    self._x, self._x0 = self._x[:, d:], self._x0 + d
-                if self._g is not None and f_from > self._fr0:
-                    d = min(f_from - self._fr0, self._g.shape[1])
-                    self._g, self._a, self._fr0 = self._g[:, d:], self._a[:, d:], self._fr0 + d
-            return out
+        return self._advance((x, gain, a), final)
 
     def push(self, x=None, gain=None, a=None) -> torch.Tensor:
         """The next block of the waveform and / or the next frames of ``(gain, a)`` -> the samples of ``e`` that became

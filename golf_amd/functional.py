@@ -653,18 +653,58 @@ def ltv_inverse(y: torch.Tensor, a: torch.Tensor, hop: int) -> torch.Tensor:
 RES_MAX_ORDER = 64   # csrc/lpc_residual.hip RES_MAX_M
 
 
+def _analysis_head(who, x, c, name, hop, sample_rate=None, a=None) -> int:
+    """What the analyses of x (B, T) beside a frame-rate track ``c`` (B, F), named ``name``, refuse first: the shapes (with
+    those of ``a`` (B, F, M) where there is one), ``hop < 1`` and a sample rate that is not positive.  Returns the hop."""
+    if x.dim() != 2:
+        raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
+    if c.dim() != 2 or c.shape[0] != x.shape[0]:
+        raise _lib.GolfError(f"{who}: {name} must be (B, F) with the B of x (got {tuple(c.shape)}, x {tuple(x.shape)})")
+    if a is not None and (a.dim() != 3 or a.shape[:2] != c.shape):
+        raise _lib.GolfError(f"{who}: a must be (B, F, M) with the (B, F) of {name} (got {tuple(a.shape)}, {name} "
+                             f"{tuple(c.shape)})")
+    hop = int(hop)
+    if hop < 1:
+        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
+    if sample_rate is not None and not sample_rate > 0:
+        raise _lib.GolfError(f"{who}: sample_rate={sample_rate} must be positive")
+    return hop
+
+
+def _check_frames(who, name, n, least, B=None) -> None:
+    """The frame count ``name`` = n is at least ``least`` and, with ``B``, small enough for the library (which refuses it too;
+    here before the outputs are allocated)."""
+    if n < least:
+        raise _lib.GolfError(f"{who}: {name}={n} frames, must be >= {least}")
+    if B is not None and B * n >= 2 ** 31:
+        raise _lib.GolfError(f"{who}: B*{name} = {B * n} frames, must be < 2^31")
+
+
+def _check_far(who, hop, first, v, count, n, a, va, b, vb) -> None:
+    """The positions of a stream entry stay where ``position * hop`` cannot overflow: the two named ``a`` and ``b`` in
+    0..2^62, and the frames from the one named ``first`` with the ``count`` = n after them below 2^62 / hop."""
+    far = 2 ** 62
+    for name, value in ((a, va), (b, vb)):
+        if not 0 <= value <= far:
+            raise _lib.GolfError(f"{who}: {name}={value} must be 0..2^62")
+    if not 0 <= v <= far // hop - n:
+        raise _lib.GolfError(f"{who}: {first}={v} must be >= 0 with ({first} + {count}) hop <= 2^62")
+
+
 @_amp_no_grad   # an analysis without a backward (ltv_inverse has one): inference only, like harmonic_analysis
-def _ltv_residual_stream(x, gain, a, x_t0, fr_first, t_first, n_out, last, hop, one_shot):
+def _ltv_residual(x, gain, a, pos, n_out, hop):
+    """``pos``: None for the one-shot entry, ``(x_t0, fr_first, t_first, last)`` for the stream entry."""
     _lib.require_device(x, gain, a)
     lib = _lib.load()
     x, gain, a = _rows(x), gain.contiguous(), a.contiguous()
     B, M = x.shape[0], a.shape[2]
     e = torch.empty(B, n_out, dtype=torch.float32, device=x.device)
-    if one_shot:
+    if pos is None:
         rc = lib.golf_ltv_residual_f32(x.data_ptr(), x.stride(0), gain.data_ptr(), a.data_ptr(), e.data_ptr(), e.stride(0), B,
                                        x.shape[1], a.shape[1], M, hop, _lib.stream_ptr())
         _lib.check(rc, "golf_ltv_residual_f32")
     else:
+        x_t0, fr_first, t_first, last = pos
         rc = lib.golf_ltv_residual_stream_f32(x.data_ptr(), x.stride(0), x_t0, x.shape[1], gain.data_ptr(), a.data_ptr(),
                                               fr_first, a.shape[1], e.data_ptr(), e.stride(0), B, t_first, n_out, int(last),
                                               M, hop, _lib.stream_ptr())
@@ -673,16 +713,7 @@ def _ltv_residual_stream(x, gain, a, x_t0, fr_first, t_first, n_out, last, hop, 
 
 
 def _residual_shapes(who, x, gain, a, hop):
-    if x.dim() != 2:
-        raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
-    if gain.dim() != 2 or gain.shape[0] != x.shape[0]:
-        raise _lib.GolfError(f"{who}: gain must be (B, F) with the B of x (got {tuple(gain.shape)}, x {tuple(x.shape)})")
-    if a.dim() != 3 or a.shape[:2] != gain.shape:
-        raise _lib.GolfError(f"{who}: a must be (B, F, M) with the (B, F) of gain (got {tuple(a.shape)}, gain "
-                             f"{tuple(gain.shape)})")
-    hop, M = int(hop), a.shape[2]
-    if hop < 1:
-        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
+    hop, M = _analysis_head(who, x, gain, "gain", hop, a=a), a.shape[2]
     if not 1 <= M <= RES_MAX_ORDER:
         raise _lib.GolfError(f"{who}: M={M} (the last dimension of a) must be 1..{RES_MAX_ORDER}")
     return hop, M
@@ -704,12 +735,11 @@ def ltv_residual(x: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: int)
     who = "ltv_residual"
     hop, M = _residual_shapes(who, x, gain, a, hop)
     (B, T), F = x.shape, gain.shape[1]
-    if F < 1:
-        raise _lib.GolfError(f"{who}: gain has {F} frames, must be >= 1")
+    _check_frames(who, "F", F, 1)
     n_out = ss_output_length(T, F, hop)
     if B == 0 or n_out == 0:
         return _residual_empty(x, gain, a, n_out)
-    return _ltv_residual_stream(x, gain, a, 0, 0, 0, n_out, True, hop, True)
+    return _ltv_residual(x, gain, a, None, n_out, hop)
 
 
 def ltv_residual_stream(x: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, x_t0: int, fr_first: int, t_first: int,
@@ -726,15 +756,9 @@ def ltv_residual_stream(x: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, x_
     hop, M = _residual_shapes(who, x, gain, a, hop)
     x_t0, fr_first, t_first, n_out, last = int(x_t0), int(fr_first), int(t_first), int(n_out), bool(last)
     (B, n_x), n_fr = x.shape, gain.shape[1]
-    far = 2 ** 62
     if n_out < 0:
         raise _lib.GolfError(f"{who}: n_out={n_out} must be >= 0")
-    if not 0 <= x_t0 <= far:
-        raise _lib.GolfError(f"{who}: x_t0={x_t0} must be 0..2^62")
-    if not 0 <= t_first <= far:
-        raise _lib.GolfError(f"{who}: t_first={t_first} must be 0..2^62")
-    if not 0 <= fr_first <= far // hop - n_fr:
-        raise _lib.GolfError(f"{who}: fr_first={fr_first} must be >= 0 with (fr_first + n_fr) hop <= 2^62")
+    _check_far(who, hop, "fr_first", fr_first, "n_fr", n_fr, "x_t0", x_t0, "t_first", t_first)
     if n_out:
         t_end, x_end, fr_end = t_first + n_out, x_t0 + n_x, fr_first + n_fr
         if n_fr < 1:
@@ -757,7 +781,7 @@ def ltv_residual_stream(x: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, x_
             raise _lib.GolfError(f"{who}: fr_first={fr_first} lies above frame {f_lo} of the first sample t_first={t_first}")
     if B == 0 or n_out == 0:
         return _residual_empty(x, gain, a, n_out)
-    return _ltv_residual_stream(x, gain, a, x_t0, fr_first, t_first, n_out, last, hop, False)
+    return _ltv_residual(x, gain, a, (x_t0, fr_first, t_first, last), n_out, hop)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -936,21 +960,75 @@ HNA_MAX_NMAG = 513         # HNA_MAX_NMAG
 
 
 @_amp_no_grad   # an analysis without a backward: inference only, like f0_yin
-def _harmonic_analysis(x, f0, sample_rate, hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth, eps,
-                       want_phases):
+def _harmonic_analysis(x, f0, pos, n_frames, sample_rate, params, eps, want_phases):
+    """``pos``: None for the one-shot entry, ``(x_t0, f_first, f0_first, last)`` for the stream entry; ``params``: what
+    ``_hna_params`` returns."""
+    hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth = params
     _lib.require_device(x, f0)
     lib = _lib.load()
     x, f0 = _rows(x), _rows(f0)
-    (B, T), F = x.shape, f0.shape[1]
-    amp = torch.empty(B, F, K, dtype=torch.float32, device=x.device)
+    B = x.shape[0]
+    amp = torch.empty(B, n_frames, K, dtype=torch.float32, device=x.device)
     phases = torch.empty_like(amp) if want_phases else None   # not asked for: not written
-    log_mag = torch.empty(B, F, n_mag, dtype=torch.float32, device=x.device) if n_mag else None
-    rcode = lib.golf_harmonic_analysis_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), f0.stride(0), amp.data_ptr(),
-                                           _lib.ptr(phases), _lib.ptr(log_mag), B, T, F, K, n_mag, hop, periods,
-                                           min_window, max_window, unvoiced_window, smooth, sample_rate, eps,
-                                           _lib.stream_ptr())
-    _lib.check(rcode, "golf_harmonic_analysis_f32")
+    log_mag = torch.empty(B, n_frames, n_mag, dtype=torch.float32, device=x.device) if n_mag else None
+    if pos is None:
+        rcode = lib.golf_harmonic_analysis_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), f0.stride(0), amp.data_ptr(),
+                                               _lib.ptr(phases), _lib.ptr(log_mag), B, x.shape[1], n_frames, K, n_mag, hop,
+                                               periods, min_window, max_window, unvoiced_window, smooth, sample_rate, eps,
+                                               _lib.stream_ptr())
+        _lib.check(rcode, "golf_harmonic_analysis_f32")
+    else:
+        x_t0, f_first, f0_first, last = pos
+        rcode = lib.golf_harmonic_analysis_stream_f32(x.data_ptr(), x.stride(0), x_t0, x.shape[1], f0.data_ptr(),
+                                                      f0.stride(0), f0_first, f0.shape[1], amp.data_ptr(), _lib.ptr(phases),
+                                                      _lib.ptr(log_mag), B, f_first, n_frames, int(last), K, n_mag, hop,
+                                                      periods, min_window, max_window, unvoiced_window, smooth, sample_rate,
+                                                      eps, _lib.stream_ptr())
+        _lib.check(rcode, "golf_harmonic_analysis_stream_f32")
     return tuple(t for t in (amp, phases, log_mag) if t is not None)
+
+
+def _hna_result(x, f0, pos, n_frames, sample_rate, params, eps, return_phases):
+    """What either entry returns once its checks have passed: empty results without a launch for an empty batch or no frame."""
+    if x.shape[0] == 0 or n_frames == 0:
+        K, n_mag = params[1:3]
+        _lib.require_device(x.float(), f0.float())
+        out = [torch.empty(x.shape[0], n_frames, K, dtype=torch.float32, device=x.device)]
+        if return_phases:
+            out.append(out[0].clone())
+        if n_mag:
+            out.append(torch.empty(x.shape[0], n_frames, n_mag, dtype=torch.float32, device=x.device))
+    else:
+        out = _harmonic_analysis(x, f0, pos, n_frames, float(sample_rate), params, float(eps), bool(return_phases))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def _check_frame_position(who, x, f0, x_t0, f_first, f0_first, n_frames, last, hop, back, ahead, f_back, f_ahead) -> None:
+    """The position of a frame analysis' stream entry: frames ``f_first .. f_first + n_frames - 1``, of which frame f may read
+    the samples ``[f hop - back, f hop + ahead)`` and the f0 frames ``f - f_back .. f + f_ahead``, from x (B, n_x), the samples
+    from ``x_t0`` on, and f0 (B, n_f0), the frames from ``f0_first`` on.  What lies beyond the buffers is read only by a
+    ``last`` call."""
+    (B, n_x), n_f0 = x.shape, f0.shape[1]
+    _check_frames(who, "n_frames", n_frames, 0, B)
+    _check_far(who, hop, "f_first", f_first, "n_frames", n_frames, "x_t0", x_t0, "f0_first", f0_first)
+    if not n_frames:
+        return
+    lo, f_lo, f_end, x_end, f0_end = max(f_first * hop - back, 0), max(f_first - f_back, 0), f_first + n_frames, x_t0 + n_x, \
+        f0_first + n_f0
+    if x_t0 > lo:
+        raise _lib.GolfError(f"{who}: x_t0={x_t0} lies above sample {lo}, where the window of frame f_first={f_first} may "
+                             "start")
+    if f0_first > f_lo:
+        raise _lib.GolfError(f"{who}: f0_first={f0_first} lies above frame {f_lo}, the first that frame f_first={f_first} "
+                             "reads")
+    if f_end > f0_end:
+        raise _lib.GolfError(f"{who}: f0 ends at frame {f0_end} (n_f0={n_f0}), before the last computed frame {f_end - 1}")
+    if not last and (f_end - 1) * hop + ahead > x_end:
+        raise _lib.GolfError(f"{who}: x ends at sample {x_end} (n_x={n_x}), before the window of frame {f_end - 1} may end "
+                             f"({(f_end - 1) * hop + ahead}), and last is not set")
+    if not last and f_end + f_ahead > f0_end:   # (f_ahead = 0: the check before this one has made it)
+        raise _lib.GolfError(f"{who}: f0 ends at frame {f0_end} (n_f0={n_f0}), without the neighbour after frame "
+                             f"{f_end - 1}, and last is not set")
 
 
 def harmonic_analysis(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop: int, num_harmonics: int,
@@ -966,37 +1044,23 @@ def harmonic_analysis(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop
     (default ``4 * hop``) <= 2048.  ``smooth`` averages the noise power over ``2 * smooth + 1`` bins.  Harmonics at or above
     Nyquist are 0; x is 0 outside [0, T).  The outputs never require grad; strided rows are read in place."""
     who = "harmonic_analysis"
-    hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth = _hna_params(
-        who, x, f0, sample_rate, hop, num_harmonics, n_mag, periods, min_window, max_window, unvoiced_window, smooth, eps)
+    params = _hna_params(who, x, f0, sample_rate, hop, num_harmonics, n_mag, periods, min_window, max_window, unvoiced_window,
+                         smooth, eps)
     B, F = f0.shape
-    if F < 1:
-        raise _lib.GolfError(f"harmonic_analysis: f0 has {F} frames, must be >= 1")
-    if B * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
-        raise _lib.GolfError(f"harmonic_analysis: B*F = {B * F} frames, must be < 2^31")
-    if B == 0:
-        out = _hna_empty(x, f0, F, K, n_mag, return_phases)
-    else:
-        out = _harmonic_analysis(x, f0, float(sample_rate), hop, K, n_mag, periods, min_window, max_window, unvoiced_window,
-                                 smooth, float(eps), bool(return_phases))
-    return out[0] if len(out) == 1 else tuple(out)
+    _check_frames(who, "F", F, 1, B)
+    return _hna_result(x, f0, None, F, sample_rate, params, eps, return_phases)
 
 
 def _hna_params(who, x, f0, sample_rate, hop, num_harmonics, n_mag, periods, min_window, max_window, unvoiced_window, smooth,
                 eps):
-    """The argument checks the two entries share; the integers with their defaults filled in."""
-    if x.dim() != 2:
-        raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
-    if f0.dim() != 2 or f0.shape[0] != x.shape[0]:
-        raise _lib.GolfError(f"{who}: f0 must be (B, F) with the B of x (got {tuple(f0.shape)}, x {tuple(x.shape)})")
-    hop, K, periods, smooth = int(hop), int(num_harmonics), int(periods), int(smooth)
+    """The argument checks the two entries share; the integers with their defaults filled in, in the order in which
+    ``_harmonic_analysis`` takes them."""
+    hop = _analysis_head(who, x, f0, "f0", hop, sample_rate)
+    K, periods, smooth = int(num_harmonics), int(periods), int(smooth)
     n_mag = 0 if n_mag is None else int(n_mag)
-    if hop < 1:
-        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
     min_window = 2 * hop if min_window is None else int(min_window)
     unvoiced_window = 4 * hop if unvoiced_window is None else int(unvoiced_window)
     max_window = int(max_window)
-    if not sample_rate > 0:
-        raise _lib.GolfError(f"{who}: sample_rate={sample_rate} must be positive")
     if not 1 <= K <= HNA_MAX_HARMONICS:
         raise _lib.GolfError(f"{who}: num_harmonics={K} must be 1..{HNA_MAX_HARMONICS}")
     if n_mag and not 2 <= n_mag <= HNA_MAX_NMAG:
@@ -1015,34 +1079,6 @@ def _hna_params(who, x, f0, sample_rate, hop, num_harmonics, n_mag, periods, min
     return hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth
 
 
-def _hna_empty(x, f0, F, K, n_mag, return_phases):
-    _lib.require_device(x.float(), f0.float())
-    out = [torch.empty(x.shape[0], F, K, dtype=torch.float32, device=x.device)]
-    if return_phases:
-        out.append(out[0].clone())
-    if n_mag:
-        out.append(torch.empty(x.shape[0], F, n_mag, dtype=torch.float32, device=x.device))
-    return out
-
-
-@_amp_no_grad
-def _harmonic_analysis_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, sample_rate, hop, K, n_mag, periods, min_window,
-                              max_window, unvoiced_window, smooth, eps, want_phases):
-    _lib.require_device(x, f0)
-    lib = _lib.load()
-    x, f0 = _rows(x), _rows(f0)
-    B = x.shape[0]
-    amp = torch.empty(B, n_frames, K, dtype=torch.float32, device=x.device)
-    phases = torch.empty_like(amp) if want_phases else None
-    log_mag = torch.empty(B, n_frames, n_mag, dtype=torch.float32, device=x.device) if n_mag else None
-    rcode = lib.golf_harmonic_analysis_stream_f32(x.data_ptr(), x.stride(0), x_t0, x.shape[1], f0.data_ptr(), f0.stride(0),
-                                                  f0_first, f0.shape[1], amp.data_ptr(), _lib.ptr(phases), _lib.ptr(log_mag),
-                                                  B, f_first, n_frames, int(last), K, n_mag, hop, periods, min_window,
-                                                  max_window, unvoiced_window, smooth, sample_rate, eps, _lib.stream_ptr())
-    _lib.check(rcode, "golf_harmonic_analysis_stream_f32")
-    return tuple(t for t in (amp, phases, log_mag) if t is not None)
-
-
 def harmonic_analysis_stream(x: torch.Tensor, f0: torch.Tensor, x_t0: int, f_first: int, f0_first: int, n_frames: int,
                              last: bool, sample_rate: float, hop: int, num_harmonics: int, n_mag: int = None,
                              periods: int = 4, min_window: int = None, max_window: int = 2048, unvoiced_window: int = None,
@@ -1057,45 +1093,12 @@ def harmonic_analysis_stream(x: torch.Tensor, f0: torch.Tensor, x_t0: int, f_fir
     f0_first + n_f0``; anything else raises ``GolfError`` before a launch.  ``n_frames = 0`` or an empty batch returns empty
     results without a launch."""
     who = "harmonic_analysis_stream"
-    hop, K, n_mag, periods, min_window, max_window, unvoiced_window, smooth = _hna_params(
+    hop, _, _, _, _, max_window, unvoiced_window, _ = params = _hna_params(
         who, x, f0, sample_rate, hop, num_harmonics, n_mag, periods, min_window, max_window, unvoiced_window, smooth, eps)
     x_t0, f_first, f0_first, n_frames, last = int(x_t0), int(f_first), int(f0_first), int(n_frames), bool(last)
-    (B, n_x), n_f0 = x.shape, f0.shape[1]
-    far = 2 ** 62
-    if n_frames < 0:
-        raise _lib.GolfError(f"{who}: n_frames={n_frames} must be >= 0")
-    if B * n_frames >= 2 ** 31:
-        raise _lib.GolfError(f"{who}: B*n_frames = {B * n_frames} frames, must be < 2^31")
-    if not 0 <= x_t0 <= far:
-        raise _lib.GolfError(f"{who}: x_t0={x_t0} must be 0..2^62")
-    if not 0 <= f0_first <= far:
-        raise _lib.GolfError(f"{who}: f0_first={f0_first} must be 0..2^62")
-    if not 0 <= f_first <= far // hop - n_frames:
-        raise _lib.GolfError(f"{who}: f_first={f_first} must be >= 0 with (f_first + n_frames) hop <= 2^62")
-    if n_frames:
-        Lmax = max(max_window, unvoiced_window)
-        lo, f_end, x_end, f0_end = max(f_first * hop - Lmax // 2, 0), f_first + n_frames, x_t0 + n_x, f0_first + n_f0
-        if x_t0 > lo:
-            raise _lib.GolfError(f"{who}: x_t0={x_t0} lies above sample {lo}, where the window of frame f_first={f_first} may "
-                                 "start")
-        if f0_first > max(f_first - 1, 0):
-            raise _lib.GolfError(f"{who}: f0_first={f0_first} lies above frame {max(f_first - 1, 0)}, the neighbour before "
-                                 f"f_first={f_first}")
-        if f_end > f0_end:
-            raise _lib.GolfError(f"{who}: f0 ends at frame {f0_end} (n_f0={n_f0}), before the last computed frame {f_end - 1}")
-        if not last and (f_end - 1) * hop + Lmax - Lmax // 2 > x_end:
-            raise _lib.GolfError(f"{who}: x ends at sample {x_end} (n_x={n_x}), before the window of frame {f_end - 1} may end "
-                                 f"({(f_end - 1) * hop + Lmax - Lmax // 2}), and last is not set")
-        if not last and f_end + 1 > f0_end:
-            raise _lib.GolfError(f"{who}: f0 ends at frame {f0_end} (n_f0={n_f0}), without the neighbour after frame "
-                                 f"{f_end - 1}, and last is not set")
-    if B == 0 or n_frames == 0:
-        out = _hna_empty(x, f0, n_frames, K, n_mag, return_phases)
-    else:
-        out = _harmonic_analysis_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, float(sample_rate), hop, K, n_mag,
-                                        periods, min_window, max_window, unvoiced_window, smooth, float(eps),
-                                        bool(return_phases))
-    return out[0] if len(out) == 1 else tuple(out)
+    Lmax = max(max_window, unvoiced_window)
+    _check_frame_position(who, x, f0, x_t0, f_first, f0_first, n_frames, last, hop, Lmax // 2, Lmax - Lmax // 2, 1, 1)
+    return _hna_result(x, f0, (x_t0, f_first, f0_first, last), n_frames, sample_rate, params, eps, return_phases)
 
 
 ENV_MIN_NFFT, ENV_MAX_NFFT = 64, 2048   # csrc/spec_envelope.hip ENV_MIN_N, ENV_MAX_N
@@ -1103,19 +1106,43 @@ ENV_VOICED_OFFSET = 0.5 * math.log(2.0)
 
 
 @_amp_no_grad   # an analysis without a backward: inference only, like harmonic_analysis
-def _spectral_envelope(x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset,
-                       want_env):
+def _spectral_envelope(x, f0, pos, n_frames, sample_rate, params, unvoiced_f0, q1, eps, voiced_offset, want_env):
+    """``pos``: None for the one-shot entry, ``(x_t0, f_first, f0_first, last)`` for the stream entry; ``params``: what
+    ``_env_params`` returns."""
+    hop, n_fft, n_ceps, _, f0_floor, f0_ceil = params
     _lib.require_device(x, f0)
     lib = _lib.load()
     x, f0 = _rows(x), _rows(f0)
-    (B, T), F = x.shape, f0.shape[1]
-    log_env = torch.empty(B, F, n_fft // 2 + 1, dtype=torch.float32, device=x.device) if want_env else None
-    ceps = torch.empty(B, F, n_ceps, dtype=torch.float32, device=x.device) if n_ceps else None   # not asked for: not written
-    rcode = lib.golf_spectral_envelope_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), f0.stride(0), _lib.ptr(log_env),
-                                           _lib.ptr(ceps), B, T, F, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil,
-                                           unvoiced_f0, q1, eps, voiced_offset, _lib.stream_ptr())
-    _lib.check(rcode, "golf_spectral_envelope_f32")
+    B = x.shape[0]
+    log_env = torch.empty(B, n_frames, n_fft // 2 + 1, dtype=torch.float32, device=x.device) if want_env else None
+    ceps = torch.empty(B, n_frames, n_ceps, dtype=torch.float32, device=x.device) if n_ceps else None   # not asked for: not written
+    if pos is None:
+        rcode = lib.golf_spectral_envelope_f32(x.data_ptr(), x.stride(0), f0.data_ptr(), f0.stride(0), _lib.ptr(log_env),
+                                               _lib.ptr(ceps), B, x.shape[1], n_frames, n_fft, n_ceps, hop, sample_rate,
+                                               f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset, _lib.stream_ptr())
+        _lib.check(rcode, "golf_spectral_envelope_f32")
+    else:
+        x_t0, f_first, f0_first, last = pos
+        rcode = lib.golf_spectral_envelope_stream_f32(x.data_ptr(), x.stride(0), x_t0, x.shape[1], f0.data_ptr(),
+                                                      f0.stride(0), f0_first, f0.shape[1], _lib.ptr(log_env), _lib.ptr(ceps),
+                                                      B, f_first, n_frames, int(last), n_fft, n_ceps, hop, sample_rate,
+                                                      f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset,
+                                                      _lib.stream_ptr())
+        _lib.check(rcode, "golf_spectral_envelope_stream_f32")
     return tuple(t for t in (log_env, ceps) if t is not None)
+
+
+def _env_result(x, f0, pos, n_frames, sample_rate, params, unvoiced_f0, q1, eps, voiced_offset, return_log_env):
+    """What either entry returns once its checks have passed: empty results without a launch for an empty batch or no frame."""
+    if x.shape[0] == 0 or n_frames == 0:
+        n_ceps, nb = params[2:4]
+        _lib.require_device(x.float(), f0.float())
+        out = [torch.empty(x.shape[0], n_frames, w, dtype=torch.float32, device=x.device)
+               for w, want in ((nb, return_log_env), (n_ceps, n_ceps)) if want]
+    else:
+        out = _spectral_envelope(x, f0, pos, n_frames, float(sample_rate), params, float(unvoiced_f0), float(q1), float(eps),
+                                 float(voiced_offset), bool(return_log_env))
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 def spectral_envelope_defaults(sample_rate: float, n_fft: int = 1024):
@@ -1127,16 +1154,8 @@ def spectral_envelope_defaults(sample_rate: float, n_fft: int = 1024):
 def _env_params(who, x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset,
                 return_log_env):
     """The argument checks the two entries share; the numbers with their defaults filled in."""
-    if x.dim() != 2:
-        raise _lib.GolfError(f"{who}: x must be (B, T) (got {tuple(x.shape)})")
-    if f0.dim() != 2 or f0.shape[0] != x.shape[0]:
-        raise _lib.GolfError(f"{who}: f0 must be (B, F) with the B of x (got {tuple(f0.shape)}, x {tuple(x.shape)})")
-    hop, n_fft = int(hop), int(n_fft)
+    hop, n_fft = _analysis_head(who, x, f0, "f0", hop, sample_rate), int(n_fft)
     n_ceps = 0 if n_ceps is None else int(n_ceps)
-    if hop < 1:
-        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
-    if not sample_rate > 0:
-        raise _lib.GolfError(f"{who}: sample_rate={sample_rate} must be positive")
     if not ENV_MIN_NFFT <= n_fft <= ENV_MAX_NFFT or n_fft & (n_fft - 1):
         raise _lib.GolfError(f"{who}: n_fft={n_fft} must be a power of two in [{ENV_MIN_NFFT}, {ENV_MAX_NFFT}]")
     nb = n_fft // 2 + 1
@@ -1176,44 +1195,17 @@ def spectral_envelope(x: torch.Tensor, f0: torch.Tensor, sample_rate: float, hop
     return log|H| of the filter an ``AdditivePulseTrain`` went through.  x is 0 outside [0, T).  The outputs never require
     grad; strided rows are read in place."""
     who = "spectral_envelope"
-    hop, n_fft, n_ceps, nb, f0_floor, f0_ceil = _env_params(who, x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil,
-                                                             unvoiced_f0, q1, eps, voiced_offset, return_log_env)
+    params = _env_params(who, x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset,
+                         return_log_env)
     B, F = f0.shape
-    if F < 1:
-        raise _lib.GolfError(f"{who}: f0 has {F} frames, must be >= 1")
-    if B * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
-        raise _lib.GolfError(f"{who}: B*F = {B * F} frames, must be < 2^31")
-    if B == 0:
-        _lib.require_device(x.float(), f0.float())
-        out = [torch.empty(0, F, w, dtype=torch.float32, device=x.device)
-               for w, want in ((nb, return_log_env), (n_ceps, n_ceps)) if want]
-    else:
-        out = _spectral_envelope(x, f0, float(sample_rate), hop, n_fft, n_ceps, f0_floor, f0_ceil, float(unvoiced_f0),
-                                 float(q1), float(eps), float(voiced_offset), bool(return_log_env))
-    return out[0] if len(out) == 1 else tuple(out)
+    _check_frames(who, "F", F, 1, B)
+    return _env_result(x, f0, None, F, sample_rate, params, unvoiced_f0, q1, eps, voiced_offset, return_log_env)
 
 
 def spectral_envelope_hwmax(sample_rate: float, n_fft: int = 1024, f0_floor: float = None) -> int:
     """The longest half window a frame of ``spectral_envelope`` can take, ``floor(1.5 sr / f0_floor + 0.5)`` samples."""
     lo = spectral_envelope_defaults(float(sample_rate), int(n_fft))[0] if f0_floor is None else float(f0_floor)
     return math.floor(1.5 * float(sample_rate) / lo + 0.5)
-
-
-@_amp_no_grad
-def _spectral_envelope_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, sample_rate, hop, n_fft, n_ceps, f0_floor,
-                              f0_ceil, unvoiced_f0, q1, eps, voiced_offset, want_env):
-    _lib.require_device(x, f0)
-    lib = _lib.load()
-    x, f0 = _rows(x), _rows(f0)
-    B = x.shape[0]
-    log_env = torch.empty(B, n_frames, n_fft // 2 + 1, dtype=torch.float32, device=x.device) if want_env else None
-    ceps = torch.empty(B, n_frames, n_ceps, dtype=torch.float32, device=x.device) if n_ceps else None
-    rcode = lib.golf_spectral_envelope_stream_f32(x.data_ptr(), x.stride(0), x_t0, x.shape[1], f0.data_ptr(), f0.stride(0),
-                                                  f0_first, f0.shape[1], _lib.ptr(log_env), _lib.ptr(ceps), B, f_first,
-                                                  n_frames, int(last), n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil,
-                                                  unvoiced_f0, q1, eps, voiced_offset, _lib.stream_ptr())
-    _lib.check(rcode, "golf_spectral_envelope_stream_f32")
-    return tuple(t for t in (log_env, ceps) if t is not None)
 
 
 def spectral_envelope_stream(x: torch.Tensor, f0: torch.Tensor, x_t0: int, f_first: int, f0_first: int, n_frames: int,
@@ -1229,43 +1221,13 @@ def spectral_envelope_stream(x: torch.Tensor, f0: torch.Tensor, x_t0: int, f_fir
     unless ``last``, ``(f_first + n_frames - 1) * hop + hwmax + 1 <= x_t0 + n_x``; anything else raises ``GolfError`` before a
     launch.  ``n_frames = 0`` or an empty batch returns empty results without a launch."""
     who = "spectral_envelope_stream"
-    hop, n_fft, n_ceps, nb, f0_floor, f0_ceil = _env_params(who, x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil,
-                                                             unvoiced_f0, q1, eps, voiced_offset, return_log_env)
+    hop, _, _, _, f0_floor, _ = params = _env_params(who, x, f0, sample_rate, hop, n_fft, n_ceps, f0_floor, f0_ceil,
+                                                         unvoiced_f0, q1, eps, voiced_offset, return_log_env)
     x_t0, f_first, f0_first, n_frames, last = int(x_t0), int(f_first), int(f0_first), int(n_frames), bool(last)
-    (B, n_x), n_f0 = x.shape, f0.shape[1]
-    far = 2 ** 62
-    if n_frames < 0:
-        raise _lib.GolfError(f"{who}: n_frames={n_frames} must be >= 0")
-    if B * n_frames >= 2 ** 31:
-        raise _lib.GolfError(f"{who}: B*n_frames = {B * n_frames} frames, must be < 2^31")
-    if not 0 <= x_t0 <= far:
-        raise _lib.GolfError(f"{who}: x_t0={x_t0} must be 0..2^62")
-    if not 0 <= f0_first <= far:
-        raise _lib.GolfError(f"{who}: f0_first={f0_first} must be 0..2^62")
-    if not 0 <= f_first <= far // hop - n_frames:
-        raise _lib.GolfError(f"{who}: f_first={f_first} must be >= 0 with (f_first + n_frames) hop <= 2^62")
-    if n_frames:
-        hwmax = math.floor(1.5 * float(sample_rate) / f0_floor + 0.5)
-        lo, f_end, x_end, f0_end = max(f_first * hop - hwmax, 0), f_first + n_frames, x_t0 + n_x, f0_first + n_f0
-        if x_t0 > lo:
-            raise _lib.GolfError(f"{who}: x_t0={x_t0} lies above sample {lo}, where the window of frame f_first={f_first} may "
-                                 "start")
-        if f0_first > f_first:
-            raise _lib.GolfError(f"{who}: f0_first={f0_first} lies above the first computed frame f_first={f_first}")
-        if f_end > f0_end:
-            raise _lib.GolfError(f"{who}: f0 ends at frame {f0_end} (n_f0={n_f0}), before the last computed frame {f_end - 1}")
-        if not last and (f_end - 1) * hop + hwmax + 1 > x_end:
-            raise _lib.GolfError(f"{who}: x ends at sample {x_end} (n_x={n_x}), before the window of frame {f_end - 1} may end "
-                                 f"({(f_end - 1) * hop + hwmax + 1}), and last is not set")
-    if B == 0 or n_frames == 0:
-        _lib.require_device(x.float(), f0.float())
-        out = [torch.empty(B, n_frames, w, dtype=torch.float32, device=x.device)
-               for w, want in ((nb, return_log_env), (n_ceps, n_ceps)) if want]
-    else:
-        out = _spectral_envelope_stream(x, f0, x_t0, f_first, f0_first, n_frames, last, float(sample_rate), hop, n_fft, n_ceps,
-                                        f0_floor, f0_ceil, float(unvoiced_f0), float(q1), float(eps), float(voiced_offset),
-                                        bool(return_log_env))
-    return out[0] if len(out) == 1 else tuple(out)
+    hwmax = math.floor(1.5 * float(sample_rate) / f0_floor + 0.5)   # spectral_envelope_hwmax at the f0_floor in force
+    _check_frame_position(who, x, f0, x_t0, f_first, f0_first, n_frames, last, hop, hwmax, hwmax + 1, 0, 0)
+    return _env_result(x, f0, (x_t0, f_first, f0_first, last), n_frames, sample_rate, params, unvoiced_f0, q1, eps,
+                       voiced_offset, return_log_env)
 
 
 # ------------------------------------------------------------------------------------------------

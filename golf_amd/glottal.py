@@ -94,7 +94,18 @@ class GlottalSourceAnalysis(nn.Module):
         assert e.ndim == 2, e.shape
         assert f0.ndim == 2, f0.shape
         amp, ph = GF.harmonic_analysis(e, f0, self.sample_rate, self.hop_length, self.num_harmonics, None, self.periods,
-                                       self.min_window, self.max_window, return_phases=True)
+                                       self.min_window, self.max_window, self.unvoiced_window, return_phases=True)
+        return self.match(amp, ph, f0)
+
+    @property
+    def unvoiced_window(self) -> int:
+        """The window of an unvoiced frame: what ``functional.harmonic_analysis`` takes when it is left out."""
+        return 4 * int(self.hop_length)
+
+    def match(self, amp, ph, f0):
+        """``(w, theta, rho)`` of frames whose harmonics ``(amp, ph)`` the harmonic analysis of the residual gave and whose
+        f0 is ``f0``: ``functional.glottal_match`` against the table, then ``unvoiced_weight`` where there is no estimate.
+        ``analyse`` and ``analysis_stream.GlottalSourceStream`` both end with it."""
         w, theta, rho = GF.glottal_match(amp, ph, f0, self.plan(), self.sample_rate, self.n_phi)
         return torch.nan_to_num_(w, nan=float(self.unvoiced_weight)), theta, rho
 

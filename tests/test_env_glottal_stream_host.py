@@ -185,6 +185,24 @@ def drive(push, finish, audio, ctrl, rng, a_sizes, c_sizes, mode):
     return [np.concatenate([o[i] for o in outs], 1) for i in range(len(outs[0]))], [o[0].shape[1] for o in outs]
 
 
+def assert_exact_trimming(calls, keep_from):
+    """Every recorded call ``(x_t0, n_x, first, c_first, n_c, last)`` -- ``first`` the first frame or sample it computes --
+    starts its buffers where the call before it left them: at ``keep_from(first, controls received then)`` or, where less had
+    come, at what had come; at 0 in an utterance's first call."""
+    prev = None   # (samples, control frames) received at the previous call of the same utterance
+    for x_t0, n_x, first, c_first, n_c, last in calls:
+        if prev is None:
+            assert (x_t0, c_first) == (0, 0)
+        else:
+            x_from, c_from = keep_from(first, prev[1])
+            assert (x_t0, c_first) == (min(x_from, prev[0]), min(c_from, prev[1]))
+        prev = None if last else (x_t0 + n_x, c_first + n_c)
+
+
+def frame_calls(calls):
+    return [(x_t0, n_x, f_first, f0_first, n_f0, last) for x_t0, n_x, f_first, f0_first, n_f0, k, last in calls]
+
+
 def tensors(blocks):
     return None if blocks is None else [torch.tensor(np.ascontiguousarray(b)) for b in blocks]
 
@@ -222,6 +240,7 @@ class HostEnvStream(_HostTake, AS.SpectralEnvelopeStream):
         with pytest.raises(GolfError, match="no CPU path"):   # the wrapper's own preconditions hold: only the device is missing
             super()._frames(x, f0, x_t0, f_first, f0_first, k, last, full)
         self.calls.append((x_t0, x.shape[1], f_first, f0_first, f0.shape[1], k, last))
+        assert (x_t0 + x.shape[1], f0_first + f0.shape[1]) == (self.pushed, self.f0_received)   # the buffers end at all that came
         m, nb = self.module, self.module.n_fft // 2 + 1
         n_ceps = nb if m.filter_order is None else m.filter_order + 1
         if k:
@@ -292,6 +311,7 @@ def test_env_offset_indexing_against_the_float64_restatement(name, mode):
         assert sum(counts) == F
         assert np.array_equal(got[0], ref["log_env"]) and np.array_equal(got[1], ref["ceps"])
         assert (st.pushed, st.f0_received, st.framed) == (0, 0, 0)
+    assert_exact_trimming(frame_calls(st.calls), lambda nxt, _: AS.env_keep_from(nxt, st.hwmax, hop))
     launches = [c for c in st.calls if c[5]]
     assert any(c[0] > 0 for c in launches) and any(c[3] > 0 for c in launches)   # a call above sample 0 and above frame 0
     if mode == "mixed" and name != "hop1":
@@ -309,6 +329,7 @@ class HostGlottalStream(_HostTake, AS.GlottalSourceStream):
 
     def _frames(self, e, f0, x_t0, f_first, f0_first, k, last, full):
         self.calls.append((x_t0, e.shape[1], f_first, f0_first, f0.shape[1], k, last))
+        assert (x_t0 + e.shape[1], f0_first + f0.shape[1]) == (self.pushed, self.f0_received)
         if not k:
             return super()._frames(e, f0, x_t0, f_first, f0_first, k, last, full)   # launches nothing: no device is asked for
         with pytest.raises(GolfError, match="no CPU path"):
@@ -364,6 +385,7 @@ def test_glottal_offset_indexing_against_the_float64_restatement(name, mode):
         for g, w in zip(got, want):
             assert g.shape == w.shape and np.array_equal(g, w)
         assert (st.pushed, st.f0_received, st.framed) == (0, 0, 0)
+    assert_exact_trimming(frame_calls(st.calls), lambda nxt, _: AS.hna_keep_from(nxt, st.span, hop))
     launches = [c for c in st.calls if c[5]]
     assert any(c[0] > 0 for c in launches) and any(c[3] > 0 for c in launches)
     assert any(c[5] == 0 for c in st.calls)   # and a push that completed no frame asked for no device
@@ -390,6 +412,7 @@ class HostResidualStream(AS.ResidualStream):
     def _samples(self, x, gain, a, x_t0, fr_first, t_first, n, last):
         self.calls.append((x_t0, 0 if x is None else x.shape[1], fr_first, 0 if gain is None else gain.shape[1], t_first, n,
                            last))
+        assert (x_t0 + self.calls[-1][1], fr_first + self.calls[-1][3]) == (self.pushed, self.frames_received)
         if not n:
             return super()._samples(x, gain, a, x_t0, fr_first, t_first, n, last).double()
         with pytest.raises(GolfError, match="no CPU path"):
@@ -424,6 +447,8 @@ def test_residual_offset_indexing_against_the_float64_restatement(name, mode):
         assert sum(counts) == want.shape[1]
         assert np.array_equal(got[0], want)
         assert (st.pushed, st.frames_received, st.emitted) == (0, 0, 0)
+    assert_exact_trimming([(x_t0, n_x, t_first, fr_first, n_fr, last) for x_t0, n_x, fr_first, n_fr, t_first, n, last in st.calls],
+                          lambda emitted, frames: AS.res_keep_from(emitted, frames, M, hop))
     launches = [c for c in st.calls if c[5]]
     assert len(launches) >= 3 or mode != "mixed"
     assert any(c[0] > 0 for c in launches) and any(c[2] > 0 for c in launches)   # above sample 0 and above frame 0

@@ -268,3 +268,125 @@ def test_functional_and_streams_without_a_device():
             s.push(torch.zeros(3, 100))
         with pytest.raises(NotImplementedError, match="requires grad"):
             s.push(torch.zeros(2, 100, requires_grad=True))
+
+
+# ---- the sample buffer of the frame-local streams, with a frame-local stand-in for the kernels -------------------------------
+WEIGHTS = [3, -1, 4, 1, -5, 9, 2, -6, 5]   # fixed integers: with small integers in x every sum is exact in fp32
+
+
+def local_frames(x, k, span, hop):
+    """``out[b, f] = sum_j WEIGHTS[j] x[b, f * hop + j]`` over ``j < span`` for the first k frames of x, which is zero beyond
+    its end: what a one-shot kernel does with ``centred=False, n_frames=k``, frame by frame."""
+    need = (k - 1) * hop + span
+    x = torch.nn.functional.pad(x, (0, max(need - x.shape[1], 0)))[:, :need]
+    return (x.unfold(1, span, hop) * torch.tensor(WEIGHTS[:span], dtype=x.dtype)).sum(-1)
+
+
+def _host_frames(base):
+    """``base`` with the device left out: ``_take`` makes every check and then accepts the CPU tensor, and ``_frames`` is the
+    stand-in, shaped as the stream's own kernel shapes its results (``_shape``)."""
+    from golf_amd._lib import GolfError
+    from golf_amd.audiotensor import AudioTensor
+
+    class Host(base):
+        block = 0   # the length of the block being pushed: the driver sets it
+
+        def _device(self):
+            return torch.device("cpu")
+
+        def _take(self, t, *args):
+            try:
+                return super()._take(t, *args)
+            except GolfError as e:
+                assert "no CPU path" in str(e)
+                return (t.as_tensor() if isinstance(t, AudioTensor) else t).detach()
+
+        def _frames(self, x, k):
+            assert k >= 1 and 1 <= x.shape[1] <= self.span + (k - 1) * self.hop + self.block   # nothing older is kept
+            self.calls = getattr(self, "calls", 0) + 1
+            return self._shape(local_frames(x, k, self.span, self.hop))
+
+    return Host
+
+
+def _frame_stream_classes():
+    from types import SimpleNamespace
+
+    from golf_amd import analysis_stream as AS
+    from golf_amd.f0 import F0Analysis
+    from golf_amd.lpc import LPCAnalysis
+
+    class Plain(_host_frames(AS._FrameStream)):
+        """The shared base alone: one (B, k) result."""
+
+        def __init__(self, span, hop, centred, B):
+            super().__init__(SimpleNamespace(hop_length=hop, centred=centred), B, span)
+
+        def _shape(self, out):
+            return (out,)
+
+        def _emit(self, k, out, final):
+            return out if k > 0 else (torch.empty(self.B, 0),)
+
+        def push_all(self, x):
+            return self._run(x, False)
+
+        def finish_all(self):
+            return self._run(None, True)
+
+    class LPC(_host_frames(AS.LPCAnalysisStream)):
+        def __init__(self, span, hop, centred, B):
+            super().__init__(LPCAnalysis(2, hop, window_length=span, centred=centred), B, return_rc=True)
+
+        def _shape(self, out):
+            return out, torch.stack([out + 1, out + 2], -1), torch.stack([out + 3, out + 4], -1)
+
+    class F0(_host_frames(AS.F0Stream)):
+        def __init__(self, span, hop, centred, B):   # tau_max = 2, so span = window_length + 2
+            super().__init__(F0Analysis(4.0, hop, f0_min=2.0, f0_max=3.0, window_length=span - 2, centred=centred), B)
+
+        def _shape(self, out):
+            return out, out + 1, out + 2
+
+    return Plain, LPC, F0
+
+
+@pytest.mark.parametrize("centred", (True, False))
+@pytest.mark.parametrize("span,hop", [(8, 3), (7, 7), (4, 9), (9, 1), (1, 1)])   # hop below, at and above the span
+def test_frame_streams_on_the_host(span, hop, centred):
+    """``_FrameStream``'s buffer -- the zero prefix before sample 0, the samples dropped between frames when hop > span, the
+    frames that read only zeros after the end, the reset at ``finish()`` -- under the base alone, ``LPCAnalysisStream`` and
+    ``F0Stream`` (whose frame of window_length + tau_max samples cannot be 1 long): two utterances per stream, every
+    length, random cuts, ``torch.equal`` to the stand-in over the whole zero-padded utterance."""
+    from golf_amd.analysis_stream import frame_reach, frames_final
+
+    B, sizes = 2, [0, 1, hop - 1, hop, hop + 1, span, 3 * span + 1]
+    for cls in _frame_stream_classes():
+        if cls.__name__ == "F0" and span < 3:
+            continue
+        st = cls(span, hop, centred, B)
+        assert (st.span, st.hop, st.centred, st.latency) == (span, hop, centred, frame_reach(span, centred))
+        launches = 0
+        for i, T in enumerate((0, 1, span - 1, span, 5 * hop + span + 1, 5 * hop + span + 1)):
+            rng = np.random.default_rng(1000 * span + 10 * hop + i)
+            x = torch.tensor(rng.integers(-8, 9, (B, T)).astype(np.float32))
+            F = frames_final(T, span, hop, centred)
+            want = st._shape(local_frames(torch.nn.functional.pad(x, (span // 2 if centred else 0, 0)), F, span, hop))
+            cuts = []
+            while sum(cuts) < T:
+                cuts.append(min(int(rng.choice(sizes)), T - sum(cuts)))
+            cuts += [0] * (i % 2)   # an empty block after the last sample, every other utterance
+            outs, p = [], 0
+            for n in cuts:
+                st.block = n
+                outs.append(st.push_all(x[:, p:p + n]))
+                p += n
+                assert st.pushed == p and st.framed == sum(o[0].shape[1] for o in outs) <= F
+            st.block = 0
+            outs.append(st.finish_all())
+            assert (st.pushed, st.framed) == (0, 0) and len(outs[0]) == len(want)
+            for j, w in enumerate(want):
+                assert all(o[j].shape[2:] == w.shape[2:] and o[j].dtype == w.dtype for o in outs)   # k = 0 included
+                assert torch.equal(torch.cat([o[j] for o in outs], 1), w), (cls.__name__, T, cuts, j)
+            launches += len(cuts) + 1
+        assert 6 <= st.calls <= launches

@@ -107,6 +107,7 @@ class HostStream(AS.HarmonicNoiseStream):
         with pytest.raises(GolfError, match="no CPU path"):   # the wrapper's own preconditions hold: only the device is missing
             super()._frames(x, f0, x_t0, f_first, f0_first, k, last, phases)
         self.calls.append((x_t0, x.shape[1], f_first, f0_first, f0.shape[1], k, last))
+        assert (x_t0 + x.shape[1], f0_first + f0.shape[1]) == (self.pushed, self.f0_received)   # the buffers end at all that came
         m, B = self.module, self.B
         n_mag = m.n_mag or 0
         if k:
@@ -127,6 +128,19 @@ class HostStream(AS.HarmonicNoiseStream):
             del out[1]
         out = [torch.tensor(np.ascontiguousarray(a)) for a in out]
         return out[0] if len(out) == 1 else tuple(out)
+
+
+def assert_exact_trimming(calls, keep_from):
+    """Every recorded call ``(x_t0, n_x, f_first, f0_first, n_f0, k, last)`` starts its buffers where the call before it left
+    them: at ``keep_from(next frame)`` or, where less had come, at what had come; at 0 in an utterance's first call."""
+    prev = None   # (samples, f0 frames) received at the previous call of the same utterance
+    for x_t0, n_x, f_first, f0_first, n_f0, k, last in calls:
+        if prev is None:
+            assert (x_t0, f0_first) == (0, 0)
+        else:
+            x_from, f_from = keep_from(f_first)
+            assert (x_t0, f0_first) == (min(x_from, prev[0]), min(f_from, prev[1]))
+        prev = None if last else (x_t0 + n_x, f0_first + n_f0)
 
 
 def make_signal(B, T, F, f_lo, f_hi, seed):
@@ -210,6 +224,7 @@ def test_offset_indexing_against_the_float64_restatement(name, mode):
         for g, w in zip(got, want):
             assert g.shape == w.shape and np.array_equal(g, w)
         assert (st.pushed, st.f0_received, st.framed) == (0, 0, 0)
+    assert_exact_trimming(st.calls, lambda nxt: AS.hna_keep_from(nxt, span, hop))
     launches = [c for c in st.calls if c[5]]
     assert len(launches) >= 3 or mode != "mixed"
     # something was dropped on the way: a later call starts above sample 0 and above frame 0
