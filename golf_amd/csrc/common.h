@@ -7,6 +7,7 @@
 
 #include "golf_amd.h"
 #include "lpc_ss_plan.h"   // SsPlan, make_ss_plan, ceil_div, align_up: HIP-free, shared with the host tests
+#include "stream_plan.h"   // RingPlan, ring_plan, frame_position_check: HIP-free, shared with the host tests
 
 namespace golf {
 

@@ -138,5 +138,21 @@ __device__ __forceinline__ float dppf(float v) {
 #define DPP_SHL1 0xF9   /* quad_perm [1,2,3,3]: lane r reads lane r+1 */
 #define DPP_BC0  0x00   /* quad_perm [0,0,0,0]: broadcast lane 0 of the quad */
 
+// ---- the carried (B, S, W) frame ring of the overlap-add streams (stream_plan.h: RingPlan), one frame per workgroup:
+// carried frame j of ncin, ring slot (cin_slot + j) % S -> ws slot S - ncin + j;  new frame j of the last ncout, ws slot
+// nslot - ncout + j -> ring slot (cout_slot + j) % S
+__device__ __forceinline__ void ring_to_ws(const float* ring, float* ws, int b, int j, int S, int W, int nslot, int ncin,
+                                           int cin_slot, int tid, int nthr) {
+    const float* src = ring + ((size_t)b * S + (cin_slot + j) % S) * W;
+    float* dst = ws + ((size_t)b * nslot + S - ncin + j) * W;
+    for (int k = tid; k < W; k += nthr) dst[k] = src[k];
+}
+__device__ __forceinline__ void ws_to_ring(const float* ws, float* ring, int b, int j, int S, int W, int nslot, int ncout,
+                                           int cout_slot, int tid, int nthr) {
+    const float* src = ws + ((size_t)b * nslot + nslot - ncout + j) * W;
+    float* dst = ring + ((size_t)b * S + (cout_slot + j) % S) * W;
+    for (int k = tid; k < W; k += nthr) dst[k] = src[k];
+}
+
 
 }  // namespace golf

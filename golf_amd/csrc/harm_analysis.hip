@@ -271,7 +271,35 @@ static int hna_check_params(const char* who, int K, int n_mag, int hop, int peri
     return GOLF_OK;
 }
 
-static int hna_launch(const HnaArgs& a, void* stream) {
+// the checks both entries share and the launch; `whole`: the one-shot entry, whose buffers are the whole utterance (every
+// frame, read as a `last` call reads it) and whose refusals name T and F
+static int hna_run(const char* who, bool whole, const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* f0,
+                   int64_t f0_stride, int64_t f0_first, int n_f0, float* amplitudes, float* phases, float* log_mag, int B,
+                   int64_t f_first, int n_frames, int last, int K, int n_mag, int hop, int periods, int min_window,
+                   int max_window, int unvoiced_window, int smooth, double sample_rate, double eps, void* stream) {
+    const char *nx = whole ? "T" : "n_x", *nf0 = whole ? "F" : "n_f0", *nfr = whole ? "F" : "n_frames";
+    if (B < 1 || n_x < 0 || n_f0 < 1 || n_frames < 1)
+        return fail(GOLF_EINVAL, "%s: bad size (B=%d %s=%d %s=%d n_frames=%d)", who, B, nx, n_x, nf0, n_f0, n_frames);
+    if ((!x && n_x > 0) || !f0 || !amplitudes)
+        return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p amplitudes=%p)", who, x, f0, amplitudes);
+    if (x_stride < n_x) return fail(GOLF_EINVAL, "%s: row stride of x %lld < %s=%d", who, (long long)x_stride, nx, n_x);
+    if (f0_stride < n_f0) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < %s=%d", who, (long long)f0_stride, nf0, n_f0);
+    if (int rc = hna_check_params(who, K, n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth, sample_rate,
+                                  eps))
+        return rc;
+    if ((int64_t)B * n_frames >= ((int64_t)1 << 31))
+        return fail(GOLF_EINVAL, "%s: B*%s = %lld frames, must be < 2^31", who, nfr, (long long)B * n_frames);
+    const int Lmax = max_window > unvoiced_window ? max_window : unvoiced_window;   // no frame's window is longer
+    if (int rc = frame_position_check(who, x_t0, n_x, f0_first, n_f0, f_first, n_frames, last, hop, Lmax / 2, Lmax - Lmax / 2,
+                                      1, 1))
+        return rc;
+    HnaArgs a;
+    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride;
+    a.amp = amplitudes, a.phases = phases, a.log_mag = log_mag;
+    a.x_t0 = x_t0, a.x_end = x_t0 + n_x, a.f0_first = f0_first, a.f0_end = f0_first + n_f0, a.f_first = f_first;
+    a.G = B * n_frames, a.nf = n_frames, a.K = K, a.n_mag = n_mag, a.hop = hop, a.periods = periods;
+    a.min_window = min_window, a.max_window = max_window, a.unvoiced_window = unvoiced_window, a.smooth = smooth;
+    a.sample_rate = sample_rate, a.eps = eps;
     const int gx = a.G < HNA_GRID_X ? a.G : HNA_GRID_X;
     hipLaunchKernelGGL(harm_analysis_kernel, dim3((unsigned)gx, (unsigned)ceil_div(a.G, gx)), dim3(HNA_THREADS), 0,
                        (hipStream_t)stream, a);
@@ -287,25 +315,8 @@ extern "C" int golf_harmonic_analysis_f32(const float* x, int64_t x_stride, cons
                                           float* amplitudes, float* phases, float* log_mag, int B, int T, int F, int K,
                                           int n_mag, int hop, int periods, int min_window, int max_window,
                                           int unvoiced_window, int smooth, double sample_rate, double eps, void* stream) {
-    const char* who = "harmonic_analysis";
-    if (B < 1 || T < 0 || F < 1) return fail(GOLF_EINVAL, "%s: bad size (B=%d T=%d F=%d)", who, B, T, F);
-    if ((!x && T > 0) || !f0 || !amplitudes)
-        return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p amplitudes=%p)", who, x, f0, amplitudes);
-    if (x_stride < T) return fail(GOLF_EINVAL, "%s: row stride of x %lld < T=%d", who, (long long)x_stride, T);
-    if (f0_stride < F) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < F=%d", who, (long long)f0_stride, F);
-    if (int rc = hna_check_params(who, K, n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth, sample_rate,
-                                  eps))
-        return rc;
-    if ((int64_t)B * F >= ((int64_t)1 << 31))
-        return fail(GOLF_EINVAL, "%s: B*F = %lld frames, must be < 2^31", who, (long long)B * F);
-    HnaArgs a;
-    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride;
-    a.amp = amplitudes, a.phases = phases, a.log_mag = log_mag;
-    a.x_t0 = 0, a.x_end = T, a.f0_first = 0, a.f0_end = F, a.f_first = 0;   // the buffers are the whole utterance
-    a.G = B * F, a.nf = F, a.K = K, a.n_mag = n_mag, a.hop = hop, a.periods = periods, a.min_window = min_window;
-    a.max_window = max_window, a.unvoiced_window = unvoiced_window, a.smooth = smooth;
-    a.sample_rate = sample_rate, a.eps = eps;
-    return hna_launch(a, stream);
+    return hna_run("harmonic_analysis", true, x, x_stride, 0, T, f0, f0_stride, 0, F, amplitudes, phases, log_mag, B, 0, F, 1, K,
+                   n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth, sample_rate, eps, stream);
 }
 
 extern "C" int golf_harmonic_analysis_stream_f32(const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* f0,
@@ -314,51 +325,7 @@ extern "C" int golf_harmonic_analysis_stream_f32(const float* x, int64_t x_strid
                                                  int last, int K, int n_mag, int hop, int periods, int min_window,
                                                  int max_window, int unvoiced_window, int smooth, double sample_rate,
                                                  double eps, void* stream) {
-    const char* who = "harmonic_analysis_stream";
-    const int64_t far = (int64_t)1 << 62;   // positions stay below it, so that no sum or product here or in the kernel wraps
-    if (B < 1 || n_x < 0 || n_f0 < 1 || n_frames < 1)
-        return fail(GOLF_EINVAL, "%s: bad size (B=%d n_x=%d n_f0=%d n_frames=%d)", who, B, n_x, n_f0, n_frames);
-    if ((!x && n_x > 0) || !f0 || !amplitudes)
-        return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p amplitudes=%p)", who, x, f0, amplitudes);
-    if (x_stride < n_x) return fail(GOLF_EINVAL, "%s: row stride of x %lld < n_x=%d", who, (long long)x_stride, n_x);
-    if (f0_stride < n_f0) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < n_f0=%d", who, (long long)f0_stride, n_f0);
-    if (int rc = hna_check_params(who, K, n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth, sample_rate,
-                                  eps))
-        return rc;
-    if ((int64_t)B * n_frames >= ((int64_t)1 << 31))
-        return fail(GOLF_EINVAL, "%s: B*n_frames = %lld frames, must be < 2^31", who, (long long)B * n_frames);
-    if (x_t0 < 0 || x_t0 > far) return fail(GOLF_EINVAL, "%s: x_t0=%lld must be 0..2^62", who, (long long)x_t0);
-    if (f0_first < 0 || f0_first > far)
-        return fail(GOLF_EINVAL, "%s: f0_first=%lld must be 0..2^62", who, (long long)f0_first);
-    if (f_first < 0 || f_first > far / hop - n_frames)
-        return fail(GOLF_EINVAL, "%s: f_first=%lld must be >= 0 with (f_first + n_frames) hop <= 2^62", who,
-                    (long long)f_first);
-    const int Lmax = max_window > unvoiced_window ? max_window : unvoiced_window;   // no frame's window is longer
-    const int64_t lo = f_first * hop - Lmax / 2, f_end = f_first + n_frames;
-    const int64_t x_end = x_t0 + n_x, f0_end = f0_first + n_f0;
-    if (x_t0 > (lo > 0 ? lo : 0))
-        return fail(GOLF_EINVAL, "%s: x_t0=%lld lies above sample %lld, where the window of frame f_first=%lld may start", who,
-                    (long long)x_t0, (long long)(lo > 0 ? lo : 0), (long long)f_first);
-    if (f0_first > (f_first > 0 ? f_first - 1 : 0))
-        return fail(GOLF_EINVAL, "%s: f0_first=%lld lies above frame %lld, the neighbour before f_first=%lld", who,
-                    (long long)f0_first, (long long)(f_first > 0 ? f_first - 1 : 0), (long long)f_first);
-    if (f_end > f0_end)
-        return fail(GOLF_EINVAL, "%s: n_f0=%d: f0 ends at frame %lld, before the last computed frame %lld", who, n_f0,
-                    (long long)f0_end, (long long)(f_end - 1));
-    if (!last && (f_end - 1) * hop + (Lmax - Lmax / 2) > x_end)
-        return fail(GOLF_EINVAL, "%s: n_x=%d: x ends at sample %lld, before the window of frame %lld may end (%lld) and "
-                    "last is not set", who, n_x, (long long)x_end, (long long)(f_end - 1),
-                    (long long)((f_end - 1) * hop + (Lmax - Lmax / 2)));
-    if (!last && f_end + 1 > f0_end)
-        return fail(GOLF_EINVAL, "%s: n_f0=%d: f0 ends at frame %lld, without the neighbour after frame %lld, and last is "
-                    "not set", who, n_f0, (long long)f0_end, (long long)(f_end - 1));
-    HnaArgs a;
-    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride;
-    a.amp = amplitudes, a.phases = phases, a.log_mag = log_mag;
-    a.x_t0 = x_t0, a.x_end = x_end, a.f0_first = f0_first, a.f0_end = f0_end, a.f_first = f_first;
-    a.G = B * n_frames, a.nf = n_frames, a.K = K, a.n_mag = n_mag, a.hop = hop, a.periods = periods;
-    a.min_window = min_window, a.max_window = max_window, a.unvoiced_window = unvoiced_window, a.smooth = smooth;
-    a.sample_rate = sample_rate, a.eps = eps;
-    return hna_launch(a, stream);
+    return hna_run("harmonic_analysis_stream", false, x, x_stride, x_t0, n_x, f0, f0_stride, f0_first, n_f0, amplitudes, phases,
+                   log_mag, B, f_first, n_frames, last, K, n_mag, hop, periods, min_window, max_window, unvoiced_window, smooth,
+                   sample_rate, eps, stream);
 }
-

@@ -1257,12 +1257,6 @@ __device__ __forceinline__ float ff_stream_gain(const FfStreamArgs& p, const flo
     return fmaf((float)n, (g1 - g0) * inv_hop, g0);
 }
 
-__device__ __forceinline__ void ff_stream_copy_in(const FfStreamArgs& p, int j, int b, int tid, int nthr) {
-    const float* src = p.carry + ((size_t)b * p.S + (p.cin_slot + j) % p.S) * p.W;
-    float* dst = p.ws + ((size_t)b * (p.S + p.nf) + p.S - p.ncin + j) * p.W;
-    for (int k = tid; k < p.W; k += nthr) dst[k] = src[k];
-}
-
 // Block recursion of ff_framesb_kernel<NT, false>, frames from the windows of FfStreamArgs, the conditioning tier per frame.
 // grid (ceil(nf / 4) + ncin, B), 64 threads, dynamic LDS = the staged inputs U[3 hop + W].
 template <int NT>
@@ -1278,7 +1272,7 @@ __global__ __launch_bounds__(64) void ff_stream_framesb_kernel(FfStreamArgs p, f
     const int b = blockIdx.y;
     const int nw = (p.nf + 3) / 4;
     if ((int)blockIdx.x >= nw) {
-        ff_stream_copy_in(p, blockIdx.x - nw, b, lane, 64);
+        ring_to_ws(p.carry, p.ws, b, blockIdx.x - nw, p.S, p.W, p.S + p.nf, p.ncin, p.cin_slot, lane, 64);
         return;
     }
     const int hop = p.hop, Wl = p.W;
@@ -1438,7 +1432,7 @@ __global__ __launch_bounds__(64) void ff_stream_frames_kernel(FfStreamArgs p) {
     const int b = blockIdx.y;
     const int nw = (p.nf + 63) / 64;
     if ((int)blockIdx.x >= nw) {
-        ff_stream_copy_in(p, blockIdx.x - nw, b, threadIdx.x, 64);
+        ring_to_ws(p.carry, p.ws, b, blockIdx.x - nw, p.S, p.W, p.S + p.nf, p.ncin, p.cin_slot, threadIdx.x, 64);
         return;
     }
     const int fl = blockIdx.x * 64 + threadIdx.x;
@@ -1482,10 +1476,7 @@ __global__ __launch_bounds__(256) void ff_stream_ola_kernel(const float* __restr
     const int b = blockIdx.y;
     const int nob = (ny + 255) / 256;
     if ((int)blockIdx.x >= nob) {
-        const int j = blockIdx.x - nob;
-        const float* src = ws + ((size_t)b * nslot + nslot - ncout + j) * Wl;
-        float* dst = carry + ((size_t)b * S + (cout_slot + j) % S) * Wl;
-        for (int k = threadIdx.x; k < Wl; k += 256) dst[k] = src[k];
+        ws_to_ring(ws, carry, b, blockIdx.x - nob, S, Wl, nslot, ncout, cout_slot, threadIdx.x, 256);
         return;
     }
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1527,13 +1518,11 @@ __global__ __launch_bounds__(256) void ff_stream_ola_kernel(const float* __restr
     y[(size_t)b * y_stride + i] = acc / norm;
 }
 
-static int ff_stream_S(int W, int hop) { return (W + hop - 1) / hop - 1; }
-
 }  // namespace golf
 
 extern "C" size_t golf_lti_frames_stream_state_bytes(int B, int W, int hop, int M) {
     if (B < 1 || hop < 1 || W < 2 * hop || M < 1 || M > 38) return 0;
-    return sizeof(float) * (size_t)B * ff_stream_S(W, hop) * W;
+    return ring_state_bytes(B, W, hop);
 }
 
 extern "C" int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride, int64_t x0, int nx, int64_t x_end,
@@ -1552,8 +1541,8 @@ extern "C" int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride
         return fail(GOLF_EINVAL, "lti_frames_stream: x_end and g_end are both open (< 0) or both set");
     const bool fin = x_end >= 0;
     const int64_t pad = W / 2, H = hop;
-    const int S = ff_stream_S(W, hop);
-    int64_t nfr = INT64_MAX, Ty = INT64_MAX;
+    const int S = ring_S(W, hop);
+    int64_t nfr = kRingOpen, Ty = kRingOpen;
     if (fin) {
         if (x_end < 1 || g_end < 2) return fail(GOLF_EINVAL, "lti_frames_stream: x_end %lld, g_end %lld (need >= 1, >= 2)",
                                                 (long long)x_end, (long long)g_end);
@@ -1562,8 +1551,7 @@ extern "C" int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride
         Ty = (nfr - 1) * H + W - 2 * pad;
         if (nfr < 1 || nfr > g_end) return fail(GOLF_EINVAL, "lti_frames_stream: %lld frames vs %lld coefficient frames",
                                                 (long long)nfr, (long long)g_end);
-        if (f0 + nf > nfr) return fail(GOLF_EINVAL, "lti_frames_stream: frames past the last one (%lld)", (long long)nfr);
-        if (n0 + ny > Ty) return fail(GOLF_EINVAL, "lti_frames_stream: samples past the end (%lld)", (long long)Ty);
+        if (int rc = ring_check_end("lti_frames_stream", f0, nf, n0, ny, nfr, Ty)) return rc;
     }
     if ((nf > 0 && nx > 0 && ex_stride < nx) || (ny > 0 && y_stride < ny))
         return fail(GOLF_EINVAL, "lti_frames_stream: row stride too small");
@@ -1583,25 +1571,8 @@ extern "C" int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride
                 return fail(GOLF_EINVAL, "lti_frames_stream: the gain window does not cover the frames' samples");
         }
     }
-    // samples [n0, n0+ny): every frame they need is filtered by now, and the carried ring still holds the earliest one
-    auto flo = [&](int64_t n) { const int64_t d = n + pad - W + 1; return d <= 0 ? (int64_t)0 : (d + H - 1) / H; };
-    const int64_t fdone = f0 + nf;
-    if (ny > 0) {
-        const int64_t fhi = std::min((n0 + ny - 1 + pad) / H, nfr - 1);
-        if (fhi >= fdone) return fail(GOLF_EINVAL, "lti_frames_stream: sample %lld needs frame %lld, not filtered yet",
-                                      (long long)(n0 + ny - 1), (long long)fhi);
-        if (flo(n0) < f0 - S) return fail(GOLF_EINVAL, "lti_frames_stream: sample %lld needs frame %lld; the carry holds "
-                                          "frames from %lld", (long long)n0, (long long)flo(n0), (long long)(f0 - S));
-    }
-    if (nf > 0 && n0 > std::max<int64_t>(0, f0 * H - pad))
-        return fail(GOLF_EINVAL, "lti_frames_stream: samples before %lld were written without frame %lld", (long long)n0,
-                    (long long)f0);
-    if (!(fin && n0 + ny == Ty) && flo(n0 + ny) < fdone - S)
-        return fail(GOLF_EINVAL, "lti_frames_stream: write the samples up to %lld before filtering frame %lld (the carry "
-                    "holds %d frames)", (long long)((fdone - S) * H - pad + W - 1), (long long)(fdone - 1), S);
-    const size_t need = sizeof(float) * (size_t)B * (S + nf) * W;
-    if ((nf > 0 || ny > 0) && (ws_bytes < need || ((uintptr_t)ws & 255)))
-        return fail(GOLF_EWORKSPACE, "lti_frames_stream: workspace needs %zu bytes, 256-aligned (got %zu)", need, ws_bytes);
+    RingPlan r;
+    if (int rc = ring_plan("lti_frames_stream", W, hop, f0, nf, n0, ny, nfr, Ty, B, ws, ws_bytes, &r)) return rc;
     if (nf == 0 && ny == 0) return GOLF_OK;
     hipStream_t st = (hipStream_t)stream;
     FfStreamArgs p;
@@ -1625,8 +1596,7 @@ extern "C" int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride
     p.hop = hop;
     p.W = W;
     p.carry = carry;
-    p.ncin = ny > 0 ? (int)std::min<int64_t>(S, f0) : 0;
-    p.cin_slot = (int)((f0 - p.ncin) % S);
+    p.ncin = r.ncin, p.cin_slot = r.cin_slot;
     p.ws = (float*)ws;
     // the one-shot's kernel choice: the first (ring, taps) with M <= taps and ring <= hop, the block recursion where it fits
     int nt_ring = 0;
@@ -1659,15 +1629,10 @@ extern "C" int golf_lti_frames_ola_stream_f32(const float* ex, int64_t ex_stride
         }
         GOLF_LAUNCH_CHECK();
     }
-    const int ncout = (int)std::min<int64_t>(S, nf);
-    if (ny > 0 || ncout > 0) {
-        const int64_t fbase = f0 - S;
-        const int mb = (int)(n0 + pad - fbase * H);
-        const int fmin = (int)std::max<int64_t>(0, -fbase);
-        const int fmax = (int)(std::min<int64_t>(fdone, nfr) - 1 - fbase);
-        hipLaunchKernelGGL(ff_stream_ola_kernel, dim3((unsigned)(ceil_div(ny, 256) + ncout), B), dim3(256), 0, st,
-                           (const float*)ws, window, y, y_stride, carry, ny, mb, fmin, fmax, S + nf, hop, W, S, ncout,
-                           (int)((fdone - ncout) % S));
+    if (ny > 0 || r.ncout > 0) {
+        hipLaunchKernelGGL(ff_stream_ola_kernel, dim3((unsigned)(ceil_div(ny, 256) + r.ncout), B), dim3(256), 0, st,
+                           (const float*)ws, window, y, y_stride, carry, ny, r.mb, r.fmin, r.fmax, r.nslot, hop, W, S, r.ncout,
+                           r.cout_slot);
         GOLF_LAUNCH_CHECK();
     }
     return GOLF_OK;

@@ -219,8 +219,30 @@ static int env_check_params(const char* who, int n_fft, int n_ceps, int hop, dou
     return GOLF_OK;
 }
 
-static int env_launch(EnvArgs& a, int B, int n_frames, int n_fft, int n_ceps, int hop, double sample_rate, double f0_floor,
-                      double f0_ceil, double unvoiced_f0, double q1, double eps, double voiced_offset, void* stream) {
+// the checks both entries share and the launch; `whole`: the one-shot entry, whose buffers are the whole utterance (every
+// frame, read as a `last` call reads it) and whose refusals name T and F
+static int env_run(const char* who, bool whole, const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* f0,
+                   int64_t f0_stride, int64_t f0_first, int n_f0, float* log_env, float* ceps, int B, int64_t f_first,
+                   int n_frames, int last, int n_fft, int n_ceps, int hop, double sample_rate, double f0_floor, double f0_ceil,
+                   double unvoiced_f0, double q1, double eps, double voiced_offset, void* stream) {
+    const char *nx = whole ? "T" : "n_x", *nf0 = whole ? "F" : "n_f0", *nfr = whole ? "F" : "n_frames";
+    if (B < 1 || n_x < 0 || n_f0 < 1 || n_frames < 1)
+        return fail(GOLF_EINVAL, "%s: bad size (B=%d %s=%d %s=%d n_frames=%d)", who, B, nx, n_x, nf0, n_f0, n_frames);
+    if ((!x && n_x > 0) || !f0) return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p)", who, x, f0);
+    if (!log_env && !ceps) return fail(GOLF_EINVAL, "%s: null pointer: log_env and ceps are both NULL", who);
+    if (ceps && n_ceps == 0) return fail(GOLF_EINVAL, "%s: n_ceps=0 with a ceps output", who);
+    if (x_stride < n_x) return fail(GOLF_EINVAL, "%s: row stride of x %lld < %s=%d", who, (long long)x_stride, nx, n_x);
+    if (f0_stride < n_f0) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < %s=%d", who, (long long)f0_stride, nf0, n_f0);
+    if (int rc = env_check_params(who, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset))
+        return rc;
+    if ((int64_t)B * n_frames >= ((int64_t)1 << 31))
+        return fail(GOLF_EINVAL, "%s: B*%s = %lld frames, must be < 2^31", who, nfr, (long long)B * n_frames);
+    const int64_t hwmax = (int64_t)floor(1.5 * sample_rate / f0_floor + 0.5);   // <= n_fft/2 - 1: no frame's half window is longer
+    if (int rc = frame_position_check(who, x_t0, n_x, f0_first, n_f0, f_first, n_frames, last, hop, hwmax, hwmax + 1, 0, 0))
+        return rc;
+    EnvArgs a;
+    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride, a.log_env = log_env, a.ceps = ceps;
+    a.x_t0 = x_t0, a.x_end = x_t0 + n_x, a.f0_first = f0_first, a.f_first = f_first;
     a.G = B * n_frames, a.F = n_frames, a.n = n_fft, a.log2n = __builtin_ctz((unsigned)n_fft), a.n_ceps = n_ceps, a.hop = hop;
     a.sample_rate = sample_rate, a.f0_floor = f0_floor, a.f0_ceil = f0_ceil, a.unvoiced_f0 = unvoiced_f0, a.q1 = q1;
     a.voiced_offset = voiced_offset, a.eps = (float)eps;
@@ -239,21 +261,8 @@ extern "C" int golf_spectral_envelope_f32(const float* x, int64_t x_stride, cons
                                           float* log_env, float* ceps, int B, int T, int F, int n_fft, int n_ceps, int hop,
                                           double sample_rate, double f0_floor, double f0_ceil, double unvoiced_f0, double q1,
                                           double eps, double voiced_offset, void* stream) {
-    const char* who = "spectral_envelope";
-    if (B < 1 || T < 0 || F < 1) return fail(GOLF_EINVAL, "%s: bad size (B=%d T=%d F=%d)", who, B, T, F);
-    if ((!x && T > 0) || !f0) return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p)", who, x, f0);
-    if (!log_env && !ceps) return fail(GOLF_EINVAL, "%s: null pointer: log_env and ceps are both NULL", who);
-    if (ceps && n_ceps == 0) return fail(GOLF_EINVAL, "%s: n_ceps=0 with a ceps output", who);
-    if (x_stride < T) return fail(GOLF_EINVAL, "%s: row stride of x %lld < T=%d", who, (long long)x_stride, T);
-    if (f0_stride < F) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < F=%d", who, (long long)f0_stride, F);
-    if (int rc = env_check_params(who, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset))
-        return rc;
-    if ((int64_t)B * F >= ((int64_t)1 << 31))
-        return fail(GOLF_EINVAL, "%s: B*F = %lld frames, must be < 2^31", who, (long long)B * F);
-    EnvArgs a;
-    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride, a.log_env = log_env, a.ceps = ceps;
-    a.x_t0 = 0, a.x_end = T, a.f0_first = 0, a.f_first = 0;   // the buffers are the whole utterance
-    return env_launch(a, B, F, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset, stream);
+    return env_run("spectral_envelope", true, x, x_stride, 0, T, f0, f0_stride, 0, F, log_env, ceps, B, 0, F, 1, n_fft, n_ceps,
+                   hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset, stream);
 }
 
 extern "C" int golf_spectral_envelope_stream_f32(const float* x, int64_t x_stride, int64_t x_t0, int n_x, const float* f0,
@@ -261,45 +270,7 @@ extern "C" int golf_spectral_envelope_stream_f32(const float* x, int64_t x_strid
                                                  int B, int64_t f_first, int n_frames, int last, int n_fft, int n_ceps, int hop,
                                                  double sample_rate, double f0_floor, double f0_ceil, double unvoiced_f0,
                                                  double q1, double eps, double voiced_offset, void* stream) {
-    const char* who = "spectral_envelope_stream";
-    const int64_t far = (int64_t)1 << 62;   // positions stay below it, so that no sum or product here or in the kernel wraps
-    if (B < 1 || n_x < 0 || n_f0 < 1 || n_frames < 1)
-        return fail(GOLF_EINVAL, "%s: bad size (B=%d n_x=%d n_f0=%d n_frames=%d)", who, B, n_x, n_f0, n_frames);
-    if ((!x && n_x > 0) || !f0) return fail(GOLF_EINVAL, "%s: null pointer (x=%p f0=%p)", who, x, f0);
-    if (!log_env && !ceps) return fail(GOLF_EINVAL, "%s: null pointer: log_env and ceps are both NULL", who);
-    if (ceps && n_ceps == 0) return fail(GOLF_EINVAL, "%s: n_ceps=0 with a ceps output", who);
-    if (x_stride < n_x) return fail(GOLF_EINVAL, "%s: row stride of x %lld < n_x=%d", who, (long long)x_stride, n_x);
-    if (f0_stride < n_f0) return fail(GOLF_EINVAL, "%s: row stride of f0 %lld < n_f0=%d", who, (long long)f0_stride, n_f0);
-    if (int rc = env_check_params(who, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset))
-        return rc;
-    if ((int64_t)B * n_frames >= ((int64_t)1 << 31))
-        return fail(GOLF_EINVAL, "%s: B*n_frames = %lld frames, must be < 2^31", who, (long long)B * n_frames);
-    if (x_t0 < 0 || x_t0 > far) return fail(GOLF_EINVAL, "%s: x_t0=%lld must be 0..2^62", who, (long long)x_t0);
-    if (f0_first < 0 || f0_first > far)
-        return fail(GOLF_EINVAL, "%s: f0_first=%lld must be 0..2^62", who, (long long)f0_first);
-    if (f_first < 0 || f_first > far / hop - n_frames)
-        return fail(GOLF_EINVAL, "%s: f_first=%lld must be >= 0 with (f_first + n_frames) hop <= 2^62", who,
-                    (long long)f_first);
-    const int64_t hwmax = (int64_t)floor(1.5 * sample_rate / f0_floor + 0.5);   // <= n_fft/2 - 1: no frame's half window is longer
-    const int64_t lo = f_first * hop - hwmax > 0 ? f_first * hop - hwmax : 0, f_end = f_first + n_frames;
-    const int64_t x_end = x_t0 + n_x, f0_end = f0_first + n_f0;
-    if (x_t0 > lo)
-        return fail(GOLF_EINVAL, "%s: x_t0=%lld lies above sample %lld, where the window of frame f_first=%lld may start", who,
-                    (long long)x_t0, (long long)lo, (long long)f_first);
-    if (f0_first > f_first)
-        return fail(GOLF_EINVAL, "%s: f0_first=%lld lies above the first computed frame f_first=%lld", who, (long long)f0_first,
-                    (long long)f_first);
-    if (f_end > f0_end)
-        return fail(GOLF_EINVAL, "%s: n_f0=%d: f0 ends at frame %lld, before the last computed frame %lld", who, n_f0,
-                    (long long)f0_end, (long long)(f_end - 1));
-    if (!last && (f_end - 1) * hop + hwmax + 1 > x_end)
-        return fail(GOLF_EINVAL, "%s: n_x=%d: x ends at sample %lld, before the window of frame %lld may end (%lld) and "
-                    "last is not set", who, n_x, (long long)x_end, (long long)(f_end - 1),
-                    (long long)((f_end - 1) * hop + hwmax + 1));
-    EnvArgs a;
-    a.x = x, a.x_stride = x_stride, a.f0 = f0, a.f0_stride = f0_stride, a.log_env = log_env, a.ceps = ceps;
-    a.x_t0 = x_t0, a.x_end = x_end, a.f0_first = f0_first, a.f_first = f_first;
-    return env_launch(a, B, n_frames, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps, voiced_offset,
-                      stream);
+    return env_run("spectral_envelope_stream", false, x, x_stride, x_t0, n_x, f0, f0_stride, f0_first, n_f0, log_env, ceps, B,
+                   f_first, n_frames, last, n_fft, n_ceps, hop, sample_rate, f0_floor, f0_ceil, unvoiced_f0, q1, eps,
+                   voiced_offset, stream);
 }
-

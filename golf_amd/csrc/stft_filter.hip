@@ -7,7 +7,7 @@
 //   u_f     = Re IFFT(FFT(w * frame_f) * H_f),  H_f given on bins 0 .. n/2 and extended by Hermitian symmetry
 //   y[m]    = sum_f w[k] u_f[k] / sum_f w[k]^2,  k = m + n/2 - f*hop, over the frames 0 <= f < frames that cover m
 //
-// Two launches, the layout of golf_lti_frames_ola_stream_f32 (lpc_ff.hip):
+// Two launches over the ring and workspace layout of stream_plan.h (RingPlan), as golf_lti_frames_ola_stream_f32 (lpc_ff.hip):
 //   frames   the new frames into ws[b][S + f - f0], plus (extra blocks) the carried frames [f0 - S, f0) ring -> ws[b][0 .. S)
 //   OLA      the output samples from ws alone, frames in ascending f with fmaf (the synthesis window is applied here, so a
 //            frame is rounded once), plus (extra blocks) the last min(S, nf) new frames ws -> ring
@@ -29,6 +29,7 @@
 #include <climits>
 
 #include "common.h"
+#include "device_common.h"
 
 namespace golf {
 
@@ -135,10 +136,7 @@ __global__ __launch_bounds__(512) void stft_frames_kernel(StftArgs p) {
     const int b = blockIdx.y;
     const int nblk = (p.nf + p.fpb - 1) / p.fpb;
     if ((int)blockIdx.x >= nblk) {
-        const int jc = blockIdx.x - nblk;
-        const float* src = p.carry + ((size_t)b * p.S + (p.cin_slot + jc) % p.S) * n;
-        float* dst = p.ws + ((size_t)b * (p.S + p.nf) + p.S - p.ncin + jc) * n;
-        for (int k = threadIdx.x; k < n; k += blockDim.x) dst[k] = src[k];
+        ring_to_ws(p.carry, p.ws, b, blockIdx.x - nblk, p.S, n, p.S + p.nf, p.ncin, p.cin_slot, threadIdx.x, blockDim.x);
         return;
     }
     const int P = n + (n >> 3);
@@ -218,10 +216,7 @@ __global__ __launch_bounds__(256) void stft_ola_kernel(const float* __restrict__
     const int b = blockIdx.y;
     const int nob = (ny + 255) / 256;
     if ((int)blockIdx.x >= nob) {
-        const int jc = blockIdx.x - nob;
-        const float* src = ws + ((size_t)b * nslot + nslot - ncout + jc) * n;
-        float* dst = carry + ((size_t)b * S + (cout_slot + jc) % S) * n;
-        for (int k = threadIdx.x; k < n; k += 256) dst[k] = src[k];
+        ws_to_ring(ws, carry, b, blockIdx.x - nob, S, n, nslot, ncout, cout_slot, threadIdx.x, 256);
         return;
     }
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -433,8 +428,6 @@ static int stft_log2(int n) {   // log2 n for a power of two in [64, 2048], else
     return 0;
 }
 
-static int stft_S(int n, int hop) { return (n + hop - 1) / hop - 1; }
-
 // The one-shot geometry the backward takes (what the forward takes with the end markers set), else an error code.
 static int stft_bwd_geometry(int B, int T, int F, int n_fft, int hop, bool report) {
     auto no = [&](int code, const char* msg) { return report ? fail(code, "stft_filter_frames_bwd: %s", msg) : code; };
@@ -454,7 +447,7 @@ using namespace golf;
 
 extern "C" size_t golf_stft_filter_stream_state_bytes(int B, int n_fft, int hop) {
     if (B < 1 || hop < 1 || !stft_log2(n_fft) || n_fft < 2 * hop) return 0;
-    return sizeof(float) * (size_t)B * stft_S(n_fft, hop) * n_fft;
+    return ring_state_bytes(B, n_fft, hop);
 }
 
 extern "C" int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stride, int64_t x0, int nx, int64_t x_end,
@@ -474,8 +467,8 @@ extern "C" int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stri
         return fail(GOLF_EINVAL, "stft_filter_stream: x_end and frames_end are both open (< 0) or both set");
     const bool fin = x_end >= 0;
     const int64_t W = n_fft, pad = n_fft / 2, H = hop;
-    const int S = stft_S(n_fft, hop);
-    int64_t nfr = INT64_MAX, Ty = INT64_MAX;
+    const int S = ring_S(n_fft, hop);
+    int64_t nfr = kRingOpen, Ty = kRingOpen;
     if (fin) {
         if (x_end <= pad) return fail(GOLF_EINVAL, "stft_filter_stream: x_end %lld cannot be reflect-padded by n_fft/2 = %lld",
                                       (long long)x_end, (long long)pad);
@@ -484,8 +477,7 @@ extern "C" int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stri
                         (long long)frames_end, (long long)(1 + x_end / H));
         nfr = frames_end;
         Ty = (nfr - 1) * H;
-        if (f0 + nf > nfr) return fail(GOLF_EINVAL, "stft_filter_stream: frames past the last one (%lld)", (long long)nfr);
-        if (n0 + ny > Ty) return fail(GOLF_EINVAL, "stft_filter_stream: samples past the end (%lld)", (long long)Ty);
+        if (int rc = ring_check_end("stft_filter_stream", f0, nf, n0, ny, nfr, Ty)) return rc;
     }
     if ((nf > 0 && nx > 0 && x_stride < nx) || (ny > 0 && y_stride < ny))
         return fail(GOLF_EINVAL, "stft_filter_stream: row stride too small");
@@ -508,25 +500,8 @@ extern "C" int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stri
             return fail(GOLF_EINVAL, "stft_filter_stream: the input window does not cover samples [%lld, %lld]",
                         (long long)lo, (long long)hi);
     }
-    // samples [n0, n0+ny): every frame they need is filtered by now, and the carried ring still holds the earliest one
-    auto flo = [&](int64_t m) { const int64_t d = m + pad - W + 1; return d <= 0 ? (int64_t)0 : (d + H - 1) / H; };
-    const int64_t fdone = f0 + nf;
-    if (ny > 0) {
-        const int64_t fhi = std::min((n0 + ny - 1 + pad) / H, nfr - 1);
-        if (fhi >= fdone) return fail(GOLF_EINVAL, "stft_filter_stream: sample %lld needs frame %lld, not filtered yet",
-                                      (long long)(n0 + ny - 1), (long long)fhi);
-        if (flo(n0) < f0 - S) return fail(GOLF_EINVAL, "stft_filter_stream: sample %lld needs frame %lld; the carry holds "
-                                          "frames from %lld", (long long)n0, (long long)flo(n0), (long long)(f0 - S));
-    }
-    if (nf > 0 && n0 > std::max<int64_t>(0, f0 * H - pad))
-        return fail(GOLF_EINVAL, "stft_filter_stream: samples before %lld were written without frame %lld", (long long)n0,
-                    (long long)f0);
-    if (!(fin && n0 + ny == Ty) && flo(n0 + ny) < fdone - S)
-        return fail(GOLF_EINVAL, "stft_filter_stream: write the samples up to %lld before filtering frame %lld (the carry "
-                    "holds %d frames)", (long long)((fdone - S) * H - pad + W - 1), (long long)(fdone - 1), S);
-    const size_t need = sizeof(float) * (size_t)B * (S + nf) * W;
-    if ((nf > 0 || ny > 0) && (ws_bytes < need || ((uintptr_t)ws & 255)))
-        return fail(GOLF_EWORKSPACE, "stft_filter_stream: workspace needs %zu bytes, 256-aligned (got %zu)", need, ws_bytes);
+    RingPlan r;
+    if (int rc = ring_plan("stft_filter_stream", n_fft, hop, f0, nf, n0, ny, nfr, Ty, B, ws, ws_bytes, &r)) return rc;
     if (nf == 0 && ny == 0) return GOLF_OK;
     hipStream_t st = (hipStream_t)stream;
     const int lim = 1 << 30;
@@ -548,8 +523,7 @@ extern "C" int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stri
     p.lg = lg;
     p.fpb = n_fft >= 256 ? 1 : 256 / n_fft;   // 64-lane blocks at least
     p.carry = carry;
-    p.ncin = ny > 0 ? (int)std::min<int64_t>(S, f0) : 0;
-    p.cin_slot = p.ncin ? (int)((f0 - p.ncin) % S) : 0;
+    p.ncin = r.ncin, p.cin_slot = r.cin_slot;
     p.ws = (float*)ws;
     if (nf > 0 || p.ncin > 0) {
         const int threads = p.fpb * (n_fft / 4);
@@ -557,15 +531,10 @@ extern "C" int golf_stft_filter_frames_stream_f32(const float* x, int64_t x_stri
         hipLaunchKernelGGL(stft_frames_kernel, dim3((unsigned)(ceil_div(nf, p.fpb) + p.ncin), B), dim3(threads), ldsb, st, p);
         GOLF_LAUNCH_CHECK();
     }
-    const int ncout = (int)std::min<int64_t>(S, nf);
-    if (ny > 0 || ncout > 0) {
-        const int64_t fbase = f0 - S;
-        const int mb = (int)(n0 + pad - fbase * H);
-        const int fmin = (int)std::max<int64_t>(0, -fbase);
-        const int fmax = (int)(std::min<int64_t>(fdone, nfr) - 1 - fbase);
-        hipLaunchKernelGGL(stft_ola_kernel, dim3((unsigned)(ceil_div(ny, 256) + ncout), B), dim3(256), 0, st,
-                           (const float*)ws, window, y, y_stride, carry, ny, mb, fmin, fmax, S + nf, hop, n_fft, S, ncout,
-                           ncout ? (int)((fdone - ncout) % S) : 0);
+    if (ny > 0 || r.ncout > 0) {
+        hipLaunchKernelGGL(stft_ola_kernel, dim3((unsigned)(ceil_div(ny, 256) + r.ncout), B), dim3(256), 0, st,
+                           (const float*)ws, window, y, y_stride, carry, ny, r.mb, r.fmin, r.fmax, r.nslot, hop, n_fft, S,
+                           r.ncout, r.cout_slot);
         GOLF_LAUNCH_CHECK();
     }
     return GOLF_OK;

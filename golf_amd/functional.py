@@ -1591,12 +1591,29 @@ def lti_frames_ola(ex, gain, a, window, hop: int) -> torch.Tensor:
     return _LTIFramesOLA.apply(ex, gain, a, window, int(hop))
 
 
+def _ola_carry(nbytes: int, B: int, W: int, device) -> torch.Tensor:
+    return torch.zeros(int(B), nbytes // (4 * int(B) * int(W)), int(W), dtype=torch.float32, device=device)
+
+
+def _ola_stream_tail(who, carry, make_carry, geometry, nf, ny, device):
+    """What the two overlap-add stream entries share once their inputs are checked: the carry (``make_carry(*geometry,
+    device)`` when None, geometry = (B, W, ...)), the (B, ny) output and the (B, S + nf, W) workspace (None for an empty call)."""
+    B, W = geometry[:2]
+    if carry is None:
+        carry = make_carry(*geometry, device)
+    if not carry.is_cuda or carry.dtype != torch.float32 or not carry.is_contiguous() or carry.shape[0] != B:
+        raise _lib.GolfError(f"{who}: carry {tuple(carry.shape)} {carry.dtype} (from {make_carry.__name__})")
+    y = torch.empty(B, int(ny), dtype=torch.float32, device=device)
+    ws = _workspace(4 * B * (carry.shape[1] + int(nf)) * W, device) if nf > 0 or ny > 0 else None
+    return carry, y, ws
+
+
 def lti_frames_stream_carry(B: int, W: int, hop: int, M: int, device) -> torch.Tensor:
     """The zeroed (B, ceil(W/hop) - 1, W) fp32 carry of ``lti_frames_ola_stream``: the last filtered frames."""
     nbytes = _lib.load().golf_lti_frames_stream_state_bytes(int(B), int(W), int(hop), int(M))
     if nbytes == 0:
         raise _lib.GolfError(f"lti_frames_ola_stream: no carry for B={B}, W={W}, hop={hop}, M={M} (W >= 2*hop, M <= 38)")
-    return torch.zeros(int(B), nbytes // (4 * int(B) * int(W)), int(W), dtype=torch.float32, device=device)
+    return _ola_carry(nbytes, B, W, device)
 
 
 def lti_frames_ola_stream(ex, gain, a, window, hop: int, carry=None, *, x0: int, g0: int, a0: int, f0: int, nf: int,
@@ -1614,13 +1631,7 @@ def lti_frames_ola_stream(ex, gain, a, window, hop: int, carry=None, *, x0: int,
     M, W = a.shape[2], window.numel()
     if gain.shape[0] != B or a.shape[0] != B or gain.ndim != 2:
         raise _lib.GolfError(f"lti_frames_ola_stream: ex {tuple(ex.shape)}, gain {tuple(gain.shape)}, a {tuple(a.shape)}")
-    if carry is None:
-        carry = lti_frames_stream_carry(B, W, hop, M, ex.device)
-    if not carry.is_cuda or carry.dtype != torch.float32 or not carry.is_contiguous() or carry.shape[0] != B:
-        raise _lib.GolfError(f"lti_frames_ola_stream: carry {tuple(carry.shape)} {carry.dtype} (from lti_frames_stream_carry)")
-    y = torch.empty(B, int(ny), dtype=torch.float32, device=ex.device)
-    S = carry.shape[1]
-    ws = _workspace(4 * B * (S + int(nf)) * W, ex.device) if nf > 0 or ny > 0 else None
+    carry, y, ws = _ola_stream_tail("lti_frames_ola_stream", carry, lti_frames_stream_carry, (B, W, hop, M), nf, ny, ex.device)
     lib = _lib.load()
     rc = lib.golf_lti_frames_ola_stream_f32(ex.data_ptr(), ex.stride(0), int(x0), nx, int(x_end), gain.data_ptr(), int(g0),
                                             gain.shape[1], int(g_end), a.data_ptr(), int(a0), a.shape[1], window.data_ptr(),
@@ -1637,7 +1648,7 @@ def stft_filter_stream_carry(B: int, n_fft: int, hop: int, device) -> torch.Tens
     if nbytes == 0:
         raise _lib.GolfError(f"stft_filter_stream: no carry for B={B}, n_fft={n_fft}, hop={hop} (n_fft a power of two in "
                              "[64, 2048], n_fft >= 2*hop)")
-    return torch.zeros(int(B), nbytes // (4 * int(B) * int(n_fft)), int(n_fft), dtype=torch.float32, device=device)
+    return _ola_carry(nbytes, B, n_fft, device)
 
 
 def stft_filter_stream(x, H, window, hop: int, carry=None, *, x0: int, h0: int, f0: int, nf: int, n0: int, ny: int,
@@ -1657,13 +1668,7 @@ def stft_filter_stream(x, H, window, hop: int, carry=None, *, x0: int, h0: int, 
     n = window.numel()
     if H.ndim != 3 or H.shape[0] != B or H.shape[2] != n // 2 + 1:
         raise _lib.GolfError(f"stft_filter_stream: x {tuple(x.shape)}, H {tuple(H.shape)}, n_fft {n}")
-    if carry is None:
-        carry = stft_filter_stream_carry(B, n, hop, x.device)
-    if not carry.is_cuda or carry.dtype != torch.float32 or not carry.is_contiguous() or carry.shape[0] != B:
-        raise _lib.GolfError(f"stft_filter_stream: carry {tuple(carry.shape)} {carry.dtype} (from stft_filter_stream_carry)")
-    y = torch.empty(B, int(ny), dtype=torch.float32, device=x.device)
-    S = carry.shape[1]
-    ws = _workspace(4 * B * (S + int(nf)) * n, x.device) if nf > 0 or ny > 0 else None
+    carry, y, ws = _ola_stream_tail("stft_filter_stream", carry, stft_filter_stream_carry, (B, n, hop), nf, ny, x.device)
     lib = _lib.load()
     rc = lib.golf_stft_filter_frames_stream_f32(x.data_ptr(), x.stride(0), int(x0), nx, int(x_end), Hf.data_ptr(), int(h0),
                                                 H.shape[1], int(cplx), int(frames_end), window.data_ptr(), int(f0), int(nf),

@@ -86,6 +86,22 @@ def test_stream_entry_vs_oracle_one_shot_and_splits(B, M, hop, W):
         assert torch.equal(got, whole)
 
 
+def test_one_frame_calls_wrap_the_ring():
+    """B 2, M 6, hop 8, W 32 (S = 3): one frame per call up to frame 11, so the slots the carried frames are read from and
+    written to wrap more than once; the bits of one call over the whole."""
+    from golf_amd import functional as GF
+
+    B, M, hop, W, F = 2, 6, 8, 32, 14
+    gen = torch.Generator().manual_seed(832)
+    a = GF.rc2lpc((0.5 * torch.tanh(torch.randn(B, F, M, generator=gen))).cuda())
+    gain = torch.exp(0.1 * torch.randn(B, F, generator=gen)).cuda()
+    ex = torch.randn(B, (F - 1) * hop + 1, generator=gen).cuda()
+    whole = _stream_filter(ex, gain, a, _win(W), hop, [])
+    got = _stream_filter(ex, gain, a, _win(W), hop, [1] * 12)
+    assert whole.shape[1] == (F - 1) * hop and whole.abs().max() > 0.1
+    assert torch.equal(got, whole)
+
+
 def test_stream_ill_conditioned_rows():
     """tests/test_gpu_lpc_ff.py::test_ff_ill_conditioned_rows through the streaming entry (random splits): the same bound,
     worst row <= 3e-4 and the second worst <= 1e-4 -- the per-frame fp64 feedback tier keeps the hard frames accurate."""

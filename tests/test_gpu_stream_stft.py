@@ -131,6 +131,35 @@ def test_entry_is_bitwise_independent_of_the_split(n, hop):
                 assert emax <= 1e-4 and el2 <= 1e-4, (kind, n, hop, T, F, emax, el2)
 
 
+def test_one_frame_calls_wrap_the_ring():
+    """B 2, n_fft 64, hop 16 (S = 3), T = 10 hop: one frame per call from frame 0 to frame 8 (the last two reach beyond T and
+    wait for the end), so the slots the carried frames are read from and written to wrap more than once; the bits of the
+    single call."""
+    from golf_amd import functional as GF
+
+    B, n, hop = 2, 64, 16
+    T, pad = 10 * hop, n // 2
+    frames = 1 + T // hop
+    gen = torch.Generator().manual_seed(6416)
+    x = torch.randn(B, T, generator=gen).cuda()
+    H = torch.complex(torch.rand(B, frames, pad + 1, generator=gen) + 0.5, 0.2 * torch.randn(B, frames, pad + 1, generator=gen)).cuda()
+    window = torch.hann_window(n).cuda()
+    single = GF.stft_filter_frames(x, H, window, hop)
+    carry, outs, n0 = None, [], 0
+    for f in range(frames - 1):
+        last = f == frames - 2
+        x_lo = max(0, f * hop - pad - 1)
+        n1 = hop * (frames - 1) if last else max(0, (f + 1) * hop - pad)
+        y, carry = GF.stft_filter_stream(x[:, x_lo:T if last else f * hop + pad + 1], H[:, f:f + 1 + last], window, hop, carry,
+                                         x0=x_lo, h0=f, f0=f, nf=1 + last, n0=n0, ny=n1 - n0, x_end=T if last else -1,
+                                         frames_end=frames if last else -1)
+        outs.append(y)
+        n0 = n1
+    split = torch.cat(outs, 1)
+    assert single.shape == split.shape == (B, hop * (frames - 1)) and single.abs().max() > 0.1
+    assert torch.equal(single, split), (single - split).abs().max()
+
+
 # ---- the decoders --------------------------------------------------------------------------------------------------------
 def _inputs(name, B, T, seed=2434):
     from golf_amd.synthetic import make_inputs
