@@ -58,6 +58,8 @@ SIGNATURES = {
                                   + [_i64, _dbl, _dbl, _vp]),
     "golf_lpc_analysis_bwd_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64, _c_f32p, _vp, _c_f32p, _i64, _vp, _sz]
                                   + [_int] * 6 + [_i64, _dbl, _vp]),
+    "golf_lpc_source_filter_f32": (_int, [_c_f32p, _i64] + [_c_f32p] * 5 + [_int] * 7 + [_dbl] + [_int] * 2
+                                   + [_i64, _dbl, _dbl, _vp]),
     "golf_f0_yin_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p, _c_f32p] + [_int] * 7 + [_i64, _dbl, _dbl, _dbl, _vp]),
     "golf_f0_candidates_f32": (_int, [_c_f32p, _i64, _c_f32p, _c_f32p] + [_int] * 8 + [_i64, _dbl, _vp]),
     "golf_f0_viterbi_workspace_bytes": (_sz, [_int] * 3),

@@ -1,5 +1,5 @@
 """Block-by-block analysis: the streaming counterparts of ``f0.F0Analysis``, ``f0.F0Tracker``, ``lpc.LPCAnalysis``,
-``hna.HarmonicNoiseAnalysis``, ``envelope.SpectralEnvelopeAnalysis`` and ``glottal.GlottalSourceAnalysis`` (with its residual,
+``lpc.SourceFilterLPCAnalysis``, ``hna.HarmonicNoiseAnalysis``, ``envelope.SpectralEnvelopeAnalysis`` and ``glottal.GlottalSourceAnalysis`` (with its residual,
 ``functional.ltv_residual``), for a live waveform that feeds a decoder stream (``stream.DecoderStream`` and its siblings take
 exactly these tracks).
 
@@ -31,11 +31,11 @@ from .envelope import SpectralEnvelopeAnalysis
 from .f0 import F0Analysis, F0Tracker
 from .glottal import GlottalSourceAnalysis
 from .hna import HarmonicNoiseAnalysis
-from .lpc import LPCAnalysis
+from .lpc import LPCAnalysis, SourceFilterLPCAnalysis
 from .stream import _Track
 
-__all__ = ["F0Stream", "F0TrackerStream", "LPCAnalysisStream", "HarmonicNoiseStream", "SpectralEnvelopeStream",
-           "GlottalSourceStream", "ResidualStream", "open_analysis_stream", "frames_open", "frames_final", "frame_reach",
+__all__ = ["F0Stream", "F0TrackerStream", "LPCAnalysisStream", "SourceFilterLPCStream", "HarmonicNoiseStream",
+           "SpectralEnvelopeStream", "GlottalSourceStream", "ResidualStream", "open_analysis_stream", "frames_open", "frames_final", "frame_reach",
            "hna_frames_final", "hna_keep_from", "env_frames_final", "env_keep_from", "res_samples_final", "res_samples_finish",
            "res_keep_from"]
 
@@ -134,7 +134,7 @@ class _Stream:
 
 
 class _FrameStream(_Stream):
-    """The protocol and the sample track the three one-input streams share.  A subclass names its frame (``span``, ``hop``,
+    """The protocol and the sample track the one-input streams share.  A subclass names its frame (``span``, ``hop``,
     ``centred``) and implements ``_frames(x, k)``, the one-shot call for the first k frames of x with ``centred=False``, and
     ``_emit(k, out, final)``, what the push returns.  The track starts with the zeros before sample 0."""
 
@@ -287,28 +287,20 @@ class F0TrackerStream(_F0Base):
                                     m.unvoiced_cost, m.lag_cost, m.jump_cost, m.switch_cost, flush=final, return_state=True)
 
 
-class LPCAnalysisStream(_FrameStream):
-    """``LPCAnalysis`` block by block: ``push`` / ``finish`` give ``(gain, a)`` as ``forward`` does -- the
-    ``end_filter_params`` of a decoder stream -- and with ``return_rc=True`` ``(gain, a, rc)``; ``push_all`` / ``finish_all``
-    give the plain tensors of ``analyse``.  A frame is emitted once its last sample has been pushed."""
+class _LPCStream(_FrameStream):
+    """What the two LPC streams share: frames of ``window_length`` samples and the protocol over the tuple ``(gain, a, ...)``.
+    A subclass implements ``_frames(x, k)`` and ``_widths()``, the last dimension of each result after ``gain``."""
 
-    def __init__(self, module: LPCAnalysis, batch_size: int, return_rc: bool = False):
-        if not isinstance(module, LPCAnalysis):
-            raise TypeError(f"LPCAnalysisStream: an LPCAnalysis is needed (got {type(module).__name__})")
+    def __init__(self, module, batch_size: int, return_rc: bool):
         super().__init__(module, batch_size, module.window_length)
         self.return_rc = bool(return_rc)
-
-    def _frames(self, x, k):
-        m = self.module
-        return GF.lpc_analysis(x, m._window, self.hop, m.lpc_order, centred=False, n_frames=k, return_rc=self.return_rc)
 
     def _emit(self, k, out, final):
         if k > 0:
             return out
-        dev, M = self._device(), self.module.lpc_order
-        gain = torch.empty(self.B, 0, dtype=torch.float32, device=dev)
-        a = torch.empty(self.B, 0, M, dtype=torch.float32, device=dev)
-        return (gain, a, a.clone()) if self.return_rc else (gain, a)
+        dev = self._device()
+        return (torch.empty(self.B, 0, dtype=torch.float32, device=dev),) + tuple(
+            torch.empty(self.B, 0, n, dtype=torch.float32, device=dev) for n in self._widths())
 
     def push_all(self, x):
         return self._run(x, False)
@@ -324,6 +316,47 @@ class LPCAnalysisStream(_FrameStream):
     def finish(self):
         """The utterance has ended: the remaining frames; the stream starts a new utterance."""
         return tuple(AudioTensor(t, self.hop) for t in self._run(None, True))
+
+
+class LPCAnalysisStream(_LPCStream):
+    """``LPCAnalysis`` block by block: ``push`` / ``finish`` give ``(gain, a)`` as ``forward`` does -- the
+    ``end_filter_params`` of a decoder stream -- and with ``return_rc=True`` ``(gain, a, rc)``; ``push_all`` / ``finish_all``
+    give the plain tensors of ``analyse``.  A frame is emitted once its last sample has been pushed."""
+
+    def __init__(self, module: LPCAnalysis, batch_size: int, return_rc: bool = False):
+        if not isinstance(module, LPCAnalysis):
+            raise TypeError(f"LPCAnalysisStream: an LPCAnalysis is needed (got {type(module).__name__})")
+        super().__init__(module, batch_size, return_rc)
+
+    def _frames(self, x, k):
+        m = self.module
+        return GF.lpc_analysis(x, m._window, self.hop, m.lpc_order, centred=False, n_frames=k, return_rc=self.return_rc)
+
+    def _widths(self):
+        return (self.module.lpc_order,) * (2 if self.return_rc else 1)
+
+
+class SourceFilterLPCStream(_LPCStream):
+    """``SourceFilterLPCAnalysis`` block by block, with the protocol of ``LPCAnalysisStream``: ``push`` / ``finish`` give
+    ``(gain, a)``, then ``rc`` with ``return_rc=True`` and ``source`` with ``return_source=True``, AudioTensors at
+    ``hop_length``; ``push_all`` / ``finish_all`` give the plain tensors of ``analyse``.  Its frames are frame-local like the
+    plain analysis', so everything pushed out plus ``finish()`` is ``torch.equal`` to the module on the concatenated input,
+    whatever the cuts, and ``(gain, a)`` feed a ``ResidualStream`` in ``LPCAnalysisStream``'s place."""
+
+    def __init__(self, module: SourceFilterLPCAnalysis, batch_size: int, return_rc: bool = False, return_source: bool = False):
+        if not isinstance(module, SourceFilterLPCAnalysis):
+            raise TypeError(f"SourceFilterLPCStream: a SourceFilterLPCAnalysis is needed (got {type(module).__name__})")
+        super().__init__(module, batch_size, return_rc)
+        self.return_source = bool(return_source)
+
+    def _frames(self, x, k):
+        m = self.module
+        return GF.source_filter_lpc(x, m._window, self.hop, m.lpc_order, m.source_order, m.iterations, m.preemphasis,
+                                    centred=False, n_frames=k, return_rc=self.return_rc, return_source=self.return_source)
+
+    def _widths(self):
+        m = self.module
+        return (m.lpc_order,) * (2 if self.return_rc else 1) + ((m.source_order,) if self.return_source else ())
 
 
 # ---- harmonic-plus-noise analysis: two inputs at two paces ------------------------------------------------------------------
@@ -700,8 +733,9 @@ class ResidualStream(_Stream):
 
 def open_analysis_stream(module, batch_size: int, **kw):
     """The stream of an analysis module: ``F0TrackerStream`` (``lag=``), ``F0Stream``, ``LPCAnalysisStream``
-    (``return_rc=``), ``HarmonicNoiseStream``, ``SpectralEnvelopeStream`` or ``GlottalSourceStream``.  (``ResidualStream``
-    has no module: it is opened with the hop and the order.)"""
+    (``return_rc=``), ``SourceFilterLPCStream`` (``return_rc=``, ``return_source=``), ``HarmonicNoiseStream``,
+    ``SpectralEnvelopeStream`` or ``GlottalSourceStream``.  (``ResidualStream`` has no module: it is opened with the hop and
+    the order.)"""
     if isinstance(module, SpectralEnvelopeAnalysis):
         return SpectralEnvelopeStream(module, batch_size, **kw)
     if isinstance(module, GlottalSourceAnalysis):
@@ -714,4 +748,6 @@ def open_analysis_stream(module, batch_size: int, **kw):
         return F0Stream(module, batch_size, **kw)
     if isinstance(module, LPCAnalysis):
         return LPCAnalysisStream(module, batch_size, **kw)
+    if isinstance(module, SourceFilterLPCAnalysis):
+        return SourceFilterLPCStream(module, batch_size, **kw)
     raise TypeError(f"open_analysis_stream: no analysis stream for {type(module).__name__}")

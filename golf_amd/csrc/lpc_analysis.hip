@@ -22,6 +22,13 @@
 //   2. one thread per sample t: over the frames that cover t in ascending order, with k = t - o_f,
 //      g_x[t] += window[k] * sum_{j=0}^{M} g_r[f][j] c_j (s_f[k+j] + s_f[k-j]),   c_0 = 1 + eps_rel, c_j = 1 otherwise,
 //      the frame's stretch of s_f staged in LDS for the 256 samples of the workgroup.
+//
+// Source-compensated analysis (golf_lpc_source_filter_f32, forward only; tests/sflpc_ref.py is the checker): iterative adaptive
+// inverse filtering restated on lags.  Filtering the windowed frame by a short polynomial c and taking its autocorrelation
+// is (r o c)[j] = rho_c[0] r[j] + sum_d rho_c[d] (r[|j-d|] + r[j+d]) with rho_c the autocorrelation of c, so the frame is
+// staged and summed once, exactly as above but for M + Q lags, and every later stage (source polynomial, tract, source, ...,
+// final tract, gain) is the same wave's recursion on a filtered lag set kept beside r in its LDS slice: rho_c over lanes d,
+// (r o c)[j] over lanes j, both as doubles.  No workspace; a frame's bits depend on its samples and the arguments only.
 #include "common.h"
 #include "device_common.h"
 
@@ -70,6 +77,39 @@ __device__ __forceinline__ double la_window_energy(const float* __restrict__ win
     return la_wave_sum(sw);
 }
 
+// the wave's frame slice: s[k] = x[o + k] * window[k] for k < W (x = 0 outside [0, T)), zeros up to S
+__device__ __forceinline__ void la_stage_frame(float* s, int S, const float* __restrict__ xr, const float* __restrict__ window,
+                                               int64_t o, int T, int W, int lane) {
+    for (int k = lane; k < S; k += 64) {
+        const int64_t t = o + k;
+        s[k] = (k < W && t >= 0 && t < T) ? xr[t] * window[k] : 0.f;
+    }
+}
+
+// lags j0 .. j0 + LA_LAGS - 1 of the staged frame, the same bits in every lane
+__device__ __forceinline__ void la_lag_pass(double (&v)[LA_LAGS], const float* s, int W, int j0, int lane) {
+#pragma unroll
+    for (int jj = 0; jj < LA_LAGS; ++jj) v[jj] = 0.0;
+    for (int n = lane; n < W; n += 64) {
+        const double sn = (double)s[n];
+#pragma unroll
+        for (int jj = 0; jj < LA_LAGS; ++jj) v[jj] += sn * (double)s[n + j0 + jj];   // zeros past W
+    }
+#pragma unroll
+    for (int jj = 0; jj < LA_LAGS; ++jj) v[jj] = la_wave_sum(v[jj]);
+}
+
+// Levinson-Durbin to order n from the lags r: lane l ends with a_{l+1} and k_{l+1} (0 from lane n on); returns E_n
+__device__ __forceinline__ double la_levinson(double& a, double& kk, const double* r, int n, int lane) {
+    a = 0.0, kk = 0.0;
+    double err = r[0];
+    for (int i = 1; i <= n; ++i) {
+        const double k = la_step(a, err, r, i, lane);
+        if (lane + 1 == i) kk = k;
+    }
+    return err;
+}
+
 __global__ void lpc_analysis_fwd_kernel(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ window,
                                         float* __restrict__ gain, float* __restrict__ a_out, float* __restrict__ rc_out,
                                         double* __restrict__ lags, int G, int T, int F, int M, int hop, int W,
@@ -82,28 +122,17 @@ __global__ void lpc_analysis_fwd_kernel(const float* __restrict__ x, int64_t x_s
     double* r = la_lds + w * (M + 1);
     float* s = (float*)(la_lds + waves * (M + 1)) + (size_t)w * S;
     const int b = g / F, f = g - b * F;
-    const int64_t o = origin + (int64_t)f * hop;
-    const float* xr = x + (int64_t)b * x_stride;
 
-    for (int k = lane; k < S; k += 64) {
-        const int64_t t = o + k;
-        s[k] = (k < W && t >= 0 && t < T) ? xr[t] * window[k] : 0.f;
-    }
+    la_stage_frame(s, S, x + (int64_t)b * x_stride, window, origin + (int64_t)f * hop, T, W, lane);
     const double sw = la_window_energy(window, W, lane);
     wave_lds_fence();
 
     for (int j0 = 0; j0 <= M; j0 += LA_LAGS) {
         double acc[LA_LAGS];
-#pragma unroll
-        for (int jj = 0; jj < LA_LAGS; ++jj) acc[jj] = 0.0;
-        for (int n = lane; n < W; n += 64) {
-            const double sn = (double)s[n];
-#pragma unroll
-            for (int jj = 0; jj < LA_LAGS; ++jj) acc[jj] += sn * (double)s[n + j0 + jj];   // zeros past W
-        }
+        la_lag_pass(acc, s, W, j0, lane);
 #pragma unroll
         for (int jj = 0; jj < LA_LAGS; ++jj) {
-            double v = la_wave_sum(acc[jj]);
+            double v = acc[jj];
             const int j = j0 + jj;
             if (j == 0) v = v * (1.0 + eps_rel) + eps_abs;
             if (lane == 0 && j <= M) {
@@ -114,16 +143,107 @@ __global__ void lpc_analysis_fwd_kernel(const float* __restrict__ x, int64_t x_s
     }
     wave_lds_fence();
 
-    double a = 0.0, kk = 0.0, err = r[0];
-    for (int i = 1; i <= M; ++i) {
-        const double k = la_step(a, err, r, i, lane);
-        if (lane + 1 == i) kk = k;
-    }
+    double a, kk;
+    const double err = la_levinson(a, kk, r, M, lane);
     if (lane < M) {
         a_out[(size_t)g * M + lane] = (float)a;
         if (rc_out) rc_out[(size_t)g * M + lane] = (float)kk;
     }
     if (lane == 0) gain[g] = (float)sqrt(fmax(err, 0.0) / sw);
+}
+
+// ---- source-compensated analysis (golf_lpc_source_filter_f32): the stages after the lags work on lag sets alone ---------------
+constexpr int SF_MAX_SOURCE = 16;
+constexpr int SF_MAX_ITER = 8;
+
+__host__ __device__ constexpr int sf_poly(int M, int Q) { return (M > Q ? M : Q) + 1; }   // coefficients of the longer one
+// doubles of one wave's slice: r[0..M+Q], then the filtered lags t, the polynomial c and its lags rho, sf_poly each
+__host__ __device__ constexpr int sf_doubles(int M, int Q) { return M + Q + 1 + 3 * sf_poly(M, Q); }
+static inline size_t sf_lds(int waves, int W, int M, int Q) {
+    return (size_t)waves * (sf_doubles(M, Q) * sizeof(double) + la_frame_floats(W, M + Q) * sizeof(float));
+}
+
+// c <- 1, a_1 .. a_n from the lane layout
+__device__ __forceinline__ void sf_store_poly(double* c, double a, int n, int lane) {
+    if (lane == 0) c[0] = 1.0;
+    if (lane < n) c[lane + 1] = a;
+    wave_lds_fence();
+}
+
+// t[0..n] <- the lags of the frame filtered by c (order P, c_0 = 1): rho[d] = sum_p c_p c_{p+d} over lanes d, then
+// t[j] = rho[0] r[j] + sum_{d=1}^{P} rho[d] (r[|j-d|] + r[j+d]) over lanes j; r holds lags 0 .. n + P.  An index past lane 63
+// (order 64 has 65 coefficients) takes a second round.
+__device__ __forceinline__ void sf_filtered_lags(double* t, double* rho, const double* r, const double* c, int P, int n,
+                                                 int lane) {
+    for (int d = lane; d <= P; d += 64) {
+        double acc = 0.0;
+        for (int p = 0; p + d <= P; ++p) acc += c[p] * c[p + d];
+        rho[d] = acc;
+    }
+    wave_lds_fence();
+    for (int j = lane; j <= n; j += 64) {
+        double acc = rho[0] * r[j];
+        for (int d = 1; d <= P; ++d) acc += rho[d] * (r[j >= d ? j - d : d - j] + r[j + d]);
+        t[j] = acc;
+    }
+    wave_lds_fence();
+}
+
+__global__ void lpc_source_filter_kernel(const float* __restrict__ x, int64_t x_stride, const float* __restrict__ window,
+                                         float* __restrict__ gain, float* __restrict__ a_out, float* __restrict__ rc_out,
+                                         float* __restrict__ src_out, int G, int T, int F, int M, int Q, int iterations,
+                                         int adaptive, double preemphasis, int hop, int W, int64_t origin, double eps_rel,
+                                         double eps_abs) {
+    extern __shared__ __attribute__((aligned(16))) double la_lds[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const int g = blockIdx.x * waves + w;
+    if (g >= G) return;   // wave-uniform; nothing below synchronises across waves
+    const int J = M + Q, S = la_frame_floats(W, J), NP = sf_poly(M, Q);
+    double* r = la_lds + w * sf_doubles(M, Q);
+    double* t = r + J + 1;
+    double* c = t + NP;
+    double* rho = c + NP;
+    float* s = (float*)(la_lds + waves * sf_doubles(M, Q)) + (size_t)w * S;
+    const int b = g / F, f = g - b * F;
+
+    la_stage_frame(s, S, x + (int64_t)b * x_stride, window, origin + (int64_t)f * hop, T, W, lane);
+    const double sw = la_window_energy(window, W, lane);
+    wave_lds_fence();
+
+    for (int j0 = 0; j0 <= J; j0 += LA_LAGS) {
+        double acc[LA_LAGS];
+        la_lag_pass(acc, s, W, j0, lane);
+#pragma unroll
+        for (int jj = 0; jj < LA_LAGS; ++jj) {
+            const int j = j0 + jj;
+            if (lane == 0 && j <= J) r[j] = j == 0 ? acc[jj] * (1.0 + eps_rel) + eps_abs : acc[jj];
+        }
+    }
+    wave_lds_fence();
+
+    double a, kk;
+    int P = 1;   // the order of the source polynomial in c
+    if (adaptive) la_levinson(a, kk, r, 1, lane);
+    else a = lane == 0 ? -preemphasis : 0.0;
+    sf_store_poly(c, a, P, lane);
+    for (int it = 0; it < iterations; ++it) {
+        sf_filtered_lags(t, rho, r, c, P, M, lane);
+        la_levinson(a, kk, t, M, lane);
+        sf_store_poly(c, a, M, lane);             // the tract
+        sf_filtered_lags(t, rho, r, c, M, Q, lane);
+        la_levinson(a, kk, t, Q, lane);
+        sf_store_poly(c, a, P = Q, lane);         // the source
+    }
+    if (src_out && lane < Q) src_out[(size_t)g * Q + lane] = (float)a;   // zero from lane P on
+    sf_filtered_lags(t, rho, r, c, P, M, lane);
+    la_levinson(a, kk, t, M, lane);
+    if (lane < M) {
+        a_out[(size_t)g * M + lane] = (float)a;
+        if (rc_out) rc_out[(size_t)g * M + lane] = (float)kk;
+    }
+    sf_store_poly(c, a, M, lane);
+    sf_filtered_lags(t, rho, r, c, M, 0, lane);   // the audio through the tract's inverse alone
+    if (lane == 0) gain[g] = (float)sqrt(fmax(t[0], 0.0) / sw);
 }
 
 // g_r (G, M+1) from the saved lags and the incoming gradients (each may be null)
@@ -252,6 +372,31 @@ int golf_lpc_analysis_fwd_f32(const float* x, int64_t x_stride, const float* win
     hipLaunchKernelGGL(lpc_analysis_fwd_kernel, dim3((unsigned)ceil_div(G, waves)), dim3(64 * waves),
                        la_fwd_lds(waves, W, M), (hipStream_t)stream, x, x_stride, window, gain, a, rc, (double*)ws, G, T, F,
                        M, hop, W, origin, eps_rel, eps_abs);
+    GOLF_LAUNCH_CHECK();
+    return GOLF_OK;
+}
+
+int golf_lpc_source_filter_f32(const float* x, int64_t x_stride, const float* window, float* gain, float* a, float* rc,
+                               float* source, int B, int T, int F, int M, int Q, int iterations, int adaptive,
+                               double preemphasis, int hop, int W, int64_t origin, double eps_rel, double eps_abs,
+                               void* stream) {
+    const char* who = "lpc_source_filter";
+    if (int e = la_check_shape(who, B ? B : 1, T, F, M, hop, W)) return e;   // an empty batch is checked like a row
+    if (Q < 1 || Q > SF_MAX_SOURCE)
+        return fail(GOLF_EUNSUPPORTED, "%s: source order Q=%d outside 1..%d", who, Q, SF_MAX_SOURCE);
+    if (iterations < 0 || iterations > SF_MAX_ITER)
+        return fail(GOLF_EUNSUPPORTED, "%s: iterations=%d outside 0..%d", who, iterations, SF_MAX_ITER);
+    if (W <= M + Q) return fail(GOLF_EUNSUPPORTED, "%s: window W=%d must exceed M + Q = %d", who, W, M + Q);
+    if (!adaptive && !(fabs(preemphasis) < 1.0))   // NaN fails the comparison too
+        return fail(GOLF_EINVAL, "%s: preemphasis=%g must be finite with |preemphasis| < 1", who, preemphasis);
+    if (B == 0) return GOLF_OK;
+    if ((!x && T > 0) || !window || !gain || !a)
+        return fail(GOLF_EINVAL, "%s: null pointer (x=%p window=%p gain=%p a=%p)", who, x, window, gain, a);
+    if (x_stride < T) return fail(GOLF_EINVAL, "%s: row stride %lld < T=%d", who, (long long)x_stride, T);
+    const int G = B * F, waves = la_fwd_waves(W);
+    hipLaunchKernelGGL(lpc_source_filter_kernel, dim3((unsigned)ceil_div(G, waves)), dim3(64 * waves),
+                       sf_lds(waves, W, M, Q), (hipStream_t)stream, x, x_stride, window, gain, a, rc, source, G, T, F, M, Q,
+                       iterations, adaptive, preemphasis, hop, W, origin, eps_rel, eps_abs);
     GOLF_LAUNCH_CHECK();
     return GOLF_OK;
 }

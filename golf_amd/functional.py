@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "f0_viterbi_stream",
+__all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "ltv_inverse", "lpc_analysis", "source_filter_lpc", "f0_yin", "f0_candidates", "f0_viterbi", "f0_track", "f0_viterbi_stream",
            "f0_viterbi_stream_state", "harmonic_analysis", "harmonic_analysis_stream", "spectral_envelope", "spectral_envelope_stream", "ltv_residual", "ltv_residual_stream", "glottal_plan", "glottal_match", "GlottalPlan",
            "lti_frames_ola",
            "glottal_osc",
@@ -865,6 +865,54 @@ def lpc_analysis(x: torch.Tensor, window: torch.Tensor, hop: int, order: int, ce
         return out if return_rc else out[:2]
     return _LPCAnalysis.apply(x, window, hop, M, -(W // 2) if centred else 0, F, float(eps_rel), float(eps_abs),
                               bool(return_rc))
+
+
+@_amp_no_grad   # an analysis without a backward: inference only, like ltv_residual
+def _source_filter_lpc(x, window, hop, M, Q, iterations, preemphasis, origin, F, eps_rel, eps_abs, want_rc, want_source):
+    _lib.require_device(x, window)
+    lib = _lib.load()
+    x, window = _rows(x), window.contiguous()
+    B, T = x.shape
+    gain = torch.empty(B, F, dtype=torch.float32, device=x.device)
+    a = torch.empty(B, F, M, dtype=torch.float32, device=x.device)
+    rc = torch.empty(B, F, M, dtype=torch.float32, device=x.device) if want_rc else None   # not asked for: not written
+    source = torch.empty(B, F, Q, dtype=torch.float32, device=x.device) if want_source else None
+    rcode = lib.golf_lpc_source_filter_f32(x.data_ptr(), x.stride(0), window.data_ptr(), gain.data_ptr(), a.data_ptr(),
+                                           _lib.ptr(rc), _lib.ptr(source), B, T, F, M, Q, iterations, preemphasis is None,
+                                           0.0 if preemphasis is None else preemphasis, hop, window.numel(), origin, eps_rel,
+                                           eps_abs, _lib.stream_ptr())
+    _lib.check(rcode, "golf_lpc_source_filter_f32")
+    return (gain, a) + ((rc,) if want_rc else ()) + ((source,) if want_source else ())
+
+
+def source_filter_lpc(x: torch.Tensor, window: torch.Tensor, hop: int, order: int, source_order: int = 4, iterations: int = 2,
+                      preemphasis: float = None, centred: bool = True, n_frames: int = None, eps_rel: float = 1e-9,
+                      eps_abs: float = 1e-12, return_rc: bool = False, return_source: bool = False):
+    """Source-compensated LPC analysis (golf_lpc_source_filter_f32, the definition is in include/golf_amd.h): x (B, T),
+    window (W,) -> ``(gain (B, F), a (B, F, order))``, then ``rc (B, F, order)`` with ``return_rc`` and ``source (B, F,
+    source_order)`` with ``return_source``, on the frames of ``lpc_analysis``.  Iterative adaptive inverse filtering on the
+    frame's lags: a first source polynomial of order 1 (``-r[1] / r[0]``, or ``-preemphasis`` when that is given), then
+    ``iterations`` rounds of tract (``order``) against source (``source_order``), then the tract once more: ``a`` is the vocal
+    tract without the glottal source's spectral tilt, which the GOLF decoders keep in the wavetable, and ``gain`` the level of
+    the audio through ``a``'s inverse alone, so that ``ltv_residual(x, gain, a, hop)`` has unit local power.
+    ``preemphasis=0, iterations=0`` is ``lpc_analysis``.  Lags and every stage run in fp64 on the device.  No gradient: the
+    outputs never require grad; strided rows of x are read in place.  1 <= order <= 64, 1 <= source_order <= 16,
+    0 <= iterations <= 8, order + source_order < W <= 4096, hop >= 1, |preemphasis| < 1."""
+    who = "source_filter_lpc"
+    if x.dim() != 2 or window.dim() != 1:
+        raise _lib.GolfError(f"{who}: x must be (B, T) and window (W,) (got {tuple(x.shape)}, {tuple(window.shape)})")
+    hop, M, Q, W = int(hop), int(order), int(source_order), window.numel()
+    if hop < 1:
+        raise _lib.GolfError(f"{who}: hop={hop} must be >= 1")
+    F = lpc_analysis_frames(x.shape[1], W, hop, centred) if n_frames is None else int(n_frames)
+    if F < 1:
+        raise _lib.GolfError(f"{who}: n_frames={F} must be >= 1")
+    if x.shape[0] * F >= 2 ** 31:   # the library refuses it too; here before the outputs are allocated
+        raise _lib.GolfError(f"{who}: B*F = {x.shape[0] * F} frames, must be < 2^31")
+    # (an empty batch goes the same way: the library checks its arguments and launches nothing)
+    return _source_filter_lpc(x, window, hop, M, Q, int(iterations), None if preemphasis is None else float(preemphasis),
+                              -(W // 2) if centred else 0, F, float(eps_rel), float(eps_abs), bool(return_rc),
+                              bool(return_source))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ from . import functional as GF
 from .audiotensor import AudioTensor
 from .utils import get_window_fn
 
-__all__ = ["BatchSecondOrderLPCSynth", "LPCAnalysis"]
+__all__ = ["BatchSecondOrderLPCSynth", "LPCAnalysis", "SourceFilterLPCAnalysis"]
 
 
 class LPCAnalysis(nn.Module):
@@ -62,6 +62,48 @@ class LPCAnalysis(nn.Module):
         """Targets for an encoder head that drives ``LTVMinimumPhaseFilterPrecise(lpc_parameterisation="rc2lpc")``."""
         gain, _, rc = self.analyse(x, return_rc=True)
         return self.to_logits(gain, rc, max_abs_value)
+
+
+class SourceFilterLPCAnalysis(nn.Module):
+    """Source-compensated LPC analysis: a waveform -> ``(gain, a)`` at hop ``hop_length`` with the glottal source's spectral
+    tilt estimated beside the vocal tract and kept out of ``a`` (golf_lpc_source_filter_f32: iterative adaptive inverse
+    filtering on the frame's lags, fp64).  ``LPCAnalysis`` fits one all-pole model to the whole spectrum; the GOLF decoders
+    keep the tilt in the wavetable and expect ``a`` to be the tract alone, which is what ``GlottalSourceAnalysis`` needs of
+    its residual.  Same frames and the same ``end_filter_params`` tuple as ``LPCAnalysis``; ``gain`` is the level of the
+    audio through ``a``'s inverse alone.  ``source_order`` and ``iterations`` size the source model and the rounds of tract
+    against source; ``preemphasis`` fixes the first source polynomial to ``1 - preemphasis z^-1`` instead of fitting it to
+    the frame.  Inference only: the outputs never require grad."""
+
+    def __init__(self, lpc_order: int, hop_length: int, window_length: int = None, window: str = "hann",
+                 centred: bool = True, source_order: int = 4, iterations: int = 2, preemphasis: float = None):
+        super().__init__()
+        self.lpc_order = lpc_order
+        self.hop_length = hop_length
+        self.window_length = hop_length * 4 if window_length is None else window_length
+        self.centred = centred
+        self.source_order = source_order
+        self.iterations = iterations
+        self.preemphasis = preemphasis
+        self.register_buffer("_window", get_window_fn(window)(self.window_length).float(), persistent=False)
+
+    def analyse(self, x, return_rc: bool = False, return_source: bool = False):
+        """Plain tensors: ``(gain (B, F), a (B, F, M))``, then ``rc`` and ``source (B, F, Q)`` as asked for."""
+        if isinstance(x, AudioTensor):
+            assert x.hop_length == 1, f"the waveform must be at hop 1 (got {x.hop_length})"
+            x = x.as_tensor()
+        assert x.ndim == 2, x.shape
+        return GF.source_filter_lpc(x, self._window, self.hop_length, self.lpc_order, self.source_order, self.iterations,
+                                    self.preemphasis, centred=self.centred, return_rc=return_rc,
+                                    return_source=return_source)
+
+    def forward(self, x):
+        gain, a = self.analyse(x)
+        return AudioTensor(gain, self.hop_length), AudioTensor(a, self.hop_length)
+
+    def logits(self, x, max_abs_value: float = 1.0):
+        """``LPCAnalysis.to_logits`` of this analysis: targets for an ``rc2lpc`` encoder head."""
+        gain, _, rc = self.analyse(x, return_rc=True)
+        return LPCAnalysis.to_logits(gain, rc, max_abs_value)
 
 
 class BatchSecondOrderLPCSynth(nn.Module):

@@ -300,6 +300,42 @@ int golf_lpc_analysis_bwd_f32(const float* g_gain, const float* g_a, const float
                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Source-compensated LPC analysis (additive in ABI 6; csrc/lpc_analysis.hip): audio -> (gain, a, rc, source) per frame, with
+ * the spectral tilt of the glottal source estimated beside the vocal tract and kept out of `a` -- iterative adaptive inverse
+ * filtering (Alku, Speech Communication 11, 1992) without its integrators (the decoders' wavetable holds the flow derivative,
+ * so lip radiation sits in the source), restated on the lags of the windowed frame.  The plain analysis above fits one
+ * all-pole model to the whole spectrum and so absorbs the source's tilt; the GOLF decoders expect `a` to be the tract alone.
+ * The float64 restatement in tests/sflpc_ref.py is the checker.  Frames, s[k], origin, x = 0 outside [0, T) and the window
+ * are those of golf_lpc_analysis_fwd_f32.  With M the tract's order, Q >= 1 the source's, I = iterations >= 0, J = M + Q:
+ *  1. r[j] = sum_{n < W-j} s[n] s[n+j]  (j = 0..J) in fp64, s one fp32 product;  r[0] <- r[0] (1 + eps_rel) + eps_abs, the
+ *     only regularisation.
+ *  2. Lags of the frame filtered by a polynomial c of order P, c_0 = 1:  rho_c[d] = sum_{p=0}^{P-d} c_p c_{p+d}  and
+ *         (r o c)[j] = rho_c[0] r[j] + sum_{d=1}^{P} rho_c[d] (r[|j-d|] + r[j+d]),   ascending d, fp64;
+ *     with eps = 0 it is the autocorrelation of the full convolution s * c.  It reads r up to j + P <= J.
+ *  3. lev_n(.) is the Levinson-Durbin recursion of golf_lpc_analysis_fwd_f32 to order n.
+ *  4. The first source polynomial, of order 1:  g = lev_1(r), that is g_1 = -r[1] / r[0]  (adaptive != 0), or
+ *     g_1 = -preemphasis  (adaptive == 0).
+ *  5. I times:  vt = lev_M((r o g)[0..M]);  g = lev_Q((r o vt)[0..Q]).
+ *  6. (a, rc, .) = lev_M((r o g)[0..M]).
+ *  7. gain = sqrt(max((r o a)[0], 0) / sum_k window[k]^2): the level of the audio through the tract's inverse alone, so
+ *     that golf_ltv_residual_f32(x, gain, a) has unit local power like the table's pulses.
+ * Outputs: gain (B, F); a (B, F, M); rc (B, F, M), the last stage's reflection coefficients (golf_rc2lpc of it is a), may be
+ * NULL; source (B, F, Q) = g_1..g_Q, zero padded when I = 0, may be NULL.  With adaptive == 0, preemphasis == 0 and I = 0,
+ * a and rc have the bits of golf_lpc_analysis_fwd_f32 and gain is its gain up to the rounding of (r o a)[0] against E_M.
+ * A silent frame gives a = 0; every lag set is positive definite, so |rc| < 1; a NaN sample reaches only the frames that read
+ * it.  One launch, one wave per frame, the frame staged in fp32 and everything after it fp64 in a fixed order: no workspace,
+ * no atomics, bit-reproducible, a frame's bits depend on its samples only.  No call allocates or synchronises;
+ * graph-capturable.  There is no gradient.
+ * Refused before any launch: null x (with T > 0), window, gain or a; B < 0, T < 0, F < 1; x_stride < T; adaptive == 0 with
+ * preemphasis not finite or |preemphasis| >= 1 (GOLF_EINVAL); M outside 1..64, Q outside 1..16, iterations outside 0..8,
+ * W <= M + Q, W > 4096 (a frame must fit LDS), hop < 1, B*F >= 2^31 (GOLF_EUNSUPPORTED).  B == 0 returns GOLF_OK.
+ * ------------------------------------------------------------------------------------------- */
+int golf_lpc_source_filter_f32(const float* x, int64_t x_stride, const float* window, float* gain, float* a, float* rc,
+                               float* source, int B, int T, int F, int M, int Q, int iterations, int adaptive,
+                               double preemphasis, int hop, int W, int64_t origin, double eps_rel, double eps_abs,
+                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f0 analysis (additive in ABI 6): audio -> (f0, period, aperiodicity) per frame by YIN (de Cheveigne & Kawahara, JASA
  * 2002, steps 1-5) -- the f0 track that every decoder takes as an input, on the frame grid of the LPC analysis above.  The
  * reference gets f0 from a third-party CPU package (pyworld.dio, models/utils.py:596-602); this is not that estimator and
