@@ -19,7 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_f64.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
+SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
            "stft_filter.hip", "minphase_fir.hip", "lpc_analysis.hip", "f0_yin.hip", "f0_viterbi.hip", "f0_viterbi_stream.hip", "harm_analysis.hip", "spec_envelope.hip", "glottal_match.hip", "lpc_residual.hip")
 
 _c_f32p = ctypes.c_void_p
@@ -283,7 +283,7 @@ def check(rc: int, what: str):
 
 def require_device(*tensors: torch.Tensor, dtype: torch.dtype = torch.float32):
     """Every tensor on a ROCm device and of ``dtype``: fp32 for every kernel but the float64 sample-wise filter
-    (csrc/lpc_f64.hip), whose callers ask for ``dtype=torch.float64`` explicitly."""
+    (csrc/lpc_any.hip), whose callers ask for ``dtype=torch.float64`` explicitly."""
     for t in tensors:
         if t is None:
             continue

@@ -137,6 +137,36 @@ __device__ __forceinline__ float dppf(float v) {
 #define DPP_SHR1 0x90   /* quad_perm [0,0,1,2]: lane r reads lane r-1 */
 #define DPP_SHL1 0xF9   /* quad_perm [1,2,3,3]: lane r reads lane r+1 */
 #define DPP_BC0  0x00   /* quad_perm [0,0,0,0]: broadcast lane 0 of the quad */
+#define DPP_WAVE_SHL1 0x130   /* the whole wave: lane l reads lane l+1 (lane 63: no source) */
+#define DPP_WAVE_SHR1 0x138   /* the whole wave: lane l reads lane l-1 (lane 0: no source) */
+
+// ---- the hat weights of the linear interpolation's adjoint (up^T), frame f of F frames at `hop` over T samples:
+// frame(t) = min(t/hop, F-2), n = t - frame(t)*hop, weight 1 - n/hop to frame(t) and n/hop to frame(t)+1 (so the last sample
+// (F-1)*hop goes wholly to frame F-1); F == 1: weight 1.  The samples with a weight for frame f are [lo, hi): those of frame
+// f-1 (rising edge) and of frame f (falling edge), clipped to [0, T).
+struct HatSpan {
+    int lo, hi;
+    int64_t tB;   // first sample of frame f
+    int F, hop;
+    bool last;    // frame F-1 has a rising edge only
+    __device__ __forceinline__ HatSpan(int f, int F_, int hop_, int T)
+        : tB((int64_t)f * hop_), F(F_), hop(hop_), last(f == F_ - 1 && F_ >= 2) {
+        int64_t lo64 = f >= 1 ? tB - hop : 0;
+        int64_t hi64 = f <= F - 2 ? tB + hop : tB;     // exclusive
+        if (F < 2 || f >= F - 2) hi64 += 1;            // the last sample (F-1)*hop belongs to frame F-2
+        if (hi64 > T) hi64 = T;
+        if (lo64 > hi64) lo64 = hi64;
+        lo = (int)lo64, hi = (int)hi64;
+    }
+    // is sample t of [lo, hi) on the frame's rising edge?
+    __device__ __forceinline__ bool rising(int64_t t) const { return F >= 2 && (last || t < tB); }
+    // its weight, as C = float or double
+    template <typename C>
+    __device__ __forceinline__ C weight(int64_t t) const {
+        if (F < 2) return C(1);
+        return (C)(rising(t) ? t - (tB - hop) : hop - (t - tB)) / (C)hop;   // an exactly converted integer over hop
+    }
+};
 
 // ---- the carried (B, S, W) frame ring of the overlap-add streams (stream_plan.h: RingPlan), one frame per workgroup:
 // carried frame j of ncin, ring slot (cin_slot + j) % S -> ws slot S - ncin + j;  new frame j of the last ncout, ws slot

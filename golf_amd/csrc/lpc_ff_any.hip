@@ -25,8 +25,6 @@
 
 namespace golf {
 
-#define DPP_WAVE_SHL1 0x130   /* lane l reads lane l+1 (lane 63: no source) */
-
 // v_writelane_b32: lane `lane` (wave-uniform) of `old` takes the wave-uniform `value`.  (The intrinsic has no clang builtin.)
 __device__ int wave_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 

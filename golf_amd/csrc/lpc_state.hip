@@ -198,23 +198,9 @@ __global__ __launch_bounds__(64) void lpc_head_reduce_kernel(const float* __rest
         const int f = (int)(blockIdx.x % (unsigned)F), b = (int)(blockIdx.x / (unsigned)F);
         const float* qb = q + (size_t)b * q_stride;
         const float* xb = ex + (size_t)b * ex_stride;
-        const int64_t tB = (int64_t)f * hop;           // first sample of frame f
-        int64_t lo64 = f >= 1 ? tB - hop : 0;
-        int64_t hi64 = f <= F - 2 ? tB + hop : tB;     // exclusive
-        if (F < 2 || f >= F - 2) hi64 += 1;            // the last sample (F-1)*hop belongs to frame F-2
-        if (hi64 > T) hi64 = T;
-        if (lo64 > hi64) lo64 = hi64;
-        const int lo = (int)lo64, hi = (int)hi64;
-        const bool last = f == F - 1 && F >= 2;        // frame F-1 has a rising edge only
+        const HatSpan span(f, F, hop, T);
         float acc = 0.f;
-        for (int t = lo + k; t < hi; t += 64) {
-            float w = 1.f;
-            if (F >= 2) {
-                const bool rising = last || t < tB;
-                w = rising ? (float)(t - (tB - hop)) / hopf : (float)(hop - (t - tB)) / hopf;
-            }
-            acc = fmaf(w * qb[t], xb[t], acc);
-        }
+        for (int t = span.lo + k; t < span.hi; t += 64) acc = fmaf(span.weight<float>(t) * qb[t], xb[t], acc);
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) acc += __shfl_down(acc, o);
         if (k == 0) g_gain[(size_t)b * F + f] = acc;

@@ -3,7 +3,7 @@
 Plain tensors in, plain tensors out; AudioTensor bookkeeping lives in the nn.Modules.
 Every function raises if the tensors are not ROCm-device tensors — no CPU path exists — and if they are not fp32, with one
 exception: the sample-wise all-pole filter (``ltv_allpole_ss``, ``ltv_allpole_ss_blocks``) also takes float64 tensors, and
-fp32 tensors with ``mode="fp64"``, and then runs its recursion in float64 on the device (csrc/lpc_f64.hip).
+fp32 tensors with ``mode="fp64"``, and then runs its recursion in float64 on the device (csrc/lpc_any.hip).
 """
 from __future__ import annotations
 
@@ -257,7 +257,7 @@ class _LTVAllPoleSS(torch.autograd.Function):
 
 
 class _LTVAllPoleF64(torch.autograd.Function):
-    """The sample-wise filter with its recursion in float64 (golf_ltv_allpole_{fwd,bwd}_f64, csrc/lpc_f64.hip): returns
+    """The sample-wise filter with its recursion in float64 (golf_ltv_allpole_{fwd,bwd}_f64, csrc/lpc_any.hip): returns
     ``(y, state)``.  ``io`` = 1: float64 tensors in and out; 0: fp32 tensors, rounded once at the store.  ``zi`` (B, M) or None
     enters through the kernel's carried-state prologue; it may be a float64 tensor with fp32 I/O -- the ``state`` output of
     the block before, (B, M) float64 and NOT rounded to the I/O type, which is what keeps a chain of fp32 blocks on the bits
@@ -428,7 +428,7 @@ def ltv_allpole_ss(ex: torch.Tensor, gain: torch.Tensor, a: torch.Tensor, hop: i
     """y[t] = ex[t]*up(gain)[t] - sum_i up(a)[t,i] y[t-1-i]; ex (B,Tx), gain (B,F), a (B,F,M) at hop.
     Output (B, min(Tx,(F-1)*hop+1)).  Differentiable w.r.t. ex, gain, a (custom HIP backward).
     Float64: with ``ex``, ``gain``, ``a`` (and ``zi``) all float64 the recursion, its adjoint and the gradient sums run in
-    double on the device (csrc/lpc_f64.hip: one wave per utterance, every shape with 1 <= M <= 64) and the result and the
+    double on the device (csrc/lpc_any.hip: one wave per utterance, every shape with 1 <= M <= 64) and the result and the
     gradients are float64 -- what torchlpc.sample_wise_lpc computes for double inputs, and what torch.autograd.gradcheck
     can be pointed at.  ``prepared``, ``fast_inference`` and any ``mode`` are ignored then; ``status`` raises (its words
     describe the chunked scan); ``length``, ``zi`` and ``return_zf`` work as in fp32.  Tensors of different dtypes raise.

@@ -222,7 +222,7 @@ int golf_ltv_allpole_bwd_f32(const float* gy, int64_t gy_stride, const float* y,
                              int B, int T, int F, int M, int hop,
                              void* ws, size_t ws_bytes, int flags, void* stream);
 
-/* a-1 in FLOAT64 (additive in ABI 6; csrc/lpc_f64.hip).  The same filter, the same up() interpolation and the same
+/* a-1 in FLOAT64 (additive in ABI 6; csrc/lpc_any.hip, its double instantiations).  The same filter, the same up() interpolation and the same
  * T <= (F-1)*hop+1 rule as golf_ltv_allpole_fwd_f32 / _bwd_f32 -- models/filters.py:99-113, where torchlpc.sample_wise_lpc
  * (models/filters.py:112) is dtype-generic and is run, gradcheck'ed and rendered in double -- with everything on the recursion's
  * dependent chain in double: accumulators, interpolated coefficients, up(gain), the fed-back output.  For the utterances at the
@@ -231,7 +231,7 @@ int golf_ltv_allpole_bwd_f32(const float* gy, int64_t gy_stride, const float* y,
  *   io = 0  they are fp32 buffers: widened at the load (exact), rounded once at the store; the arithmetic is the same
  *   state, zi, g_zi (B, M) and the workspace are doubles for either io (a chain of fp32 blocks continues from the unrounded
  *   outputs, and so stays on the bits of the one-shot call).
- * One wave per utterance, one lane per tap (the wave-per-utterance design of csrc/lpc_any.hip, for every shape: any
+ * One wave per utterance, one lane per tap (the wave-per-utterance kernels of csrc/lpc_any.hip, for every shape: any
  * 1 <= M <= 64, hop >= 1, F >= 1, on or off the ring grid); the cost is that of one serial recursion per utterance.  Strides are
  * in elements of the io type, rows 64-bit addressed.  GOLF_EINVAL: a null required pointer, a non-positive size, T beyond
  * (F-1)*hop+1, a row stride below its width, io outside {0, 1}, a workspace that is missing, misaligned or too small;

@@ -1,4 +1,4 @@
-"""The sample-wise LTV all-pole filter with its recursion in float64 (csrc/lpc_f64.hip): double tensors, and fp32 tensors
+"""The sample-wise LTV all-pole filter with its recursion in float64 (csrc/lpc_any.hip): double tensors, and fp32 tensors
 with ``mode="fp64"``, against the float64 oracle -- forward, carried state, all gradients, gradcheck.
 
 Bars.  Double tensors: 1e-10 relative (max-norm and L2).  A sequential fp32 emulation sits at <= 6e-6 on exactly these

@@ -90,7 +90,8 @@ def leaves(ex, gain, a, grads=(True, True, True)):
     (3, 10, 22, 100, 777, 0.5),      # excitation ends inside a frame
     (3, 10, 22, 100, 1200, 0.5),     # excitation longer than (F-1)*hop+1: its tail's gradient is exactly 0
     (9, 4, 12, 50, None, 0.5),       # a batch that does not fill the last workgroup
-])
+    (2, 5, 1, 15, None, 0.5),        # M = 1
+] + [(1, 20, 22, 16, Tx, 0.5) for Tx in (63, 64, 65, 129)])   # I/O-block edges (hop 16: no ring width for order 22)
 def test_fwd_bwd_vs_oracle(B, F, M, hop, Tx, scale):
     ex, gain, a, gy, T, (r_y, r_ex, r_gain, r_a) = case(B, F, M, hop, Tx, scale)
     y, g_ex, g_gain, g_a = run(*leaves(ex, gain, a), dev(gy), hop)

@@ -1,4 +1,4 @@
-"""CPU: the float64 sample-wise filter's C entries (golf_ltv_allpole_{fwd,bwd}_f64, csrc/lpc_f64.hip) refuse bad arguments
+"""CPU: the float64 sample-wise filter's C entries (golf_ltv_allpole_{fwd,bwd}_f64, csrc/lpc_any.hip) refuse bad arguments
 before any launch, and its Python entrances check dtypes and devices before they touch a device."""
 import pytest
 import torch

@@ -1,5 +1,5 @@
-"""Device time per sample of the sample-wise filter's float64 recursion (csrc/lpc_f64.hip) beside the fp32 wave-per-utterance
-kernels it restates (csrc/lpc_any.hip), in one process (dev tool; bench.py is the contract).  Reported, not gated.
+"""Device time per sample of the sample-wise filter's float64 recursion beside the fp32 instantiation of the same
+wave-per-utterance kernels (csrc/lpc_any.hip), in one process (dev tool; bench.py is the contract).  Reported, not gated.
 
 B = 32 x 48 001 samples, M = 22:  hop 240 through the float64 recursion -- fp32 tensors with mode="fp64" (io = fp32) and
 float64 tensors (io = fp64) -- and hop 300 (off the ring grid) through the fp32 chain.  All three run one recursion per
