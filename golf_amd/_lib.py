@@ -20,7 +20,8 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgolf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = ("abi.hip", "lpc_ss.hip", "lpc_any.hip", "lpc_state.hip", "lpc_ff.hip", "lpc_ff_any.hip", "glottal_osc.hip", "noise_fir.hip", "ctrl.hip", "noise_band.hip", "peer.hip",
-           "stft_filter.hip", "minphase_fir.hip", "lpc_analysis.hip", "f0_yin.hip", "f0_viterbi.hip", "f0_viterbi_stream.hip", "harm_analysis.hip", "spec_envelope.hip", "glottal_match.hip", "lpc_residual.hip")
+           "stft_filter.hip", "minphase_fir.hip", "lpc_analysis.hip", "f0_yin.hip", "f0_viterbi.hip", "f0_viterbi_stream.hip", "harm_analysis.hip", "spec_envelope.hip", "glottal_match.hip", "lpc_residual.hip",
+           "mlsa_design.hip")
 
 _c_f32p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -154,6 +155,10 @@ SIGNATURES = {
     "golf_min_phase_fir_basis_f32": (_int, [_int, _vp, _sz, _vp]),
     "golf_min_phase_fir_kernels_f32": (_int, [_c_f32p, _c_f32p, _vp, _c_f32p, _int, _int, _vp]),
     "golf_min_phase_fir_kernels_bwd_f32": (_int, [_c_f32p, _c_f32p, _c_f32p, _vp, _c_f32p, _int, _int, _vp]),
+    "golf_mlsa_response_basis_bytes": (_sz, [_int] * 2),
+    "golf_mlsa_response_basis_f32": (_int, [_int, _int, _dbl, _vp, _sz, _vp]),
+    "golf_mlsa_response_rows_f32": (_int, [_c_f32p, _vp, _sz, _c_f32p, _int, _int, _int, _vp]),
+    "golf_mlsa_response_rows_bwd_f32": (_int, [_c_f32p, _c_f32p, _vp, _sz, _c_f32p, _int, _int, _int, _vp]),
     "golf_ltv_fir_frames_causal_length": (_int, [_int] * 4),
     "golf_ltv_fir_frames_causal_fwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _int, _c_f32p, _i64] + [_int] * 6 + [_vp]),
     "golf_ltv_fir_frames_causal_bwd_f32": (_int, [_c_f32p, _i64, _c_f32p, _i64, _c_f32p, _int, _c_f32p, _i64, _c_f32p]

@@ -9,7 +9,7 @@ from __future__ import annotations
 from importlib import import_module
 from typing import Any, Mapping, Union
 
-__all__ = ["resolve_class", "instantiate", "build_model", "load_yaml"]
+__all__ = ["resolve_class", "instantiate", "build_model", "load_yaml", "mlsa_to_stft_filter"]
 
 _ALIASES = (("models.audiotensor", "golf_amd.audiotensor"), ("models.", "golf_amd."), ("loss.spec", "golf_amd.loss"),
             ("ltng.ae", "golf_amd.ae"))
@@ -91,3 +91,44 @@ def build_model(config: Union[str, Mapping]):
     if "decoder" in cfg:
         return instantiate(cfg["decoder"])
     return instantiate(cfg)
+
+
+def mlsa_to_stft_filter(cfg: Any) -> Any:
+    """A deep copy of a parsed config in which every ``models.filters.LTVMLSAFilter`` node (diffsptk's ``MLSA`` with its own
+    framing: no counterpart here, ``build_model`` on such a config raises) is rewritten to ``models.filters.LTVMLSAFilter2``,
+    the reference's STFT-domain form of the same filter: ``fft_length`` becomes ``n_fft``; ``frame_period``,
+    ``filter_order``, ``alpha``, ``gamma`` and ``window`` carry over.  Accepted only for ``mode: freq-domain``, ``phase:
+    minimum``, ``gamma: 0``, ``c: null``, ``ignore_gain: false`` and ``frame_length == fft_length``; anything else raises
+    ``NotImplementedError`` naming the field.  An explicit opt-in -- ``build_model(mlsa_to_stft_filter(load_yaml(path)))`` --
+    because the two classes frame the signal differently: a declared parity gap."""
+    import copy
+
+    required = (("mode", "freq-domain"), ("phase", "minimum"), ("gamma", 0), ("c", None), ("ignore_gain", False))
+
+    def rewrite(node):
+        if isinstance(node, dict):
+            if node.get("class_path") == "models.filters.LTVMLSAFilter":
+                a = dict(node.get("init_args") or {})
+                for field, want in required:
+                    if field in a and a[field] != want:
+                        raise NotImplementedError(f"mlsa_to_stft_filter: {field}={a[field]!r} (only {field}={want!r} has an "
+                                                  "STFT-domain counterpart)")
+                if "fft_length" not in a:
+                    raise NotImplementedError("mlsa_to_stft_filter: fft_length is not given")
+                if a.get("frame_length", a["fft_length"]) != a["fft_length"]:
+                    raise NotImplementedError(f"mlsa_to_stft_filter: frame_length={a['frame_length']} != fft_length="
+                                              f"{a['fft_length']}")
+                known = {f for f, _ in required} | {"fft_length", "frame_length", "frame_period", "filter_order", "alpha",
+                                                    "window"}
+                for field in a:
+                    if field not in known:
+                        raise NotImplementedError(f"mlsa_to_stft_filter: {field}={a[field]!r} has no counterpart")
+                init = {"n_fft": a["fft_length"]}
+                init.update({k: a[k] for k in ("frame_period", "filter_order", "alpha", "gamma", "window") if k in a})
+                return {"class_path": "models.filters.LTVMLSAFilter2", "init_args": init}
+            return {k: rewrite(v) for k, v in node.items()}
+        if isinstance(node, (list, tuple)):
+            return [rewrite(v) for v in node]
+        return copy.deepcopy(node)
+
+    return rewrite(cfg)

@@ -17,7 +17,7 @@ from .audiotensor import AudioTensor
 from .ctrl import Controllable, wrap_ctrl_fn
 from .utils import biquads2lpc, get_logits2biquads, get_radiation_time_filter, get_window_fn, lsp2lpc, rc2lpc
 
-__all__ = ["LTVCepFilter", "DiffWorldSPFilter", "melscale_fbanks", "FilterInterface", "LTVFilterInterface", "LTVMinimumPhaseFilterPrecise", "LTVMinimumPhaseFilter",
+__all__ = ["LTVCepFilter", "LTVMLSAFilter2", "DiffWorldSPFilter", "melscale_fbanks", "FilterInterface", "LTVFilterInterface", "LTVMinimumPhaseFilterPrecise", "LTVMinimumPhaseFilter",
            "LTVZeroPhaseFIRFilter", "LTVZeroPhaseFIRFilterPrecise", "LTVAPZeroPhaseFIRFilter", "LTIAcousticFilter",
            "LTVMinimumPhaseFIRFilterPrecise", "LTVMinimumPhaseFIRFilter", "LTIRadiationFilter",
            "SampleBasedLTVMinimumPhaseFilter", "convert2samplewise"]
@@ -482,6 +482,111 @@ class LTVCepFilter(LTVFilterInterface):
         y = torch.istft(Y, self.n_fft, self.hop_length, self.n_fft, self._window, center=True, normalized=False,
                         onesided=False, return_complex=False)
         return AudioTensor(y)
+
+
+class LTVMLSAFilter2(LTVFilterInterface):
+    """Mel-cepstral filter of the MLSA baseline in its STFT-domain form (reference models/filters.py:626-684): ``filter_order
+    + 1`` mel cepstral coefficients per frame -> complex minimum-phase response on the frequencies warped by ``alpha`` ->
+    applied in the STFT domain, with the framing of ``LTVCepFilter`` (two-sided STFT with ``window``, multiply, inverse STFT,
+    hop*(frames-1) samples).  The response is the package's definition (include/golf_amd.h): H_k = exp(sum_m mc[m]
+    e^{-j m theta_k}), whose imaginary exponent is the minimum phase because the warped cepstrum is causal.  The reference
+    truncates the warped cepstrum at order n_fft/2 and takes the phase from a discrete Hilbert transform; the two agree to
+    5e-15 in log H for n_fft >= 256, and below that this definition is the specification.  Only ``gamma = 0``.
+
+    On a ROCm device the response rows come from the design kernel (``GF.mel_cepstrum_response``:
+    golf_mlsa_response_rows_{,bwd_}f32, differentiable) and the STFT-domain part runs on the frame-filter kernel, under the
+    conditions given for ``LTVCepFilter`` plus ``filter_order <= 64``.  CPU tensors, float64 and every other geometry run the
+    same definition in plain torch and torch.stft / torch.istft, as does an instance with ``hip_frames = False``.
+
+    A standalone class: the reference derives it from ``LTVMLSAFilter``, whose own framing lives in diffsptk and has no
+    counterpart here (``config.mlsa_to_stft_filter`` rewrites such a config to this class, as an explicit opt-in).
+
+    ``fit`` is the analysis counterpart: with ``envelope.SpectralEnvelopeAnalysis(..., filter_order=None)``, which returns the
+    log envelope, ``fit(log_env)`` gives the ``mc`` this filter takes."""
+
+    hip_frames = True   # False: torch.stft / torch.istft on the device too
+
+    def __init__(self, n_fft: int, frame_period: int, filter_order: int, *args, window: str = "hanning", alpha: float = 0,
+                 gamma: float = 0, **kwargs):
+        super().__init__()
+        if args:
+            raise NotImplementedError(f"LTVMLSAFilter2: unsupported positional arguments {args}")
+        if gamma != 0:
+            raise NotImplementedError(f"LTVMLSAFilter2: unsupported gamma={gamma} (only gamma = 0, the plain mel cepstrum)")
+        # saved configs spell out the MLSA defaults (ckpts/interspeech24/mlsa/config.yaml); anything else is refused
+        defaults = {"c": None, "ignore_gain": False, "phase": "minimum", "mode": "freq-domain", "frame_length": n_fft,
+                    "fft_length": n_fft}
+        odd = {k: v for k, v in kwargs.items() if k not in defaults or v != defaults[k]}
+        if odd:
+            raise NotImplementedError(f"LTVMLSAFilter2: unsupported MLSA arguments {odd}")
+        if n_fft % 2 or filter_order < 0 or not -1 < alpha < 1:
+            raise ValueError("LTVMLSAFilter2: n_fft must be even, filter_order >= 0 and |alpha| < 1")
+        self.n_fft, self.hop_length, self.filter_order, self.alpha = n_fft, frame_period, filter_order, float(alpha)
+        window_fn = get_window_fn(window)
+        try:
+            w64 = window_fn(n_fft, dtype=torch.float64)
+        except TypeError:   # a scipy window: float64 already
+            w64 = window_fn(n_fft).double()
+        self.register_buffer("_window", w64.float(), persistent=False)
+        # evaluated in float64 for the float64 path (``.double()`` on the module would only widen the fp32 values)
+        self.register_buffer("_window64", w64, persistent=False)
+        # the design kernel's basis: this module's own, built on first device use (no process-wide cache)
+        self.register_buffer("_basis", None, persistent=False)
+        self.ctrl = wrap_ctrl_fn(split_size=(filter_order + 1,), trsfm_fn=lambda x: (x,))
+
+    def _response_basis(self, mc: Tensor):
+        """The kernel's basis on ``mc``'s device, or None where ``GF.mel_cepstrum_response`` runs torch.  Built once per
+        device and synchronously, so that a later use on any stream is ordered after the build."""
+        if not (mc.is_cuda and mc.dtype in (torch.float32, torch.float16, torch.bfloat16)
+                and GF.mel_cepstrum_kernel_takes(self.n_fft, self.filter_order, self.alpha)):
+            return None
+        b = self._basis
+        if b is None or b.device != mc.device or b.dtype != torch.float32:
+            b = GF.mel_cepstrum_basis(self.n_fft, self.filter_order, self.alpha, mc.device)
+            torch.cuda.current_stream(mc.device).synchronize()
+            self._basis = b
+        return b
+
+    def response_rows(self, mc: Tensor) -> Tensor:
+        """(B, F, order + 1) mel cepstra -> (B, F, n_fft/2 + 1) complex response rows on bins 0 .. n_fft/2."""
+        if mc.shape[-1] != self.filter_order + 1:
+            raise ValueError(f"LTVMLSAFilter2: {mc.shape[-1]} coefficients per frame, expected {self.filter_order + 1}")
+        return GF.mel_cepstrum_response(mc, self.n_fft, self.alpha, basis=self._response_basis(mc))
+
+    def frequency_response(self, mc: Tensor) -> Tensor:
+        """(B, F, order + 1) mel cepstra -> (B, n_fft, F) complex two-sided response (Hermitian extension of the rows)."""
+        H = self.response_rows(mc)
+        return torch.cat([H, H[..., 1:-1].flip(-1).conj()], dim=-1).transpose(-1, -2)
+
+    def forward(self, ex: AudioTensor, mc: AudioTensor, **kwargs) -> AudioTensor:
+        assert mc.hop_length == self.hop_length
+        x = ex.as_tensor()
+        if _on_hip_frames(self, x, mc.as_tensor()):
+            return _hip_frames(self, x, mc.as_tensor())
+        H = self.frequency_response(mc.as_tensor())
+        window = self._window64.to(x.dtype) if x.dtype == torch.float64 else self._window.to(x.dtype)
+        X = torch.stft(x, self.n_fft, self.hop_length, self.n_fft, window, center=True, pad_mode="reflect",
+                       normalized=False, onesided=False, return_complex=True)
+        frames = min(X.shape[-1], H.shape[-1])
+        Y = X[..., :frames] * H[..., :frames]
+        y = torch.istft(Y, self.n_fft, self.hop_length, self.n_fft, window, center=True, normalized=False,
+                        onesided=False, return_complex=False)
+        return AudioTensor(y)
+
+    def fit(self, log_env: Tensor) -> Tensor:
+        """Least-squares mel cepstrum of natural-log magnitude rows: (B, F, n_fft/2 + 1) -> (B, F, order + 1), the ``mc``
+        whose log|H| = sum_m mc[m] cos(m theta_k) is closest to ``log_env`` under the Hermitian bin weights 1, 2, .., 2, 1.
+        Solved in float64, returned in ``log_env``'s dtype; plain torch, differentiable.  Meant for n_fft >= 512: the warped
+        cosines are well conditioned there (condition number 2.9 at n_fft 1024, order 24, alpha 0.46; 7.8 at 2048, 64, 0.77)
+        and nearly dependent on a coarse grid (4.6e9 at n_fft 64, order 24, alpha 0.46)."""
+        if log_env.shape[-1] != self.n_fft // 2 + 1:
+            raise ValueError(f"LTVMLSAFilter2.fit: {log_env.shape[-1]} bins, expected {self.n_fft // 2 + 1}")
+        c, _ = GF.mel_cepstrum_tables(self.n_fft, self.filter_order, self.alpha, torch.float64, log_env.device)
+        w = torch.full((c.shape[1], 1), 2.0, dtype=torch.float64, device=log_env.device).sqrt()
+        w[0] = w[-1] = 1.0
+        rows = log_env.double().reshape(-1, c.shape[1]).t() * w                       # (bins, B*F)
+        mc = torch.linalg.lstsq(c.t() * w, rows).solution                               # (order + 1, B*F)
+        return mc.t().reshape(*log_env.shape[:-1], self.filter_order + 1).to(log_env.dtype)
 
 
 def melscale_fbanks(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample_rate: int, norm=None,

@@ -23,7 +23,9 @@ __all__ = ["ltv_allpole_ss", "ltv_allpole_ss_blocks", "ltv_allpole_prepare", "lt
            "zero_phase_fir_basis", "zero_phase_fir_kernels", "ltv_fir_frames", "zero_phase_fir_filter",
            "zero_phase_fir_filter_precise", "min_phase_fir_basis", "min_phase_window", "min_phase_fir_kernels",
            "min_phase_fir_filter", "min_phase_fir_filter_precise", "ltv_fir_frames_causal",
-           "fir_frames_length", "lti_fir", "harmonic_osc", "biquad_frames_ola"]
+           "fir_frames_length", "lti_fir", "harmonic_osc", "biquad_frames_ola",
+           "mel_cepstrum_response", "mel_cepstrum_response_torch", "mel_cepstrum_tables", "mel_cepstrum_basis",
+           "mel_cepstrum_rows", "mel_cepstrum_kernel_takes"]
 
 HAVE_TRANSITIONS = 1
 FAST_TRANSITIONS = 2
@@ -1776,6 +1778,103 @@ def stft_filter_frames(x, H, window, hop: int) -> torch.Tensor:
     if T <= n // 2:
         raise _lib.GolfError(f"stft_filter_frames: {T} samples cannot be reflect-padded by n_fft/2 = {n // 2}")
     return _STFTFilterFrames.apply(x, H, window, int(hop))
+
+
+# ------------------------------------------------------------------------------------------------
+# mel-cepstral filter design: mel cepstra -> complex minimum-phase response rows (include/golf_amd.h, csrc/mlsa_design.hip)
+# ------------------------------------------------------------------------------------------------
+def mel_cepstrum_tables(n_fft: int, order: int, alpha: float, dtype=torch.float32, device=None):
+    """cos(m theta_k) and sin(m theta_k), (order + 1, n_fft/2 + 1) each, evaluated in float64 and rounded to ``dtype``;
+    theta_k = w_k + 2 atan2(alpha sin w_k, 1 - alpha cos w_k) is the all-pass phase warp of w_k = 2 pi k / n_fft.  The sine
+    is exactly 0 at bins 0 and n_fft/2 (sin(m pi) is 1e-14 in float64), so that the response is real there."""
+    w = 2.0 * math.pi * torch.arange(n_fft // 2 + 1, dtype=torch.float64, device=device) / n_fft
+    theta = w + 2.0 * torch.atan2(alpha * torch.sin(w), 1.0 - alpha * torch.cos(w))
+    angle = torch.arange(order + 1, dtype=torch.float64, device=device).unsqueeze(1) * theta
+    c, s = torch.cos(angle), torch.sin(angle)
+    s[:, 0] = s[:, -1] = 0
+    return c.to(dtype), s.to(dtype)
+
+
+def mel_cepstrum_response_torch(mc: torch.Tensor, n_fft: int, alpha: float, tables=None) -> torch.Tensor:
+    """The definition of ``mel_cepstrum_response`` in plain torch, in ``mc``'s precision and on its device: two real
+    contractions with ``mel_cepstrum_tables`` (built here unless passed), exp of the complex logarithm.  What CPU tensors,
+    float64 and the geometries the kernel refuses run, and what the kernel is timed against."""
+    c, s = tables if tables is not None else mel_cepstrum_tables(n_fft, mc.shape[-1] - 1, alpha, mc.dtype, mc.device)
+    return torch.exp(torch.complex(mc @ c, -(mc @ s)))
+
+
+def mel_cepstrum_kernel_takes(n_fft: int, order: int, alpha: float) -> bool:
+    """Whether golf_mlsa_response_rows_f32 covers the geometry: n_fft a power of two in [64, 2048], order <= 64, |alpha| < 1."""
+    return n_fft & (n_fft - 1) == 0 and 64 <= n_fft <= 2048 and 0 <= order <= 64 and -1.0 < alpha < 1.0
+
+
+def mel_cepstrum_basis(n_fft: int, order: int, alpha: float, device) -> torch.Tensor:
+    """The kernel's basis for (n_fft, order, alpha) on ``device`` (golf_mlsa_response_basis_f32), a flat fp32 tensor holding
+    ``mel_cepstrum_tables`` with rows padded to n_fft/2 + 64.  Enqueued on the current stream; the caller owns it.  Raises
+    ``GolfError`` for a geometry the kernel refuses."""
+    if torch.device(device).type != "cuda":
+        raise _lib.GolfError("golf_amd kernels need ROCm device tensors (mel_cepstrum_basis on %s); there is no CPU path"
+                             % torch.device(device).type)
+    lib = _lib.load()
+    nbytes = lib.golf_mlsa_response_basis_bytes(int(n_fft), int(order))
+    b = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=device)   # never a null pointer: the entry names the reason
+    with torch.cuda.device(b.device):
+        _lib.check(lib.golf_mlsa_response_basis_f32(int(n_fft), int(order), float(alpha), b.data_ptr(), nbytes,
+                                                    _lib.stream_ptr()), "golf_mlsa_response_basis_f32")
+    return b
+
+
+def mel_cepstrum_rows(mc: torch.Tensor, basis: torch.Tensor, n_fft: int) -> torch.Tensor:
+    """(..., order + 1) fp32 mel cepstra on the device -> (..., n_fft/2 + 1) complex64 response rows
+    (golf_mlsa_response_rows_f32; no autograd).  ``basis`` from ``mel_cepstrum_basis`` for the same n_fft and order."""
+    _lib.require_device(mc, basis)
+    mc = mc.detach().contiguous()
+    h = torch.empty(*mc.shape[:-1], n_fft // 2 + 1, 2, dtype=torch.float32, device=mc.device)
+    if mc.numel() == 0:   # an empty block of a stream: no rows, no launch (and no pointer to pass)
+        return torch.view_as_complex(h)
+    _lib.check(_lib.load().golf_mlsa_response_rows_f32(mc.data_ptr(), basis.data_ptr(), basis.numel() * 4, h.data_ptr(),
+                                                       mc.numel() // mc.shape[-1], int(n_fft), mc.shape[-1] - 1,
+                                                       _lib.stream_ptr()), "golf_mlsa_response_rows_f32")
+    return torch.view_as_complex(h)
+
+
+class _MelCepstrumRows(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, mc, basis, n_fft):
+        h = mel_cepstrum_rows(mc, basis, n_fft)
+        ctx.save_for_backward(mc.detach().contiguous(), basis)
+        ctx.n_fft = n_fft
+        return h
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g_h):
+        mc, basis = ctx.saved_tensors
+        g = torch.view_as_real(g_h.resolve_conj().to(torch.complex64).contiguous())
+        g_mc = torch.empty_like(mc)   # written in full
+        if mc.numel() == 0:
+            return g_mc, None, None
+        _lib.check(_lib.load().golf_mlsa_response_rows_bwd_f32(g.data_ptr(), mc.data_ptr(), basis.data_ptr(), basis.numel() * 4,
+                                                               g_mc.data_ptr(), mc.numel() // mc.shape[-1], ctx.n_fft,
+                                                               mc.shape[-1] - 1, _lib.stream_ptr()),
+                   "golf_mlsa_response_rows_bwd_f32")
+        return g_mc, None, None
+
+
+def mel_cepstrum_response(mc: torch.Tensor, n_fft: int, alpha: float, basis: torch.Tensor = None) -> torch.Tensor:
+    """(..., M + 1) mel cepstra -> (..., n_fft/2 + 1) complex minimum-phase response rows H = exp(sum_m mc[m] e^{-j m theta_k})
+    on the warped frequencies theta_k (include/golf_amd.h; gamma = 0).  fp32 tensors on a ROCm device -- fp16 / bf16 under
+    autocast -- with a geometry the kernel takes (``mel_cepstrum_kernel_takes``) run golf_mlsa_response_rows_{,bwd_}f32:
+    differentiable w.r.t. ``mc``, a row's bits independent of the other rows.  ``basis``: the ``mel_cepstrum_basis`` of
+    (n_fft, M, alpha), built per call when None (a module keeps its own).  Everything else -- CPU tensors, float64, n_fft =
+    1000, M > 64 -- is ``mel_cepstrum_response_torch``."""
+    dtypes = (torch.float32, torch.float16, torch.bfloat16) if torch.is_autocast_enabled() else (torch.float32,)
+    if not (mc.is_cuda and mc.dtype in dtypes and mel_cepstrum_kernel_takes(int(n_fft), mc.shape[-1] - 1, float(alpha))):
+        return mel_cepstrum_response_torch(mc, int(n_fft), float(alpha))
+    if basis is None:
+        basis = mel_cepstrum_basis(n_fft, mc.shape[-1] - 1, alpha, mc.device)
+    return _MelCepstrumRows.apply(mc, basis, int(n_fft))
 
 
 # ------------------------------------------------------------------------------------------------

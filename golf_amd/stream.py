@@ -1148,15 +1148,15 @@ def _is_glottal(osc) -> bool:
 
 def _branch_kind(f) -> Optional[str]:
     """"pass" / "fir" / "frames" / "stft" for PassThrough, the plain zero-phase FIR, the frame-wise LPC filter and the
-    STFT-domain filters (LTVCepFilter, DiffWorldSPFilter); None otherwise."""
+    STFT-domain filters (LTVCepFilter, LTVMLSAFilter2, DiffWorldSPFilter); None otherwise."""
     from .ctrl import PassThrough
-    from .filters import DiffWorldSPFilter, LTVCepFilter, LTVMinimumPhaseFilter, LTVZeroPhaseFIRFilter
+    from .filters import DiffWorldSPFilter, LTVCepFilter, LTVMinimumPhaseFilter, LTVMLSAFilter2, LTVZeroPhaseFIRFilter
 
     if type(f) is PassThrough:
         return "pass"
     if _plain(f, LTVZeroPhaseFIRFilter):
         return "fir"
-    if type(f) in (LTVCepFilter, DiffWorldSPFilter):
+    if type(f) in (LTVCepFilter, LTVMLSAFilter2, DiffWorldSPFilter):
         return "stft"
     return "frames" if type(f) is LTVMinimumPhaseFilter else None
 
@@ -1427,7 +1427,7 @@ class HarmonicPlusNoiseStream(_Stream):
     Inference only; one stream for the whole batch."""
     _COVERS = ("it covers HarmonicPlusNoiseSynth with the harmonic oscillator bank -- HarmonicOscillator, AdditiveSynthesizer, "
                "V1AdditiveSynthesizer, SawToothOscillator, AdditivePulseTrain -- or an indexed glottal table; PassThrough, "
-               "LTVZeroPhaseFIRFilter, LTVMinimumPhaseFilter, LTVCepFilter or DiffWorldSPFilter (centred, n_fft a power of two "
+               "LTVZeroPhaseFIRFilter, LTVMinimumPhaseFilter, LTVCepFilter, LTVMLSAFilter2 or DiffWorldSPFilter (centred, n_fft a power of two "
                "in [64, 2048]) on each branch; standard normal noise or noise pushed with "
                "every block; PassThrough or LTIAcousticFilter as the end filter; voicing at the phase's hop")
 
@@ -1508,7 +1508,7 @@ class SpectralDecoderStream(_Stream):
     Inference only; one stream for the whole batch."""
     _COVERS = ("it covers SourceFilterSynth with the harmonic oscillator bank -- HarmonicOscillator, AdditiveSynthesizer, "
                "V1AdditiveSynthesizer, SawToothOscillator, AdditivePulseTrain --, standard normal noise or noise pushed with "
-               "every block, the zero-phase FIR noise filter or none, LTVCepFilter or DiffWorldSPFilter (centred, n_fft a "
+               "every block, the zero-phase FIR noise filter or none, LTVCepFilter, LTVMLSAFilter2 or DiffWorldSPFilter (centred, n_fft a "
                "power of two in [64, 2048]) as the end filter, the LTI room filter or none")
 
     def __init__(self, decoder, batch_size: int):

@@ -1036,6 +1036,39 @@ int golf_min_phase_fir_kernels_f32(const float* log_mag, const float* window, co
 int golf_min_phase_fir_kernels_bwd_f32(const float* g_kern, const float* log_mag, const float* window, const void* basis,
                                        float* g_log_mag, int G, int n_mag, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mel-cepstral filter design: mel cepstra -> complex minimum-phase response rows, the design step of LTVMLSAFilter2
+ * (models/filters.py:626-684; gamma = 0, the plain mel cepstrum, only).  The package's own definition, exact in float64,
+ * with N = n_fft, M = order, bins k = 0 .. N/2, w_k = 2 pi k / N:
+ *     theta_k = w_k + 2 atan2(alpha sin w_k, 1 - alpha cos w_k)              the all-pass phase warp; theta_0 = 0, theta_{N/2} = pi
+ *     L_k     = sum_{m=0..M} mc[m] (cos(m theta_k) - j sin(m theta_k))       the natural logarithm of H
+ *     H_k     = exp(Re L_k) (cos(Im L_k) + j sin(Im L_k))
+ * The warped cepstrum is causal, so Im L is the minimum phase.  The reference truncates the warped cepstrum at order N/2
+ * and takes the phase from a discrete Hilbert transform instead; the two agree to 5e-15 in L for N >= 256 with M <= 64 and
+ * alpha <= 0.77, and differ where the truncated tail is not negligible (2e-2 at N 128, 0.2 at N 64 with M 24, alpha 0.46):
+ * below N 256 this definition is the specification.
+ * Rows are (R, N/2+1, 2) interleaved complex -- the h_kind 1 layout of golf_stft_filter_frames_* -- with Im H exactly 0 at
+ * bins 0 and N/2.  A row's bits depend on its own mc row and the basis only (not on R, the row's position or its
+ * neighbours), which is what makes a streamed decoder equal the one-shot one bit for bit.
+ * `basis` holds cos(m theta_k) and sin(m theta_k) as fp32 values rounded once from a float64 evaluation (the sine exactly 0
+ * at bins 0 and N/2), built once per (n_fft, order, alpha) into a caller-owned buffer of golf_mlsa_response_basis_bytes()
+ * (0 for an unsupported geometry).
+ * Backward, with g_h in torch's complex convention (d/d re + j d/d im), P + jQ = conj(g_h_k) H_k:
+ *     g_mc[m] = sum_{k=0..N/2} (P_k cos(m theta_k) + Q_k sin(m theta_k))
+ * H is recomputed from mc; the bins are summed in a fixed order without atomics: bit-reproducible.
+ * Refused before any launch: null pointers (GOLF_EINVAL), n_fft not a power of two in [64, 2048] or order outside [0, 64]
+ * (GOLF_EUNSUPPORTED), |alpha| >= 1 (GOLF_EINVAL), a basis buffer shorter than golf_mlsa_response_basis_bytes()
+ * (GOLF_EWORKSPACE), R < 0 (GOLF_EINVAL).  R = 0 does nothing.  Nothing is allocated, nothing synchronises.
+ * ------------------------------------------------------------------------------------------- */
+size_t golf_mlsa_response_basis_bytes(int n_fft, int order);
+int golf_mlsa_response_basis_f32(int n_fft, int order, double alpha, void* basis, size_t basis_bytes, void* stream);
+/* mc (R, order+1) -> h (R, n_fft/2+1, 2) */
+int golf_mlsa_response_rows_f32(const float* mc, const void* basis, size_t basis_bytes, float* h, int R, int n_fft, int order,
+                                void* stream);
+/* g_h (R, n_fft/2+1, 2), mc (R, order+1) -> g_mc (R, order+1) */
+int golf_mlsa_response_rows_bwd_f32(const float* g_h, const float* mc, const void* basis, size_t basis_bytes, float* g_mc, int R,
+                                    int n_fft, int order, void* stream);
+
 /* Causal frame FIR, replaces LTVMinimumPhaseFIRFilter.forward, models/filters.py:270-283 (left pad by N-1, unfold
  * N+hop-1 samples every hop, correlate each frame with its flipped kernel):
  *     y[b, f*hop+n] = sum_{j<N} kernel[b,f,j] * ex[b, f*hop+n-j],   nfr = min(T / hop, F - frame0) frames,
