@@ -249,6 +249,9 @@ def cases():
     make("n256", 256, 60, voices(256), seed=20, unvoiced_f0=mid(256))
     make("n1024", 1024, 240, voices(1024), seed=30)
     make("n2048", 2048, 480, voices(2048), seed=40, unvoiced_f0=mid(2048))
+    # log2 n odd, like 2048: the kernel's ping-pong FFT ends in the other buffer
+    make("n128", 128, 15, voices(128), seed=15, unvoiced_f0=mid(128))
+    make("n512", 512, 120, voices(512), seed=25, unvoiced_f0=mid(512))
     # the clamps: f0 below f0_floor (the longest window) and above f0_ceil (the shortest), and one in between
     make("clamps", 1024, 240, [np.full(8, 50.0), np.full(8, 2500.0), np.full(8, 300.0)], seed=50)
     make("floor_1021", 1024, 240, [np.full(8, 40.0), np.full(8, 60.0), np.full(8, 70.0)], seed=55,

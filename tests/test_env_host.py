@@ -147,7 +147,7 @@ def test_copy_synthesis_returns_the_envelope():
 def test_cases_reach_their_edges():
     c = R.cases()
     assert all(v[0].shape[0] == 3 and 8 <= v[1].shape[1] <= 12 for v in c.values())
-    assert {v[2]["n_fft"] for v in c.values()} == {64, 256, 1024, 2048} and c["n64"][2]["hop"] == 8
+    assert {v[2]["n_fft"] for v in c.values()} == {64, 128, 256, 512, 1024, 2048} and c["n64"][2]["hop"] == 8
     assert c["n1024"][2]["hop"] == 240 and c["n1024"][2]["sample_rate"] == 24000.0
     ref = R.reference("clamps")
     assert (ref["hw"][0] == 511).all() and (ref["fe"][0] > 50.0).all()           # below the floor: 2 hw + 1 = n_fft - 1

@@ -9,7 +9,15 @@ Bars: the project's parity bar, 1e-4 (TOL of the LPC suites), per frame with no 
 coefficients (1e-6 absolute where the reference is exactly 0: silent frames), rc: absolute, gain: relative; g_x: rel-max
 and rel-L2 over the batch.  What clears the bar and what does not (CPU probe on this audio, against all-float64): the
 windowed frame rounded to fp32 with fp64 lags and recursion <= 2.5e-6; an fp32 recursion on exact lags 7e-4 .. 4e-3; fp32
-lags 1e-3 .. 9e-2.  The float64 gradient itself moves by 2.3e-6 rel-max under a 6e-8 relative perturbation of x."""
+lags 1e-3 .. 9e-2.  The float64 gradient itself moves by 2.3e-6 rel-max under a 6e-8 relative perturbation of x.
+
+The widest windows (W > 2048, two-wave workgroups) on the same CPU probe, the windowed frame rounded to fp32 and everything
+after it in fp64: forward W2049 a 4.3e-7, rc 1.7e-7, gain 1.5e-7; W4096_M64 a 1.1e-6, rc 2.6e-7, gain 1.6e-8.  The float64
+gradient moves under a 6e-8 relative perturbation of x by 2.2e-6 (W2049), 1.1e-5 (W4096_M64: a ninth of the bar) and 2.2e-6
+(W4095_from0).  Measured on an MI355X (forward a / rc / gain; the largest g_x rel-max over the four cotangent sets): W2049
+7.8e-7 / 2.1e-7 / 5.2e-8, g_x 5.6e-6; W4096_M64 1.1e-6 / 2.5e-7 / 7.1e-8, g_x 6.0e-6; W4095_from0 3.8e-8 / 2.4e-8 / 4.2e-8,
+g_x 1.5e-6; M1 3.0e-6 / 2.7e-8 / 7.8e-8, g_x 4.9e-8; M7 1.4e-7 / 3.1e-8 / 6.0e-8, g_x 9.7e-8; M63 2.3e-7 / 2.5e-8 / 5.5e-8,
+g_x 2.3e-7."""
 import functools
 
 import numpy as np
@@ -35,6 +43,15 @@ CASES = {
     "from0": (2, 4801, 960, 240, 22, False, None, "speech"),
     "more_frames": (5, 777, 50, 7, 13, True, 130, "noise"),
     "strided": (3, 1000, 256, 64, 16, True, None, "noise-strided"),
+    # W > 2048: two-wave workgroups (another LDS slice layout, another workgroup-to-frame mapping).  T = 4800, not 4801: the
+    # silent-stretch assertions hang on T == 4801 and presume windows of 960
+    "W2049": (3, 4800, 2049, 600, 22, True, None, "speech"),         # the first width on two waves, odd
+    "W4096_M64": (3, 4800, 4096, 1200, 64, True, None, "speech"),    # both limits
+    "W4095_from0": (3, 4800, 4095, 1200, 9, False, None, "speech"),  # F = 1: G = 3 leaves a two-wave workgroup half idle
+    # the orders at the ends of the lag passes and of the recursion's lanes
+    "M1": (5, 777, 50, 7, 1, True, None, "noise"),                   # the smallest order
+    "M7": (5, 777, 50, 7, 7, True, None, "noise"),                   # the last lag of the first LA_LAGS pass
+    "M63": (5, 777, 128, 7, 63, True, None, "noise"),                # one lane idle in the recursion
 }
 SILENT = slice(1500, 3500)   # row 1 of the speech cases with T = 4801
 COTANGENTS = ("all", "gain", "a", "rc")

@@ -32,6 +32,7 @@ CASES = [
     (2, 12, 17, 5, 56),
     (3, 1, 22, 240, 7),           # F = 1: one sample, e[0] = x[0] / gain[0]
     (2, 4, 30, 12, 56),           # clipped to (F - 1) hop + 1 = 37 samples
+    (8, 2, 2, 7, 8),              # one tile per row: the rows tests/test_gpu_grid_folds.py tiles past the grid's fold
 ]
 
 

@@ -18,7 +18,9 @@ from test_gpu_stream_stft import _call_args, _cep, _decoder, _fixed_noise, _inpu
 pytestmark = pytest.mark.gpu
 
 BAR = 1e-4
-GEOMETRIES = [(64, 24), (128, 32), (1024, 240), (2048, 600)]   # log2 n even and odd; the shared 64-lane block; 512 lanes
+# log2 n even and odd; the shared 64-lane block; 512 lanes; one frame per block of n/4 lanes from 256 on: a single wave (256)
+# and two waves with a radix-2 last stage (512)
+GEOMETRIES = [(64, 24), (128, 32), (256, 60), (512, 120), (1024, 240), (2048, 600)]
 
 
 def _np(t):

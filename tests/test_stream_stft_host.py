@@ -4,7 +4,9 @@ checks of golf_stft_filter_frames_stream_f32 (no launch)."""
 import numpy as np
 import pytest
 
-STFT = [(64, 24), (128, 32), (1024, 240)]   # (n_fft, hop): hop not dividing n_fft, the golden fixtures' shape, the shipped one
+# (n_fft, hop): hop not dividing n_fft, the golden fixtures' shape, the kernel's 64-lane block (the first size with one frame
+# per block), its 128-lane block with a radix-2 last stage, the shipped one
+STFT = [(64, 24), (128, 32), (256, 60), (512, 120), (1024, 240)]
 FIR = dict(taps=510, hop=240)               # the noise filter of both shipped decoders (n_mag 256 at hop 240)
 
 
